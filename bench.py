@@ -7,14 +7,18 @@ per-token reps from poses and patch coordinates on device (`gta_build_reps`), th
 metric configuration: the MSN-Hard `gta_so3` encoder attention (V=5 views of 128x128 images -> 16x16 patches/view ->
 1280 tokens, d=768 = 8 heads x 96 channels, f_dims se3 48 / so3 24 / so2 24), bf16, 32 scenes per GPU.
 
-    python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 The step goes through the C ABI with pre-planned buffers (gta_amd.plan: what a serving loop does -- no allocation, no
-autograd bookkeeping per call).  The dominant kernel's duration is taken inside the timed region from HIP events
-attached to its own dispatch (hipExtLaunchKernelGGL through the library's profiling hook, on the launch stream).
-After the timed region the output of the full-size batch is checked against the CPU oracle on sampled scenes
-(`parity_max_abs`).  `oracle/` is imported for that check and for the `cpu_baseline` leg only.
+autograd bookkeeping per call).  A plain run does only what the headline needs: set up, precondition and warm up, time
+the K steps, write the last step's output if `--dump-outputs DIR` is given, print the line.
+
+`--full` adds everything else, as one run: the cold-start figures, the dominant kernel's duration taken inside the timed
+region from HIP events attached to its own dispatch (hipExtLaunchKernelGGL through the library's profiling hook, on the
+launch stream) and the roofline built on it, the check of the full-size batch's output against the CPU oracle on
+sampled scenes (`parity_max_abs`), the forward + backward, block-layer, other-workload and whole-model legs, and the CPU
+baseline.  `oracle/` is imported for the parity check and the `cpu_baseline` leg only.
 
 Multi-GPU: data-parallel replicas (one process per GPU, fixed per-GPU batch -> "weak"); the operator has no exchange
 step, so there is no data-path collective -- only the barrier and the MAX-over-ranks of the timed region go through RCCL.
@@ -189,6 +193,26 @@ def precondition(fn, seconds, chunk=20):
         if torch.cuda.is_available():
             torch.cuda.synchronize()
     return n
+
+
+DUMP_MAX_BYTES = 32 << 20
+
+
+def output_sample(t, max_bytes=DUMP_MAX_BYTES):
+    """A [B, ...] output as float32 numpy: all of it if it fits in max_bytes, else the most whole scenes that fit, picked by a fixed seed
+    (the same scenes for the same B, so that two builds' dumps compare entry by entry).  -> (array, sorted scene indices)"""
+    B = t.shape[0]
+    n = max(1, min(B, max_bytes // (4 * (t.numel() // B))))
+    scenes = sorted(torch.randperm(B, generator=torch.Generator().manual_seed(0))[:n].tolist()) if n < B else list(range(B))
+    return t[torch.tensor(scenes, device=t.device)].float().cpu().contiguous().numpy(), scenes
+
+
+def dump_outputs(dirname, outputs):
+    """{name: [B, ...] tensor} -> dirname/<name>.npy (output_sample of each)"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in outputs.items():
+        np.save(os.path.join(dirname, name + ".npy"), output_sample(t)[0])
 
 
 class PlannedStep:
@@ -487,7 +511,7 @@ def dry_run(args):
     srt_train = None
     if args.model_train_steps < 0:
         args.model_train_steps = 5 if world > 1 else 0
-    if args.model_train_steps > 0:
+    if args.full and args.model_train_steps > 0:
         torch.manual_seed(7)
         model = torch.nn.Module()
         model.encoder = torch.nn.Sequential(torch.nn.Linear(16, 32), torch.nn.GELU(), torch.nn.Linear(32, 16))
@@ -567,13 +591,21 @@ def main():
     ap.add_argument("--workload", default="ms-enc", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default: the workload's)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run everything else this file measures or checks: cold start, per-kernel dispatch events and "
+                         "the roofline, the oracle parity check, the fwd_bwd, block-layer, other-workload and whole-model legs and the CPU "
+                         "baseline.  The options below that shape those legs act only with --full")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR",
+                    help="after the timed steps, write the output of the last one (the attention output [B, H, Tq, dh] a caller of the "
+                         "planned step receives) as DIR/out.npy in float32: the whole batch if it fits in 32 MB, else the most whole "
+                         "scenes that do, picked by a fixed seed.  Inputs are seeded, so the same arguments give the same inputs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the oracle check of the full-batch output")
     ap.add_argument("--model-train-steps", type=int, default=-1,
                     help="also time K optimizer steps of the whole MSN gta_so3 TransformingSRT (gta_amd.srt) on synthetic "
                          "multi-view batches, DDP over the ranks (RCCL's bucketed gradient all-reduce: the one collective of the "
                          "north star); reported as `srt_train`, not part of `value`.  Default: 5 when launched on more than one "
-                         "GPU (so the driver's `--gpus N --steps K --warmup W` line carries the collective), 0 on one GPU")
+                         "GPU (so a `--full` line of `--gpus N` carries the collective), 0 on one GPU")
     ap.add_argument("--model-batch", type=int, default=8, help="per-GPU scenes for --model-train-steps")
     ap.add_argument("--train-steps", type=int, default=10,
                     help="extra (untimed-for-`value`) forward+backward steps reported as fwd_bwd_* fields; 0 = skip")
@@ -596,7 +628,7 @@ def main():
                          "just built its inputs starts on an idle GPU; MI355X then grants the attention kernel 1.30-1.50 GHz for the first tens of "
                          "milliseconds and settles at 1.75-1.77 GHz after about a second of load, where it stays (tools/clock_ramp.py, "
                          "profiles/r05/raw/clock_ramp.txt: 0.197 ms/step from t = 1 s to t = 6 s).  `--steps 20 --warmup 5` is 6 ms of GPU work: "
-                         "without this phase `value` is a number about the clock ramp, not about the kernels.  The line reports both: `value` "
+                         "without this phase `value` is a number about the clock ramp, not about the kernels.  A --full line reports both: `value` "
                          "(sustained) and `cold_start` (W warmup + K steps from idle, what rounds 1-4 reported).  0 = no preconditioning, "
                          "value == the cold number")
     ap.add_argument("--kv-mode", dest="kv_mode", default="prepass", choices=["prepass", "fused", "prepass_rows32", "prepass_fwd2", "prepass_item_cxx", "prepass_bwd_keys32", "prepass_bwd_keys64", "prepass_bwd_split", "prepass_bwd_keys64_split"],
@@ -649,15 +681,15 @@ def main():
                      flags=(native.FLAG_FP32_PRODUCTS if args.precise else 0) | (native.FLAG_FUSED_KV if fused
                      else native.FLAG_ROWS32 if args.kv_mode == "prepass_rows32"
                      else (native.FLAG_ROWS32 | native.FLAG_FWD2_GENERIC) if args.kv_mode == "prepass_fwd2"
-                     else native.FLAG_ITEM_CXX if args.kv_mode == "prepass_item_cxx" else 0), time_kernel=not fused)
+                     else native.FLAG_ITEM_CXX if args.kv_mode == "prepass_item_cxx" else 0), time_kernel=args.full and not fused)
     step, fwd, q, k, v, exd, tc, ak, cross, kname, rows_it = ps.step, ps.fwd, ps.q, ps.k, ps.v, ps.exd, ps.tc, ps.ak, ps.cross, ps.kname, ps.rows_it
     qm, km, vm, ex = ps.masters
     Tq, Tk, dh = ps.Tq, ps.Tk, ps.dh
     dtype = ps.dtype
 
-    # ---- cold start (reported beside `value`): W warmup + K steps from the idle GPU this process starts on -- rounds 1-4's `value` ----
+    # ---- cold start (reported beside `value` by --full): W warmup + K steps from the idle GPU this process starts on -- rounds 1-4's `value` ----
     cold_start, precond = None, None
-    if args.precondition_s > 0:
+    if args.full and args.precondition_s > 0:
         for _ in range(args.warmup):
             step()
         torch.cuda.synchronize()
@@ -672,6 +704,7 @@ def main():
                       "kernel_ms": c_kern_ms, "frac": (c_flops / (c_kern_ms * 1e-3) / 1e12 / PEAK_BF16_TFLOPS) if c_kern_ms else None,
                       "kernel_cycles": c_cycles, "sclk_mhz": c_mhz,
                       "note": "this rank, W warmup + K steps right after the process built its inputs (idle GPU): the protocol of rounds 1-4"}
+    if args.precondition_s > 0:
         # ---- preconditioning: the same step, untimed, until the part has settled on its sustained clock ----
         tp0 = time.perf_counter()
         n_pre = precondition(step, args.precondition_s, 50)      # (synchronised every 50 steps: the host enqueues a step in 26 us, the GPU runs it in 200)
@@ -685,7 +718,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(i)
+        out = step(i)
     t_host = time.perf_counter() - t0                      # (host side of the loop: how far ahead of the GPU it runs)
     torch.cuda.synchronize()
     mine = time.perf_counter() - t0                        # this rank's own K steps (before it waits for the others)
@@ -701,26 +734,28 @@ def main():
         g = [torch.zeros(1, device=device, dtype=torch.float64) for _ in range(world)]
         dist.all_gather(g, torch.tensor([mine / args.steps * 1e3], device=device, dtype=torch.float64))
         per_rank = [float(u.item()) for u in g]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"out": out})
 
     kern_ms, kern_cycles, sclk_mhz = ps.kernel_times()
     n_kernel_samples = ps.n_samples
     ps.release_events()
     # every rank's granted shader clock and attention-kernel time (eight GPUs under load are not granted one clock)
     per_rank_sclk, per_rank_kern = [sclk_mhz], [kern_ms]
-    if dist is not None:
+    if dist is not None and args.full:
         g = [torch.zeros(2, device=device, dtype=torch.float64) for _ in range(world)]
         dist.all_gather(g, torch.tensor([sclk_mhz or 0.0, kern_ms or 0.0], device=device, dtype=torch.float64))
         per_rank_sclk = [float(u[0].item()) or None for u in g]
         per_rank_kern = [float(u[1].item()) or None for u in g]
 
     parity = None
-    if rank == 0 and not args.no_parity:
+    if args.full and rank == 0 and not args.no_parity:
         scenes = sorted({0, B // 3, (2 * B) // 3, B - 1})
         parity = parity_check(fwd.out, (qm, km, vm, ex), ak, cross, scenes)
 
     # forward + backward of the operator (gta_attn_bwd: q-side pre-pass, dQ, dK/dV), reported beside the headline
     fwd_bwd_ms, extra_errors = None, {}
-    if args.train_steps > 0:
+    if args.full and args.train_steps > 0:
         try:
             qg, kg, vg = (t.detach().clone().requires_grad_() for t in (q, k, v))
             tcg = tc.detach().clone().requires_grad_() if tc is not None else None
@@ -750,7 +785,7 @@ def main():
         except Exception as e:  # noqa: BLE001   (an extra leg: its failure is reported, the headline line is still printed)
             extra_errors["fwd_bwd"] = f"{type(e).__name__}: {str(e)[:300]}"
     block_layer = None
-    if args.block_steps > 0 and rank == 0 and args.workload == "ms-enc" and not args.dry_run:
+    if args.full and args.block_steps > 0 and rank == 0 and args.workload == "ms-enc" and not args.dry_run:
         try:
             block_layer = block_layer_leg(B, args.block_steps, device, min(0.6, args.precondition_s))
         except Exception as e:  # noqa: BLE001
@@ -759,7 +794,7 @@ def main():
     wl_names = ([w for w in ("ms-dec", "cl-enc", "cl-dec", "dit") if w != args.workload]
                 if (args.workloads == "auto" and args.workload == "ms-enc" and args.dtype == "bf16" and not fused and args.kv_mode == "prepass" and world <= 1)
                 else [] if args.workloads in ("auto", "none", "") else [w for w in args.workloads.split(",") if w])
-    if wl_names and rank == 0:
+    if args.full and wl_names and rank == 0:
         # the other BASELINE workloads (configs 2, 3's decoder, 5) on the same box, right behind the headline: what only the builder's
         # `workloads.jsonl` held before.  The headline's tensors are released first (ms-dec alone holds 0.6 GB).
         workloads = {}
@@ -782,7 +817,7 @@ def main():
                 workloads["render-cl"] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
             torch.cuda.empty_cache()
     srt_train = None
-    if args.model_train_steps > 0:
+    if args.full and args.model_train_steps > 0:
         # whole-model optimizer step (conv stem, 5 + 2 Transformer blocks on the HIP attention path,
         # render MLP, MSE loss, AdamW; bf16 autocast; DDP's bucketed gradient all-reduce over RCCL when world > 1)
         # (a failure of this extra leg must not take the headline line with it: it is reported, the line is still printed)
@@ -803,7 +838,7 @@ def main():
     flops = 4.0 * B * H * Tq * Tk * dh                               # QK^T + PV, 2 flop/MAC
     alg_bytes = (2 * Tq + 2 * Tk) * H * dh * q.element_size() * B    # read Q,K,V once, write O once
     achieved = flops / (kern_ms * 1e-3) / 1e12 if kern_ms else None
-    traffic, mfma_busy_sq, traffic_src = latest_traffic(args.workload, B, args.dtype, kname) if not fused else (None, None, None)
+    traffic, mfma_busy_sq, traffic_src = latest_traffic(args.workload, B, args.dtype, kname) if args.full and not fused else (None, None, None)
 
     if rank == 0:
         n = max(world, 1)
@@ -819,13 +854,16 @@ def main():
                                    f"B={B}/GPU, H={H}, Tq={Tq}, Tk={Tk}, dh={dh}, f_dims={f_dims}, "
                                    f"views q/k={Nq}/{Nk}" + (", fp32-faithful products (GTA_FLAG_FP32_PRODUCTS)" if args.precise else ""),
                        "global_batch": n * B, "parallelism": f"dp{n}"},
-            "protocol": ("sustained: K steps behind W warmup steps behind ~%.1f s of the same step untimed (r05 on); `cold_start` = rounds 1-4's protocol, same run"
-                         % args.precondition_s) if args.precondition_s > 0 else "cold: W warmup + K steps from whatever state the GPU was in (rounds 1-4's protocol)",
-            "preconditioning": precond, "cold_start": cold_start,
-            "host_ms_per_step": t_host / args.steps * 1e3, "per_rank_ms_per_step": per_rank, "extra_leg_errors": extra_errors or None,
-            "per_rank_sclk_mhz": per_rank_sclk, "per_rank_kernel_ms": per_rank_kern,
-            "dist": __import__("gta_amd.ddp", fromlist=["backend_info"]).backend_info(),
+            "protocol": ("sustained: K steps behind W warmup steps behind ~%.1f s of the same step untimed (r05 on)" % args.precondition_s
+                         + ("; `cold_start` = rounds 1-4's protocol, same run" if args.full else ""))
+                        if args.precondition_s > 0 else "cold: W warmup + K steps from whatever state the GPU was in (rounds 1-4's protocol)",
+            "preconditioning": precond,
+            "host_ms_per_step": t_host / args.steps * 1e3, "per_rank_ms_per_step": per_rank, "full": args.full,
         }
+        if args.full:
+            line.update({"cold_start": cold_start, "extra_leg_errors": extra_errors or None,
+                         "per_rank_sclk_mhz": per_rank_sclk, "per_rank_kernel_ms": per_rank_kern,
+                         "dist": __import__("gta_amd.ddp", fromlist=["backend_info"]).backend_info()})
         if achieved is not None:
             line["roofline"] = {"bound": "mfma", "kernel": kname, "rows_per_item": rows_it, "achieved": achieved,
                                 "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": achieved / PEAK_BF16_TFLOPS,
@@ -854,7 +892,7 @@ def main():
             line["workloads"] = workloads
         if srt_train is not None:
             line["srt_train"] = srt_train
-        if not args.no_cpu_baseline and n == 1:
+        if args.full and not args.no_cpu_baseline and n == 1:
             line["cpu_baseline"] = cpu_baseline(args.workload, 99)
         print(json.dumps(line), flush=True)
     if dist is not None:

@@ -99,7 +99,7 @@ def test_bench_launch_contract_dry_run_world2():
     import subprocess
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--dry-run"]
+           "--dry-run", "--full"]
     env = dict(os.environ, OMP_NUM_THREADS="1")
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -112,7 +112,7 @@ def test_bench_launch_contract_dry_run_world2():
     assert rec["ms_per_step"] >= max(rec["per_rank_ms_per_step"]) * 0.95
     assert rec["per_rank_ms_per_step"][1] > rec["per_rank_ms_per_step"][0]
     assert rec["config"]["global_batch"] == 64 and rec["config"]["parallelism"] == "dp2"
-    # launched on more than one rank without --model-train-steps, the line carries the whole-model leg: optimizer steps under the two
+    # launched on more than one rank with --full and without --model-train-steps, the line carries the whole-model leg: optimizer steps under the two
     # DDP instances of train.py:182-188 and the gradient all-reduce's bucket timeline (the north star's one collective)
     st = rec["srt_train"]
     assert st["steps"] == 5 and st["ms_per_step"] > 0 and st["scenes_per_s"] > 0 and st["ddp"].startswith("two DistributedDataParallel")

@@ -70,7 +70,7 @@ def test_rep_plan_equals_the_builders():
 
 
 def test_bench_line_contract_on_the_gpu():
-    """`bench.py` end to end with small counts (the driver's command line shape): ONE JSON line with the contract's keys, the roofline and
+    """`bench.py --full` end to end with small counts (the driver's command line shape): ONE JSON line with the contract's keys, the roofline and
     cpu-baseline objects, the r05 additions (`cold_start`, `preconditioning`, `workloads` with per-workload kernel time and parity) and no failed
     extra leg."""
     import json
@@ -79,7 +79,7 @@ def test_bench_line_contract_on_the_gpu():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--precondition-s", "0.05",
-                        "--workloads", "cl-enc", "--block-steps", "0", "--train-steps", "1", "--batch", "4"],
+                        "--workloads", "cl-enc", "--block-steps", "0", "--train-steps", "1", "--batch", "4", "--full"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -96,3 +96,31 @@ def test_bench_line_contract_on_the_gpu():
     assert "error" not in w and w["kernel"] == "gta_fwdc_kernel" and 0 < w["frac"] < 1 and len(w["ms_per_step_regions"]) == 3
     assert w["parity"]["parity_max_abs"] <= 2.5e-2 * w["parity"]["ref_max_abs"]
     assert d["cold_start"]["value"] > 0 and d["preconditioning"]["steps"] > 0
+
+
+def test_bench_plain_line_and_dumped_output(tmp_path):
+    """A plain `bench.py` run (no --full): the headline keys only, none of the --full legs, and `--dump-outputs` writes the last timed step's
+    output, which is the oracle's attention on the bench's seeded inputs."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--precondition-s", "0.05",
+                        "--batch", "4", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0 and not d["full"]
+    for key in ("roofline", "parity", "cpu_baseline", "cold_start", "workloads", "fwd_bwd", "block_layer", "srt_train"):
+        assert key not in d, key
+    out = np.load(tmp_path / "out.npy")
+    assert out.dtype == np.float32 and out.shape == (4, 8, 1280, 96) and np.isfinite(out).all()
+    q, k, v, ex, ak, cross = synth.attention_inputs(4, 8, 5, 256, 5, 256, MS, 6, 2, seed=1234)
+    idx = torch.tensor([3])
+    st = C.err_stats(torch.from_numpy(out[3:]), _oracle(q, k, v, ex, ak, cross, idx))
+    assert st["finite"] and st["max_abs"] <= 2.5e-2 * st["ref_max"] and st["rel_rms"] <= 1.2e-2, st

@@ -653,3 +653,23 @@ def test_bench_host_helpers():
     # the five BASELINE workloads (the default line times exactly these) + the `--workload`-only MSN layouts without the so3 slab (r06)
     assert set(bench.WORKLOADS) == {"ms-enc", "ms-dec", "cl-enc", "cl-dec", "dit", "ms-gta-enc", "ms-gta-dec", "ms-se3-enc"}
     assert os.environ.get("OMP_WAIT_POLICY") == "PASSIVE"
+
+
+def test_bench_output_sample(tmp_path):
+    """bench.py --dump-outputs: an output over the byte budget is cut to whole scenes picked by a fixed seed (the same ones on every call),
+    converted to float32; one inside the budget is written whole; the budget stays inside 64 MB."""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.DUMP_MAX_BYTES <= 64 << 20
+    t = torch.randn(40, 3, 5).to(torch.bfloat16)
+    a, scenes = bench.output_sample(t, max_bytes=4 * 15 * 7 + 3)
+    assert len(scenes) == 7 and scenes == sorted(set(scenes)) and scenes != list(range(7))
+    assert a.dtype == np.float32 and a.shape == (7, 3, 5) and np.array_equal(a, t[scenes].float().numpy())
+    assert bench.output_sample(t, max_bytes=4 * 15 * 7 + 3)[1] == scenes
+    assert bench.output_sample(t)[1] == list(range(40))
+    bench.dump_outputs(str(tmp_path / "d"), {"out": t.permute(0, 2, 1)})
+    assert np.array_equal(np.load(tmp_path / "d" / "out.npy"), t.permute(0, 2, 1).float().numpy())

@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 for i in 1 2 3; do
 for v in prev new; do
 LIB=$R/gta_amd/csrc/libgta_hip.so; [ $v = prev ] && LIB=$R/gta_amd/csrc/libgta_hip_prev.so
-GTA_HIP_LIB=$LIB timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$v$i -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-parity --block-steps 0 --train-steps 20 ${AB_ARGS} > $OUT/$v$i.log 2>&1
+GTA_HIP_LIB=$LIB timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$v$i -- python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-parity --block-steps 0 --train-steps 20 ${AB_ARGS} > $OUT/$v$i.log 2>&1
 f=$(ls $OUT/$v$i/*/*kernel_stats.csv | head -1)
 python - $f $v$i $OUT/$v$i.log <<'PY'
 import csv,sys,re

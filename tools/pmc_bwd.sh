@@ -1,7 +1,7 @@
 # PMC counters of the backward kernels (separate passes, --kernel-trace only)
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/pmc_bwd; rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="--no-cpu-baseline --no-parity --block-steps 0 --steps 2 --warmup 1 --train-steps 3"
+B="--full --no-cpu-baseline --no-parity --block-steps 0 --steps 2 --warmup 1 --train-steps 3"
 timeout 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA --kernel-trace --output-format csv -d $OUT/sq1 -- python $R/bench.py $B > $OUT/sq1.log 2>&1
 timeout 300 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU SQ_WAIT_INST_LDS SQ_LDS_ADDR_CONFLICT SQ_LDS_UNALIGNED_STALL --kernel-trace --output-format csv -d $OUT/sq2 -- python $R/bench.py $B > $OUT/sq2.log 2>&1
 python - $OUT <<'PY'

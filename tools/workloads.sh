@@ -5,10 +5,10 @@ OUT=$R/gpurun_out/prof_$ROUND
 mkdir -p $OUT
 : > $OUT/workloads.jsonl
 for w in ms-enc ms-dec cl-enc cl-dec dit; do
-  timeout 300 python $R/bench.py --workload $w --block-steps 0 2>/dev/null | tail -1 >> $OUT/workloads.jsonl
+  timeout 300 python $R/bench.py --full --workload $w --block-steps 0 2>/dev/null | tail -1 >> $OUT/workloads.jsonl
 done
 # the fp32-faithful mode at the CLEVR-TR encoder shape (runs/clevrtr/GTA/gta/config.yaml:55 mixed_prec: False)
-timeout 300 python $R/bench.py --workload cl-enc --dtype f32 --precise --block-steps 0 2>/dev/null | tail -1 >> $OUT/workloads.jsonl
+timeout 300 python $R/bench.py --full --workload cl-enc --dtype f32 --precise --block-steps 0 2>/dev/null | tail -1 >> $OUT/workloads.jsonl
 python - <<PY
 import json
 for l in open("$OUT/workloads.jsonl"):
