@@ -6,11 +6,7 @@ pre-pass, dQ, dK/dV) plus a deterministic reduction for ``d trans_coeff``.
 import torch
 
 from . import native
-
-
-def _rows_ok(t: torch.Tensor) -> bool:
-    esz = t.element_size()
-    return t.stride(3) == 1 and t.data_ptr() % 16 == 0 and all((s * esz) % 16 == 0 for s in t.stride()[:3])
+from .gta import _kernel_layout_ok
 
 
 def packed_slices(ts) -> bool:
@@ -47,7 +43,7 @@ def attn_bwd(cfg, q, k, v, out, dout, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k, k
     flags = flags & ~(native.FLAG_FUSED_KV | native.FLAG_KV_READY | native.FLAG_PREP_ONLY | native.FLAG_PERSIST)      # (GTA_FLAG_FP32_PRODUCTS stays: the X3 walks)
     dt = q.dtype
     dout = dout.to(dt)
-    if not _rows_ok(dout):
+    if not _kernel_layout_ok(dout):
         dout = dout.contiguous()
     B, H, Tq, dh = q.shape
     Tk = k.shape[2]

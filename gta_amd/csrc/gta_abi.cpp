@@ -18,12 +18,9 @@ int gta_fwd_lds_bytes(int dhp, int esz);
 int gta_fwd_dispatch(const GtaFwdParams& p, int dhp, int esz, bool dma, int n_wg, hipStream_t stream);
 long gta_fwd2_workspace_bytes(int B, int H, int Tk, int dhp, int Nq, int esz, bool x3);
 long gta_fwd2_qtiles_offset(int B, int H, int Tk, int dhp, bool x3);
-bool gta_fwd2_x3_takes(int dhp, int esz);                                              // fp32-faithful products on the two-stage plan
-int gta_fwd2_rows_per_item(const GtaFwdParams& p, int dhp, int esz);                   // 256: gta_attn64_kernel, 128: gta_fwd2_kernel
-const char* gta_fwd2_attention_kernel_name(const GtaFwdParams& p, int dhp, int esz);
 long gta_fwd2_image_bytes(int B, int H, int Tk, int dhp, bool x3);
 int gta_fwd2_lds_bytes(int dhp, int nq);
-int gta_fwd2_dispatch(GtaFwdParams& p, int dhp, int esz, bool run_prep, bool run_flash, hipStream_t stream);
+int gta_fwd2_dispatch(GtaFwdParams& p, const GtaFwdSel& s, int dhp, int esz, bool run_prep, bool run_flash, hipStream_t stream);
 int gta_bwd_dispatch(const GtaBwdParams& p, int dhp, int esz, hipStream_t stream);
 
 namespace {
@@ -96,6 +93,45 @@ int check_common(const GtaAttnDesc* d) {
     return GTA_OK;
 }
 
+// The fused forward's argument block for d and the operands of a call (null where the call has none).  A workspace holds the two-stage
+// plan's K'/V' tile images, per-tile key norms and (bf16 at dh = 96 with view reps) q-side rep tiles; the single-kernel plan reads none of them.
+int fwd_params(GtaFwdParams& p, const GtaAttnDesc* d, const void* q, const void* k, const void* v, const float* vrep_q, const float* vrep_k,
+               const float* cs_q, const float* cs_k, const float* trans_coeff, const float* tau, void* out, float* lse, void* workspace) {
+    memset(&p, 0, sizeof p);
+    if (int rc = build_ctab(d, p.ctab)) return rc;
+    const bool need_view = d->d_se3 > 0 || d->d_so3 > 0, need_cs = d->d_so2 > 0;
+    p.q = q; p.k = k; p.v = v; p.o = out; p.lse = lse;
+    p.vrep_q = need_view ? vrep_q : nullptr; p.vrep_k = need_view ? vrep_k : nullptr;
+    p.cs_q = need_cs ? cs_q : nullptr; p.cs_k = need_cs ? cs_k : nullptr;
+    p.trans_coeff = trans_coeff; p.tau = tau;
+    p.q_sb = d->q_stride[0]; p.q_sh = d->q_stride[1]; p.q_st = d->q_stride[2];
+    p.k_sb = d->k_stride[0]; p.k_sh = d->k_stride[1]; p.k_st = d->k_stride[2];
+    p.v_sb = d->v_stride[0]; p.v_sh = d->v_stride[1]; p.v_st = d->v_stride[2];
+    p.o_sb = d->o_stride[0]; p.o_sh = d->o_stride[1]; p.o_st = d->o_stride[2];
+    p.B = d->B; p.H = d->H; p.Tq = d->Tq; p.Tk = d->Tk; p.Nq = d->Nq; p.Nk = d->Nk;
+    p.Pq = d->Tq / d->Nq; p.Pk = d->Tk / d->Nk;
+    p.invPq = 1.0f / (float)p.Pq; p.invPk = 1.0f / (float)p.Pk;
+    p.dh = d->dh; p.nso2 = d->d_so2 / 2;
+    p.n_qtiles = (d->Tq + 127) / 128;
+    p.flags = d->flags; p.scale = d->scale;
+    if (workspace) {
+        const int dhp = padded_dh(d->dh);
+        p.kp = workspace;
+        p.kn = (float*)((char*)workspace + ((gta_fwd2_image_bytes(d->B, d->H, d->Tk, dhp, (d->flags & GTA_FLAG_FP32_PRODUCTS) != 0) + 255) & ~255L));
+        if (dhp == 96 && d->dtype == GTA_DTYPE_BF16 && need_view) p.qtiles = (char*)workspace + gta_fwd2_qtiles_offset(d->B, d->H, d->Tk, 96, false);
+    }
+    return GTA_OK;
+}
+
+// the forward instance of a full call with LSE and a workspace, for a supported d: every operand at one placeholder address (the selection
+// reads only whether a pointer is null and how it is aligned)
+GtaFwdSel full_call_selection(const GtaAttnDesc* d) {
+    float* const x = (float*)256;
+    GtaFwdParams p;
+    fwd_params(p, d, x, x, x, x, x, x, x, x, x, x, x, x);
+    return gta_fwd_select(p, padded_dh(d->dh), d->dtype == GTA_DTYPE_BF16 ? 2 : 4);
+}
+
 }  // namespace
 
 // debug hook (not part of the product ABI): device buffer [capacity_items][8] for the per-item s_memtime stamps of the NEXT attention
@@ -134,17 +170,11 @@ extern "C" int gta_attn_fwd_supported(const GtaAttnDesc* desc) {
     return check_common(desc);
 }
 
-// does this call run the two-stage plan when it is given a workspace?  (GTA_FLAG_FP32_PRODUCTS: where the split-bf16 instances exist)
-static bool two_stage_plan(const GtaAttnDesc* d) {
-    if (d->flags & (GTA_FLAG_FUSED_KV | GTA_FLAG_PRETRANSFORMED)) return false;
-    if (d->flags & GTA_FLAG_FP32_PRODUCTS) return gta_fwd2_x3_takes(padded_dh(d->dh), d->dtype == GTA_DTYPE_BF16 ? 2 : 4);
-    return true;
-}
 extern "C" int64_t gta_attn_fwd_workspace_bytes(const GtaAttnDesc* desc) {
     if (gta_attn_fwd_supported(desc)) return 0;
-    if ((desc->flags & GTA_FLAG_FP32_PRODUCTS) && !two_stage_plan(desc)) return 0;       // (that mode runs the single-kernel plan here)
-    return gta_fwd2_workspace_bytes(desc->B, desc->H, desc->Tk, padded_dh(desc->dh), desc->Nq, desc->dtype == GTA_DTYPE_BF16 ? 2 : 4,
-                                    (desc->flags & GTA_FLAG_FP32_PRODUCTS) != 0);
+    const bool x3 = (desc->flags & GTA_FLAG_FP32_PRODUCTS) != 0;
+    if (x3 && full_call_selection(desc).kind == GTA_FWD_SINGLE) return 0;       // (that mode runs the single-kernel plan here)
+    return gta_fwd2_workspace_bytes(desc->B, desc->H, desc->Tk, padded_dh(desc->dh), desc->Nq, desc->dtype == GTA_DTYPE_BF16 ? 2 : 4, x3);
 }
 
 extern "C" int gta_attn_fwd_launch_info(const GtaAttnDesc* desc, int32_t* lds_bytes, int32_t* n_workgroups,
@@ -161,21 +191,10 @@ extern "C" int gta_attn_fwd_launch_info(const GtaAttnDesc* desc, int32_t* lds_by
 // which attention kernel gta_attn_fwd launches for desc when given a workspace (diagnostic; the names are the kernels' own)
 extern "C" const char* gta_debug_attention_kernel(const GtaAttnDesc* d, int32_t* n_items, int32_t* rows_per_item) {
     if (gta_attn_fwd_supported(d)) return "";
-    GtaFwdParams p;
-    memset(&p, 0, sizeof p);
-    if (build_ctab(d, p.ctab)) return "";
-    const int esz = d->dtype == GTA_DTYPE_BF16 ? 2 : 4;
-    const bool need_view = d->d_se3 > 0 || d->d_so3 > 0;
-    p.B = d->B; p.H = d->H; p.Tq = d->Tq; p.Tk = d->Tk; p.dh = d->dh; p.flags = d->flags; p.kn = (float*)256; p.cs_q = d->d_so2 ? (const float*)256 : nullptr; p.kp = (void*)256;
-    // (what gta_attn_fwd would hand the dispatch for a full call with LSE: only null / non-null matters here)
-    p.Nq = d->Nq; p.Nk = d->Nk; p.Pq = d->Tq / d->Nq; p.Pk = d->Tk / d->Nk; p.nso2 = d->d_so2 / 2; p.lse = (float*)256;
-    p.vrep_q = need_view ? (const float*)256 : nullptr; p.q_st = d->q_stride[2]; p.o_st = d->o_stride[2];
-    p.qtiles = (padded_dh(d->dh) == 96 && esz == 2 && need_view) ? (void*)256 : nullptr;
-    const bool two_stage = two_stage_plan(d);
-    const int rows = !two_stage ? 128 : gta_fwd2_rows_per_item(p, padded_dh(d->dh), esz);
-    if (n_items) *n_items = d->B * d->H * ((d->Tq + rows - 1) / rows);
-    if (rows_per_item) *rows_per_item = rows;
-    return !two_stage ? "gta_fwd_kernel" : gta_fwd2_attention_kernel_name(p, padded_dh(d->dh), esz);
+    const GtaFwdSel s = full_call_selection(d);
+    if (n_items) *n_items = d->B * d->H * ((d->Tq + s.rows - 1) / s.rows);
+    if (rows_per_item) *rows_per_item = s.rows;
+    return s.name;
 }
 
 extern "C" int gta_attn_fwd(const GtaAttnDesc* d, const void* q, const void* k, const void* v,
@@ -186,59 +205,34 @@ extern "C" int gta_attn_fwd(const GtaAttnDesc* d, const void* q, const void* k, 
     if (rc) return rc;
     if (!k || !v || ((!q || !out) && !(d->flags & GTA_FLAG_PREP_ONLY))) return fail(GTA_E_BADARG, "null q/k/v/out");
     GtaFwdParams p;
-    memset(&p, 0, sizeof p);
-    rc = build_ctab(d, p.ctab);
+    rc = fwd_params(p, d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, out, lse, workspace);
     if (rc) return rc;
     const bool pre = (d->flags & GTA_FLAG_PRETRANSFORMED) != 0;
-    const bool need_view = d->d_se3 > 0 || d->d_so3 > 0;
-    const bool need_cs = d->d_so2 > 0;
-    if (need_view && (!vrep_q || (!pre && !vrep_k))) return fail(GTA_E_BADARG, "se3/so3 slabs need vrep_q and vrep_k");
-    if (need_cs && (!cs_q || (!pre && !cs_k))) return fail(GTA_E_BADARG, "so2 slab needs cs_q and cs_k");
-    const int esz = d->dtype == GTA_DTYPE_BF16 ? 2 : 4;
-    p.q = q; p.k = k; p.v = v; p.o = out; p.lse = lse;
-    p.vrep_q = need_view ? vrep_q : nullptr; p.vrep_k = need_view ? vrep_k : nullptr;
-    p.cs_q = need_cs ? cs_q : nullptr; p.cs_k = need_cs ? cs_k : nullptr;
-    p.trans_coeff = trans_coeff; p.tau = tau;
-    p.q_sb = d->q_stride[0]; p.q_sh = d->q_stride[1]; p.q_st = d->q_stride[2];
-    p.k_sb = d->k_stride[0]; p.k_sh = d->k_stride[1]; p.k_st = d->k_stride[2];
-    p.v_sb = d->v_stride[0]; p.v_sh = d->v_stride[1]; p.v_st = d->v_stride[2];
-    p.o_sb = d->o_stride[0]; p.o_sh = d->o_stride[1]; p.o_st = d->o_stride[2];
-    p.B = d->B; p.H = d->H; p.Tq = d->Tq; p.Tk = d->Tk; p.Nq = d->Nq; p.Nk = d->Nk;
-    p.Pq = d->Tq / d->Nq; p.Pk = d->Tk / d->Nk;
-    p.invPq = 1.0f / (float)p.Pq; p.invPk = 1.0f / (float)p.Pk;
-    p.dh = d->dh; p.nso2 = d->d_so2 / 2;
-    p.n_qtiles = (d->Tq + 127) / 128;
-    p.flags = d->flags; p.scale = d->scale;
+    if ((d->d_se3 > 0 || d->d_so3 > 0) && (!vrep_q || (!pre && !vrep_k))) return fail(GTA_E_BADARG, "se3/so3 slabs need vrep_q and vrep_k");
+    if (d->d_so2 > 0 && (!cs_q || (!pre && !cs_k))) return fail(GTA_E_BADARG, "so2 slab needs cs_q and cs_k");
+    const int dhp = padded_dh(d->dh), esz = d->dtype == GTA_DTYPE_BF16 ? 2 : 4;
 #ifdef GTA_ABLATE
     { const char* e = getenv("GTA_DBG"); p.dbg = e ? (uint32_t)atoi(e) : 0u; }
 #endif
+    const GtaFwdSel s = gta_fwd_select(p, dhp, esz);
     const long n_wg = (long)d->B * d->H * p.n_qtiles;
     if (t_prof && !(d->flags & GTA_FLAG_PREP_ONLY)) {      // (start / end stamps of every work item: gta_debug_profile_next_attention_kernel)
-        GtaFwdParams pk = p;
-        pk.kn = (float*)1;
-        const bool two_stage = workspace && two_stage_plan(d);
-        const int rows = two_stage ? gta_fwd2_rows_per_item(pk, padded_dh(d->dh), esz) : 128;
-        if ((int64_t)d->B * d->H * ((d->Tq + rows - 1) / rows) <= t_prof_items) p.prof = t_prof;
+        if ((int64_t)d->B * d->H * ((d->Tq + s.rows - 1) / s.rows) <= t_prof_items) p.prof = t_prof;
         t_prof = nullptr;
         t_prof_items = 0;
     }
     if (n_wg > 0x7fffffffL) return fail(GTA_E_UNSUPPORTED, "grid too large");
     if ((d->flags & GTA_FLAG_FP32_PRODUCTS) && d->dtype != GTA_DTYPE_F32)
         return fail(GTA_E_BADARG, "GTA_FLAG_FP32_PRODUCTS is for fp32 inputs (bf16 inputs ask for bf16 arithmetic)");
-    if (workspace && two_stage_plan(d)) {
-        const bool x3 = (d->flags & GTA_FLAG_FP32_PRODUCTS) != 0;
-        if (workspace_bytes < gta_fwd2_workspace_bytes(d->B, d->H, d->Tk, padded_dh(d->dh), d->Nq, esz, x3))
+    if (s.kind != GTA_FWD_SINGLE) {
+        if (workspace_bytes < gta_fwd2_workspace_bytes(d->B, d->H, d->Tk, dhp, d->Nq, esz, (d->flags & GTA_FLAG_FP32_PRODUCTS) != 0))
             return fail(GTA_E_BADARG, "workspace smaller than gta_attn_fwd_workspace_bytes()");
         if (d->H > 65535 || d->B > 65535) return fail(GTA_E_UNSUPPORTED, "B or H above 65535");
-        p.kp = workspace;
-        p.kn = (float*)((char*)workspace + ((gta_fwd2_image_bytes(d->B, d->H, d->Tk, padded_dh(d->dh), x3) + 255) & ~255L));
-        if (padded_dh(d->dh) == 96 && esz == 2 && need_view) p.qtiles = (char*)workspace + gta_fwd2_qtiles_offset(d->B, d->H, d->Tk, 96, false);
-        rc = gta_fwd2_dispatch(p, padded_dh(d->dh), esz, !(d->flags & GTA_FLAG_KV_READY), !(d->flags & GTA_FLAG_PREP_ONLY),
-                               (hipStream_t)stream);
+        rc = gta_fwd2_dispatch(p, s, dhp, esz, !(d->flags & GTA_FLAG_KV_READY), !(d->flags & GTA_FLAG_PREP_ONLY), (hipStream_t)stream);
         if (rc) return fail(rc, rc == GTA_E_LAUNCH ? hipGetErrorString(hipGetLastError()) : "no kernel instance");
         return GTA_OK;
     }
-    rc = gta_fwd_dispatch(p, padded_dh(d->dh), esz, !(d->flags & GTA_FLAG_NO_DMA), (int)n_wg, (hipStream_t)stream);
+    rc = gta_fwd_dispatch(p, dhp, esz, !(d->flags & GTA_FLAG_NO_DMA), (int)n_wg, (hipStream_t)stream);
     if (rc) return fail(rc, rc == GTA_E_LAUNCH ? hipGetErrorString(hipGetLastError()) : "no kernel instance");
     return GTA_OK;
 }
@@ -286,7 +280,8 @@ extern "C" int gta_attn_bwd(const GtaAttnDesc* d, const void* q, const void* k, 
     if (!q || !k || !v || !out || !dout || !lse || !dq || !dk || !dv || !dqkv_stride || !dout_stride || !workspace)
         return fail(GTA_E_BADARG, "null argument");
     if (d->flags & GTA_FLAG_PRETRANSFORMED) return fail(GTA_E_UNSUPPORTED, "backward of the pretransformed mode");
-    if ((d->flags & GTA_FLAG_FP32_PRODUCTS) && (d->dtype != GTA_DTYPE_F32 || padded_dh(d->dh) > 64))
+    const int dhp = padded_dh(d->dh), esz = d->dtype == GTA_DTYPE_BF16 ? 2 : 4;
+    if ((d->flags & GTA_FLAG_FP32_PRODUCTS) && !gta_x3_takes(dhp, esz))
         return fail(GTA_E_UNSUPPORTED, "GTA_FLAG_FP32_PRODUCTS backward: fp32 inputs at dh <= 64 (other sizes: gta_rep_apply + gta_attn_bwd_plain_f32)");
     GtaBwdParams p;
     memset(&p, 0, sizeof p);
@@ -295,24 +290,16 @@ extern "C" int gta_attn_bwd(const GtaAttnDesc* d, const void* q, const void* k, 
     const bool need_view = d->d_se3 > 0 || d->d_so3 > 0, need_cs = d->d_so2 > 0;
     if (need_view && (!vrep_q || !vrep_k)) return fail(GTA_E_BADARG, "se3/so3 slabs need vrep_q and vrep_k");
     if (need_cs && (!cs_q || !cs_k)) return fail(GTA_E_BADARG, "so2 slab needs cs_q and cs_k");
-    const int esz = d->dtype == GTA_DTYPE_BF16 ? 2 : 4;
     for (int i = 0; i < 9; ++i) if ((dqkv_stride[i] * esz) % 16) return fail(GTA_E_BADARG, "gradient strides must keep rows 16-byte aligned");
     for (int i = 0; i < 3; ++i) if ((dout_stride[i] * esz) % 16) return fail(GTA_E_BADARG, "dout strides must keep rows 16-byte aligned");
     const BwdLayout L = bwd_layout(d);
     if (workspace_bytes < L.total) return fail(GTA_E_BADARG, "workspace smaller than gta_attn_bwd_workspace_bytes()");
     char* ws = (char*)workspace;
-    if (!kv_images) {     // recompute K'/V' images with the forward's pre-pass
+    if (!kv_images) {     // recompute K'/V' images with the forward's pre-pass (GTA_FLAG_FP32_PRODUCTS: hi and lo images, as the X3 walks read them)
         GtaFwdParams f;
-        memset(&f, 0, sizeof f);
-        memcpy(f.ctab, p.ctab, sizeof f.ctab);
-        f.k = k; f.v = v; f.kp = ws + L.off_kv;
-        f.vrep_k = need_view ? vrep_k : nullptr; f.cs_k = need_cs ? cs_k : nullptr; f.trans_coeff = trans_coeff;
-        f.k_sb = d->k_stride[0]; f.k_sh = d->k_stride[1]; f.k_st = d->k_stride[2];
-        f.v_sb = d->v_stride[0]; f.v_sh = d->v_stride[1]; f.v_st = d->v_stride[2];
-        f.B = d->B; f.H = d->H; f.Tq = d->Tq; f.Tk = d->Tk; f.Nq = d->Nq; f.Nk = d->Nk;
-        f.Pq = d->Tq / d->Nq; f.Pk = d->Tk / d->Nk; f.invPq = 1.0f / f.Pq; f.invPk = 1.0f / f.Pk;
-        f.dh = d->dh; f.nso2 = d->d_so2 / 2; f.flags = d->flags; f.scale = d->scale;      // (GTA_FLAG_FP32_PRODUCTS: the pre-pass writes hi and lo images, as the X3 walks read them)
-        rc = gta_fwd2_dispatch(f, padded_dh(d->dh), esz, true, false, (hipStream_t)stream);
+        fwd_params(f, d, nullptr, k, v, nullptr, vrep_k, nullptr, cs_k, trans_coeff, nullptr, nullptr, nullptr, nullptr);
+        f.kp = ws + L.off_kv;
+        rc = gta_fwd2_dispatch(f, gta_fwd_select(f, dhp, esz), dhp, esz, true, false, (hipStream_t)stream);
         if (rc) return fail(rc, "K/V pre-pass launch failed");
         kv_images = ws + L.off_kv;
     }
@@ -336,7 +323,7 @@ extern "C" int gta_attn_bwd(const GtaAttnDesc* d, const void* q, const void* k, 
     p.Pq = d->Tq / d->Nq; p.Pk = d->Tk / d->Nk; p.invPq = 1.0f / (float)p.Pq; p.invPk = 1.0f / (float)p.Pk;
     p.dh = d->dh; p.nso2 = d->d_so2 / 2; p.flags = d->flags; p.scale = d->scale;
     if (d->H > 65535 || d->B > 65535) return fail(GTA_E_UNSUPPORTED, "B or H above 65535");
-    rc = gta_bwd_dispatch(p, padded_dh(d->dh), esz, (hipStream_t)stream);
+    rc = gta_bwd_dispatch(p, dhp, esz, (hipStream_t)stream);
     if (rc) return fail(rc, rc == GTA_E_LAUNCH ? hipGetErrorString(hipGetLastError()) : "no kernel instance");
     return GTA_OK;
 }

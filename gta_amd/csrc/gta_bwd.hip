@@ -1859,11 +1859,8 @@ int run_bwd(const GtaBwdParams& p, hipStream_t stream) {
     hipLaunchKernelGGL((gta_bwd_prep_kernel<DHP, ESZ>), dim3((unsigned)prep_grid), dim3(256), lds_prep, stream, p);
     const int n_dq = p.B * p.H * ((p.Tq + 127) / 128);
     const int n_dkv = p.B * p.H * ((p.Tk + 127) / 128);
-    bool ms_layout = false;
-    if constexpr (DHP == 96 && ESZ == 2) {
-        ms_layout = p.dh == 96 && p.nso2 == 12;          // (the generated kernels' epilogues are written for the MSN chunk layout)
-        for (int c = 0; c < 12; ++c) ms_layout = ms_layout && p.ctab[c] == gta_layout_desc(GTA_LAYOUT_MS, c);
-    }
+    // (the generated kernels' epilogues are written for the MSN chunk layout)
+    const bool ms_layout = DHP == 96 && ESZ == 2 && gta_layout_of(p.ctab, p.dh, DHP) == GTA_LAYOUT_MS;
     bool dq64 = false, dkv64 = false;
     if constexpr (DHP == 96 && ESZ == 2) {
         // 64 rows / keys per wave, 256 per workgroup (the generated streams) from half a chip of workgroups on (measured at B = 4 .. 32 per GPU at the MSN
@@ -1912,11 +1909,9 @@ int run_bwd(const GtaBwdParams& p, hipStream_t stream) {
 
 }  // namespace
 
-// the fp32-faithful backward on the matrix cores exists where the forward's two-stage X3 plan does: fp32 inputs, dh <= 64
-bool gta_bwd_x3_takes(int dhp, int esz) { return esz == 4 && dhp <= 64; }
 int gta_bwd_dispatch(const GtaBwdParams& p, int dhp, int esz, hipStream_t stream) {
-    if (p.flags & GTA_FLAG_FP32_PRODUCTS) {
-        if (!gta_bwd_x3_takes(dhp, esz)) return GTA_E_UNSUPPORTED;
+    if (p.flags & GTA_FLAG_FP32_PRODUCTS) {             // the fp32-faithful backward on the matrix cores (gta_fwd_params.h)
+        if (!gta_x3_takes(dhp, esz)) return GTA_E_UNSUPPORTED;
         return dhp == 32 ? run_bwd_x3<32>(p, stream) : run_bwd_x3<64>(p, stream);
     }
 #define GTA_CASEB(D) case D: return esz == 2 ? run_bwd<D, 2>(p, stream) : run_bwd<D, 4>(p, stream);

@@ -61,6 +61,17 @@ __host__ __device__ constexpr uint32_t gta_layout_desc(int layout, int c) {
          : layout == GTA_LAYOUT_SE3 ? (GTA_HALF_SE3 | (GTA_HALF_SE3 << 2))
          : gta_so2_desc(4 * c);
 }
+// (host) which compile-time layout, if any, the run-time chunk table of a dh-channel head is, for the instances of padded size dhp
+inline int gta_layout_of(const uint32_t* ctab, int dh, int dhp) {
+    if (dh != dhp) return GTA_LAYOUT_GENERIC;
+    for (int L : {GTA_LAYOUT_MS, GTA_LAYOUT_MSG, GTA_LAYOUT_SE3, GTA_LAYOUT_CL, GTA_LAYOUT_SO2}) {
+        if (((L == GTA_LAYOUT_MS || L == GTA_LAYOUT_MSG || L == GTA_LAYOUT_SE3) && dhp != 96) || (L == GTA_LAYOUT_CL && dhp != 64)) continue;
+        bool same = true;
+        for (int c = 0; c < dh / 8; ++c) same = same && ctab[c] == gta_layout_desc(L, c);
+        if (same) return L;
+    }
+    return GTA_LAYOUT_GENERIC;
+}
 
 // ---- bf16 <-> f32 -------------------------------------------------------------------------------
 GTA_DEV uint32_t pack_bf16x2(float lo, float hi) {

@@ -36,12 +36,9 @@
 #include "gta_flash_common.h"
 
 int gta_prep_dispatch(const GtaFwdParams& p, int dhp, int esz, hipStream_t stream);                  // gta_prep.hip
-bool gta_attn64_takes(const GtaFwdParams& p, int dhp, int layout, int esz);                                  // gta_fwd64.hip
-int gta_qtiles_dispatch(const GtaFwdParams& p, hipStream_t stream);
-int gta_attn64_dispatch(const GtaFwdParams& p, int esz, int layout, hipStream_t stream);
-const char* gta_attn64_kernel_name(const GtaFwdParams& p, int esz, int layout);
-bool gta_fwdc_takes(const GtaFwdParams& p, int dhp, int layout, int esz);                                    // gta_fwd_cl.hip
-int gta_fwdc_dispatch(const GtaFwdParams& p, int layout, hipStream_t stream);
+int gta_qtiles_dispatch(const GtaFwdParams& p, hipStream_t stream);                                  // gta_fwd64.hip
+int gta_attn64_dispatch(const GtaFwdParams& p, const GtaFwdSel& s, int esz, hipStream_t stream);
+int gta_fwdc_dispatch(const GtaFwdParams& p, int layout, hipStream_t stream);                        // gta_fwd_cl.hip
 
 // profiling hook (not part of the product ABI, see gta_hip.h): events for the NEXT attention-kernel launch of this thread
 thread_local void* gta_dbg_fwd_ev_start = nullptr;      // (also read by gta_fwd64.hip)
@@ -895,9 +892,6 @@ long gta_fwd2_qtiles_offset(int B, int H, int Tk, int dhp, bool x3) {
 long gta_fwd2_workspace_bytes(int B, int H, int Tk, int dhp, int Nq, int esz, bool x3) {
     return gta_fwd2_qtiles_offset(B, H, Tk, dhp, x3) + (dhp == 96 && esz == 2 ? (long)B * Nq * GTA_QT_TILES * GTA_QT_BYTES : 0L);
 }
-// the fp32-faithful mode on the two-stage plan: fp32 inputs at dh <= 64 (CLEVR-TR, runs/clevrtr/GTA/gta/config.yaml:55); other head sizes
-// keep the single-kernel plan (gta_fwd_kernel<..., x3>)
-bool gta_fwd2_x3_takes(int dhp, int esz) { return esz == 4 && dhp <= 64; }
 int gta_fwd2_lds_bytes(int dhp, int nrec) {
     switch (dhp) {
         case 32: return Smem2<32>::total(nrec);
@@ -908,45 +902,26 @@ int gta_fwd2_lds_bytes(int dhp, int nrec) {
     return -1;
 }
 
-// which compile-time layout (if any) the run-time chunk table is
-static int layout_of(const GtaFwdParams& p, int dhp) {
-    const int ch = p.dh / 8;
-    if (p.dh != dhp) return GTA_LAYOUT_GENERIC;
-    for (int L : {GTA_LAYOUT_MS, GTA_LAYOUT_MSG, GTA_LAYOUT_SE3, GTA_LAYOUT_CL, GTA_LAYOUT_SO2}) {
-        if (((L == GTA_LAYOUT_MS || L == GTA_LAYOUT_MSG || L == GTA_LAYOUT_SE3) && dhp != 96) || (L == GTA_LAYOUT_CL && dhp != 64)) continue;
-        bool same = true;
-        for (int c = 0; c < ch; ++c) same = same && p.ctab[c] == gta_layout_desc(L, c);
-        if (same) return L;
-    }
-    return GTA_LAYOUT_GENERIC;
-}
-
-int gta_fwd2_rows_per_item(const GtaFwdParams& p, int dhp, int esz) {
-    return !(p.flags & GTA_FLAG_FP32_PRODUCTS) && gta_attn64_takes(p, dhp, layout_of(p, dhp), esz) ? 256 : 128;
-}
-const char* gta_fwd2_attention_kernel_name(const GtaFwdParams& p, int dhp, int esz) {
-    if (p.flags & GTA_FLAG_FP32_PRODUCTS) return "gta_fwd2_kernel";
-    if (gta_attn64_takes(p, dhp, layout_of(p, dhp), esz)) return gta_attn64_kernel_name(p, esz, layout_of(p, dhp));
-    return gta_fwdc_takes(p, dhp, layout_of(p, dhp), esz) ? "gta_fwdc_kernel" : "gta_fwd2_kernel";
-}
-
 // Compile-time layouts exist for the shipped configs; others read the chunk table.
 template <int DHP, int ESZ>
-static int launch_flash(const GtaFwdParams& p, hipStream_t stream) {
-    if (p.flags & GTA_FLAG_FP32_PRODUCTS) {              // split-bf16 operands, three MFMAs per product: the X3 instances of the 32-row kernel
-        if constexpr (ESZ == 4 && DHP <= 64) {
-            switch (layout_of(p, DHP)) {
-                case GTA_LAYOUT_CL:  if (DHP == 64) return launch_fwd2<DHP, ESZ, (DHP == 64 ? GTA_LAYOUT_CL : GTA_LAYOUT_GENERIC), true>(p, stream); break;
-                case GTA_LAYOUT_SO2: return launch_fwd2<DHP, ESZ, GTA_LAYOUT_SO2, true>(p, stream);
+static int launch_flash(const GtaFwdParams& p, const GtaFwdSel& s, hipStream_t stream) {
+    switch (s.kind) {
+        case GTA_FWD_FWD2_X3:                            // split-bf16 operands, three MFMAs per product: the X3 instances of the 32-row kernel
+            if constexpr (ESZ == 4 && DHP <= 64) {
+                switch (s.layout) {
+                    case GTA_LAYOUT_CL:  if (DHP == 64) return launch_fwd2<DHP, ESZ, (DHP == 64 ? GTA_LAYOUT_CL : GTA_LAYOUT_GENERIC), true>(p, stream); break;
+                    case GTA_LAYOUT_SO2: return launch_fwd2<DHP, ESZ, GTA_LAYOUT_SO2, true>(p, stream);
+                }
+                return launch_fwd2<DHP, ESZ, GTA_LAYOUT_GENERIC, true>(p, stream);
+            } else {
+                return GTA_E_UNSUPPORTED;
             }
-            return launch_fwd2<DHP, ESZ, GTA_LAYOUT_GENERIC, true>(p, stream);
-        } else {
-            return GTA_E_UNSUPPORTED;
-        }
+        case GTA_FWD_ATTN64:
+        case GTA_FWD_ATTN64_ITEMS: return gta_attn64_dispatch(p, s, ESZ, stream);       // 64 rows per wave (gta_fwd64.hip)
+        case GTA_FWD_FWDC: return gta_fwdc_dispatch(p, s.layout, stream);                  // the dh = 64 bf16 instance (gta_fwd_cl.hip)
+        default: break;
     }
-    if (gta_attn64_takes(p, DHP, layout_of(p, DHP), ESZ)) return gta_attn64_dispatch(p, ESZ, layout_of(p, DHP), stream);   // 64 rows per wave (gta_fwd64.hip)
-    if (gta_fwdc_takes(p, DHP, layout_of(p, DHP), ESZ)) return gta_fwdc_dispatch(p, layout_of(p, DHP), stream);             // the dh = 64 bf16 instance (gta_fwd_cl.hip)
-    switch (layout_of(p, DHP)) {
+    switch (s.layout) {
         case GTA_LAYOUT_MS:  if (DHP == 96) return launch_fwd2<DHP, ESZ, (DHP == 96 ? GTA_LAYOUT_MS : GTA_LAYOUT_GENERIC)>(p, stream); break;
         case GTA_LAYOUT_CL:  if (DHP == 64) return launch_fwd2<DHP, ESZ, (DHP == 64 ? GTA_LAYOUT_CL : GTA_LAYOUT_GENERIC)>(p, stream); break;
         case GTA_LAYOUT_SO2: return launch_fwd2<DHP, ESZ, GTA_LAYOUT_SO2>(p, stream);
@@ -955,23 +930,22 @@ static int launch_flash(const GtaFwdParams& p, hipStream_t stream) {
 }
 
 // prep (unless the caller says K'/V' images are already in the workspace) + attention kernel.
-int gta_fwd2_dispatch(GtaFwdParams& p, int dhp, int esz, bool run_prep, bool run_flash, hipStream_t stream) {
+int gta_fwd2_dispatch(GtaFwdParams& p, const GtaFwdSel& s, int dhp, int esz, bool run_prep, bool run_flash, hipStream_t stream) {
     p.n_qtiles = (p.Tq + 127) / 128;
     p.n_items = p.B * p.H * p.n_qtiles;
     // view records a 128-row query tile can touch (staged per item, two buffers)
     p.nrec = 128 / p.Pq + 2 < p.Nq ? 128 / p.Pq + 2 : p.Nq;
     int rc = GTA_OK;
-    // the q-side rep tiles (rho_q / rho_q^-1 on the matrix cores) only where the 64-rows-per-wave kernel will use them
-    // (the operand tiles are the MSN gta_so3 layout's: GTA_LAYOUT_MS)
-    if (!(p.qtiles && esz == 2 && run_flash && layout_of(p, dhp) == GTA_LAYOUT_MS && gta_attn64_takes(p, dhp, GTA_LAYOUT_MS, esz))) p.qtiles = nullptr;
+    // the q-side rep tiles (rho_q / rho_q^-1 on the matrix cores) only where this call's attention kernel uses them
+    if (!run_flash || !s.qtiles) p.qtiles = nullptr;
     if (run_prep) rc = gta_prep_dispatch(p, dhp, esz, stream);
     else if (p.qtiles) rc = gta_qtiles_dispatch(p, stream);
     if (rc != GTA_OK || !run_flash) return rc;
     switch (dhp) {
-        case 32: return esz == 2 ? launch_flash<32, 2>(p, stream) : launch_flash<32, 4>(p, stream);
-        case 64: return esz == 2 ? launch_flash<64, 2>(p, stream) : launch_flash<64, 4>(p, stream);
-        case 96: return esz == 2 ? launch_flash<96, 2>(p, stream) : launch_flash<96, 4>(p, stream);
-        case 128: return esz == 2 ? launch_flash<128, 2>(p, stream) : launch_flash<128, 4>(p, stream);
+        case 32: return esz == 2 ? launch_flash<32, 2>(p, s, stream) : launch_flash<32, 4>(p, s, stream);
+        case 64: return esz == 2 ? launch_flash<64, 2>(p, s, stream) : launch_flash<64, 4>(p, s, stream);
+        case 96: return esz == 2 ? launch_flash<96, 2>(p, s, stream) : launch_flash<96, 4>(p, s, stream);
+        case 128: return esz == 2 ? launch_flash<128, 2>(p, s, stream) : launch_flash<128, 4>(p, s, stream);
     }
     return GTA_E_UNSUPPORTED;
 }

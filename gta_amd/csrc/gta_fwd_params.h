@@ -25,3 +25,21 @@ struct GtaFwdParams {
     float scale;
     uint32_t ctab[16];                          // chunk descriptors (gta_common.h)
 };
+
+// the split-bf16 (X3) instances of GTA_FLAG_FP32_PRODUCTS exist on the two-stage forward and in the backward for fp32 inputs at dh <= 64
+// (CLEVR-TR, runs/clevrtr/GTA/gta/config.yaml:55); other head sizes keep the single-kernel forward (gta_fwd_kernel<..., x3>)
+inline bool gta_x3_takes(int dhp, int esz) { return esz == 4 && dhp <= 64; }
+
+// which forward instance a call runs: gta_fwd_select (gta_fwd64.hip) decides once per call; the launches, the profiler's item count and
+// gta_debug_attention_kernel read the decision
+enum GtaFwdKind { GTA_FWD_SINGLE, GTA_FWD_FWD2, GTA_FWD_FWD2_X3, GTA_FWD_FWDC, GTA_FWD_ATTN64, GTA_FWD_ATTN64_ITEMS };
+struct GtaFwdSel {
+    GtaFwdKind kind;
+    int layout;                                 // GTA_LAYOUT_* the chunk table is (gta_common.h)
+    bool coal;                                  // attn64 kinds: the instance with coalesced item I/O
+    bool qtiles;                                // the attention kernel reads the q-side rep tiles (p.qtiles)
+    int rows;                                   // query rows per work item
+    const char* name;                           // the kernel's own name
+};
+// p: the argument block with the operands of the call (p.kp = the workspace or null; p.kn, p.qtiles inside it)
+GtaFwdSel gta_fwd_select(const GtaFwdParams& p, int dhp, int esz);

@@ -328,7 +328,7 @@ int launch_prep(const GtaFwdParams& p, hipStream_t stream) {
 }  // namespace
 
 int gta_prep_dispatch(const GtaFwdParams& p, int dhp, int esz, hipStream_t stream) {
-    if (p.flags & GTA_FLAG_FP32_PRODUCTS) {             // split-bf16 images (gta_fwd2_x3_takes: fp32 inputs, dh <= 64)
+    if (p.flags & GTA_FLAG_FP32_PRODUCTS) {             // split-bf16 images (gta_x3_takes: fp32 inputs, dh <= 64)
         if (esz != 4) return GTA_E_UNSUPPORTED;
         switch (dhp) {
             case 32: return launch_prep<32, 4, true>(p, stream);

@@ -162,6 +162,7 @@ def _as_kernel_layout(t: torch.Tensor) -> torch.Tensor:
 
 
 def _kernel_layout_ok(t: torch.Tensor) -> bool:
+    """unit channel stride, 16-B aligned base and row strides: what the kernels read (and write) a [B,H,T,dh] view as"""
     esz = t.element_size()
     return t.stride(3) == 1 and t.data_ptr() % 16 == 0 and all((s * esz) % 16 == 0 for s in t.stride()[:3])
 
@@ -471,92 +472,81 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
              full-image decode, trainer.py:137-181) stream them again without re-running the pre-pass."""
     if scale is None:
         scale = q.shape[-1] ** -0.5
-    explicit_fused = kv_mode == "fused"        # (asked for by name: with precise=True and gradients, the exact-fp32 route of r04 -- see below)
-    flags = 0
-    if v_transform:
-        flags |= native.FLAG_V_TRANSFORM
-    if euclid:
-        flags |= native.FLAG_EUCLID
-    if pretransformed:
-        flags |= native.FLAG_PRETRANSFORMED
-    if not use_dma:
-        flags |= native.FLAG_NO_DMA
-    if kv_mode == "prepass_pg":        # tuning knob: persistent grid instead of one workgroup per query tile
-        flags |= native.FLAG_PERSIST
-        kv_mode = "prepass"
-    if kv_mode == "prepass_rows32":    # tuning knob: keep the 32-rows-per-wave attention kernel where the 64-rows one would run
-        flags |= native.FLAG_ROWS32
-        kv_mode = "prepass"
-    if kv_mode == "prepass_fwd2":      # tuning knob (r06): the generic 32-row kernel gta_fwd2_kernel where the dh = 64 bf16 instance gta_fwdc_kernel would run
-        flags |= native.FLAG_ROWS32 | native.FLAG_FWD2_GENERIC
-        kv_mode = "prepass"
-    if kv_mode == "prepass_item_cxx":  # tuning knob: the 64-rows kernel with its compiler-scheduled item prologue / epilogue (not the item stream)
-        flags |= native.FLAG_ITEM_CXX
-        kv_mode = "prepass"
-    if kv_mode in ("prepass_bwd_keys32", "prepass_bwd_keys64", "prepass_bwd_split", "prepass_bwd_keys64_split"):
-        # tuning knobs of the backward: the 32-keys-per-wave dK/dV kernel / the generated 64-keys streams whatever the size / the dQ and dK/dV kernels
-        # (whichever pair the size selects; keys64_split: the generated pair) as two launches instead of the joint one
-        if "keys32" in kv_mode:
-            flags |= native.FLAG_BWD_KEYS32
-        if "keys64" in kv_mode:
-            flags |= native.FLAG_BWD_KEYS64
-        if kv_mode.endswith("split"):
-            flags |= native.FLAG_BWD_SPLIT
-        kv_mode = "prepass"
-    if kv_mode not in ("auto", "prepass", "fused"):
-        raise ValueError(f"kv_mode {kv_mode!r}")
-    precise = bool(precise)
-    if precise:
-        if q.dtype != torch.float32:
-            raise native.GtaError("precise=True is for float32 inputs (bf16 inputs ask for bf16 arithmetic)")
-        flags |= native.FLAG_FP32_PRODUCTS
-        # r05: at dh <= 64 (CLEVR-TR, the reference's fp32 config) the mode has a two-stage plan of its own -- the pre-pass writes hi and lo
-        # images, the 32-row kernel runs three MFMAs per product; other head sizes keep the single-kernel plan (asked of the library below)
-    if kv_cache is not None:
-        if torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (q, k, v, trans_coeff)):
-            raise native.GtaError("kv_cache is an inference feature: call under torch.no_grad()")
-        kv_mode = "prepass"
-    if kv_mode == "auto":
-        kv_mode = "prepass" if q.shape[2] > 256 else "fused"
-    Nq, Nk = _views(f_dims, packed, q, k)
-    if precise and kv_mode == "prepass" and q.is_cuda and not pretransformed:
-        # (probed with the tensors the kernel will see: _as_kernel_layout fixes unaligned strides that the raw views would be refused for)
-        def _shape_of(t):          # same shape in the layout the call will use (no data: only sizes, dtype and strides matter to the question)
-            return t if (t.dtype == q.dtype and _kernel_layout_ok(t)) else q.new_empty(t.shape)
-        qp_, kp_, vp_ = _shape_of(q), _shape_of(k), _shape_of(v)
-        probe = native.make_desc(qp_, kp_, vp_, qp_, f_dims, so3_degree, Nq, Nk, scale, flags)
-        if native.attn_fwd_workspace_bytes(probe) == 0:       # no split-bf16 two-stage instance at this head size
-            if kv_cache is not None:
-                raise native.GtaError("precise=True at this head size runs the single-kernel plan: no kv_cache")
-            kv_mode = "fused"
-    if kv_mode == "fused" or not use_dma:
-        flags |= native.FLAG_FUSED_KV
+    if kv_cache is not None and torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (q, k, v, trans_coeff)):
+        raise native.GtaError("kv_cache is an inference feature: call under torch.no_grad()")
     if isinstance(trans_coeff, (int, float)):
         trans_coeff = torch.tensor([float(trans_coeff)], device=q.device, dtype=torch.float32)
     if isinstance(tau, (int, float)):
         tau = None if float(tau) == 1.0 else torch.tensor([float(tau)], device=q.device, dtype=torch.float32)
     needs_grad = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (q, k, v, trans_coeff, tau))
-    if precise and needs_grad and not pretransformed:
-        # fp32-faithful TRAINING.  r06: where the fused kernels have split-bf16 instances on BOTH sides (fp32 inputs at dh <= 64: the two-stage forward
-        # of r05 and the X3 walks of gta_bwd.hip) the call stays on the fused path -- hi / lo images, three MFMAs per product, rho and its adjoint in
-        # fp32 inside the pre-passes and epilogues; the forward's images serve the backward.  Elsewhere: rho in fp32 (gta_rep_apply), split-bf16
-        # plain forward, EXACT-fp32 backward (gta_plain32.hip) and the adjoint rho kernels -- the generic path serves every layout that way.
-        fused_x3 = False
-        if q.is_cuda and q.shape[-1] <= 64 and not euclid and not explicit_fused:
-            qp_, kp_, vp_ = (t if (t.dtype == q.dtype and _kernel_layout_ok(t)) else q.new_empty(t.shape) for t in (q, k, v))
-            probe = native.make_desc(qp_, kp_, vp_, qp_, f_dims, so3_degree, Nq, Nk, scale, flags & ~native.FLAG_FUSED_KV)
-            fused_x3 = native.attn_fwd_supported(probe) == 0 and native.attn_fwd_workspace_bytes(probe) > 0
-        if not fused_x3:
-            return _generic_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, precise=True)
-        flags &= ~native.FLAG_FUSED_KV                       # (the two-stage plan whatever the number of query rows: its images are the backward's)
-    if q.is_cuda and not pretransformed:
-        probe = native.make_desc(q, k, v, q, f_dims, so3_degree, Nq, Nk, scale, flags)
-        if native.attn_fwd_supported(probe) == -3:       # GTA_E_UNSUPPORTED: valid request, no fused kernel
-            return _generic_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid,
-                                    precise=bool(precise))
+    Nq, Nk = _views(f_dims, packed, q, k)
+    flags = attention_route(tuple(q.shape), k.shape[2], q.dtype, f_dims, so3_degree, Nq, Nk, v_transform=v_transform, euclid=euclid,
+                            pretransformed=pretransformed, use_dma=use_dma, kv_mode=kv_mode, kv_cache=kv_cache is not None,
+                            precise=bool(precise), needs_grad=needs_grad)
+    if flags is None:
+        return _generic_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, precise=bool(precise))
     cfg = ({k_: int(v_) for k_, v_ in f_dims.items()}, int(so3_degree), Nq, Nk, float(scale), flags)
     return _GtaAttn.apply(q, k, v, trans_coeff, tau, kv_cache, cfg, packed.get("vrep_q"), packed.get("vrep_k"),
                           packed.get("cs_q"), packed.get("cs_k"))
+
+
+# kv_mode name -> flags of its tuning knob; every name but 'auto' and 'fused' asks for the two-stage plan ('prepass')
+KV_MODES = {
+    "auto": 0, "fused": 0, "prepass": 0,
+    "prepass_pg": native.FLAG_PERSIST,                                  # persistent grid instead of one workgroup per query tile
+    "prepass_rows32": native.FLAG_ROWS32,                               # the 32-rows-per-wave attention kernel where the 64-rows one would run
+    "prepass_fwd2": native.FLAG_ROWS32 | native.FLAG_FWD2_GENERIC,      # (r06) gta_fwd2_kernel where the dh = 64 bf16 instance gta_fwdc_kernel would run
+    "prepass_item_cxx": native.FLAG_ITEM_CXX,                           # the 64-rows kernel with its compiler-scheduled item prologue / epilogue
+    # the backward's: the 32-keys-per-wave dK/dV kernel / the generated 64-keys streams whatever the size / the dQ and dK/dV kernels (whichever
+    # pair the size selects; keys64_split: the generated pair) as two launches instead of the joint one
+    "prepass_bwd_keys32": native.FLAG_BWD_KEYS32,
+    "prepass_bwd_keys64": native.FLAG_BWD_KEYS64,
+    "prepass_bwd_split": native.FLAG_BWD_SPLIT,
+    "prepass_bwd_keys64_split": native.FLAG_BWD_KEYS64 | native.FLAG_BWD_SPLIT,
+}
+
+
+def attention_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree: int, Nq: int, Nk: int, *, v_transform: bool = True,
+                    euclid: bool = False, pretransformed: bool = False, use_dma: bool = True, kv_mode: str = "auto",
+                    kv_cache: bool = False, precise: bool = False, needs_grad: bool = False) -> Optional[int]:
+    """How ``gta_attention`` runs a call: the descriptor flags of the fused path, or None for the generic one (rho-apply kernels around the
+    plain attention kernel).  q_shape = (B, H, Tq, dh); Tk keys; dtype of q.
+
+    Sizes alone decide: the library is asked about a descriptor at contiguous strides, and its answers do not depend on strides that pass
+    its row-alignment check -- those and the ones ``_as_kernel_layout`` hands the kernels both do."""
+    if kv_mode not in KV_MODES:
+        raise ValueError(f"kv_mode {kv_mode!r}")
+    flags = (KV_MODES[kv_mode] | (native.FLAG_V_TRANSFORM if v_transform else 0) | (native.FLAG_EUCLID if euclid else 0)
+             | (native.FLAG_PRETRANSFORMED if pretransformed else 0) | (0 if use_dma else native.FLAG_NO_DMA))
+    if precise:
+        if dtype != torch.float32:
+            raise native.GtaError("precise=True is for float32 inputs (bf16 inputs ask for bf16 arithmetic)")
+        flags |= native.FLAG_FP32_PRODUCTS
+    B, H, Tq, dh = q_shape
+    qs, ks = (H * Tq * dh, Tq * dh, dh), (H * Tk * dh, Tk * dh, dh)
+    probe = lambda fl: native.make_desc_from(dtype, q_shape, Tk, (qs, ks, ks, qs), f_dims, so3_degree, Nq, Nk, 1.0, fl)
+    route = "prepass" if kv_cache or kv_mode.startswith("prepass") else kv_mode
+    if route == "auto":
+        route = "prepass" if Tq > 256 else "fused"
+    if precise and route == "prepass" and not pretransformed and native.attn_fwd_workspace_bytes(probe(flags)) == 0:
+        # r05: the mode has a two-stage plan of its own at dh <= 64 (CLEVR-TR, the reference's fp32 config) -- the pre-pass writes hi and lo
+        # images, the 32-row kernel runs three MFMAs per product; other head sizes keep the single-kernel plan
+        if kv_cache:
+            raise native.GtaError("precise=True at this head size runs the single-kernel plan: no kv_cache")
+        route = "fused"
+    if route == "fused" or not use_dma:
+        flags |= native.FLAG_FUSED_KV
+    if precise and needs_grad and not pretransformed:
+        # fp32-faithful TRAINING.  r06: where the fused kernels have split-bf16 instances on BOTH sides (fp32 inputs at dh <= 64: the two-stage forward
+        # of r05 and the X3 walks of gta_bwd.hip) the call stays on the fused path -- hi / lo images, three MFMAs per product, rho and its adjoint in
+        # fp32 inside the pre-passes and epilogues; the forward's images serve the backward -- on the two-stage plan whatever the number of query
+        # rows.  Elsewhere, and when kv_mode='fused' asks for it by name: rho in fp32 (gta_rep_apply), split-bf16 plain forward, EXACT-fp32
+        # backward (gta_plain32.hip) and the adjoint rho kernels -- the generic path serves every layout that way.
+        flags &= ~native.FLAG_FUSED_KV        # (use_dma=False too ends on the two-stage plan here: kept as it was, changing it is a change of behaviour)
+        return flags if kv_mode != "fused" and native.attn_fwd_workspace_bytes(probe(flags)) > 0 else None
+    if not pretransformed and native.attn_fwd_supported(probe(flags)) == -3:       # GTA_E_UNSUPPORTED: valid request, no fused kernel
+        return None
+    return flags
 
 
 def _closure_has_tau(attn_fn) -> bool:

@@ -223,21 +223,29 @@ def build_reps(transforms: torch.Tensor, so3_degree: int, coord: torch.Tensor, n
 def make_desc(q, k, v, out, f_dims: dict, so3_degree: int, Nq: int, Nk: int, scale: float,
               flags: int) -> GtaAttnDesc:
     """q/k/v/out are [B,H,T,dh] tensors (any strides with unit channel stride)."""
+    for name, t in (("q_stride", q), ("k_stride", k), ("v_stride", v), ("o_stride", out)):
+        if t.stride(3) != 1:
+            raise GtaError(f"{name}: channel stride must be 1")
+    return make_desc_from(q.dtype, tuple(q.shape), k.shape[2], [t.stride()[:3] for t in (q, k, v, out)], f_dims, so3_degree, Nq, Nk,
+                          scale, flags)
+
+
+def make_desc_from(dtype, q_shape, Tk: int, strides, f_dims: dict, so3_degree: int, Nq: int, Nk: int, scale: float,
+                   flags: int) -> GtaAttnDesc:
+    """make_desc from sizes alone: q_shape = (B, H, Tq, dh), strides = the (batch, head, token) element strides of q, k, v, out."""
     d = GtaAttnDesc()
     d.abi_version = GTA_ABI_VERSION
-    d.dtype = DTYPE_BF16 if q.dtype == torch.bfloat16 else DTYPE_F32
-    d.B, d.H, d.Tq, d.dh = q.shape
-    d.Tk = k.shape[2]
+    d.dtype = DTYPE_BF16 if dtype == torch.bfloat16 else DTYPE_F32
+    d.B, d.H, d.Tq, d.dh = q_shape
+    d.Tk = Tk
     d.Nq, d.Nk = Nq, Nk
     d.d_triv = int(f_dims.get("triv", 0)); d.d_se3 = int(f_dims.get("se3", 0))
     d.d_so3 = int(f_dims.get("so3", 0)); d.d_so2 = int(f_dims.get("so2", 0)); d.d_t2 = int(f_dims.get("t2", 0))
     d.so3_degree = int(so3_degree)
     d.flags = flags
     d.scale = float(scale)
-    for name, t in (("q_stride", q), ("k_stride", k), ("v_stride", v), ("o_stride", out)):
-        if t.stride(3) != 1:
-            raise GtaError(f"{name}: channel stride must be 1")
-        getattr(d, name)[:] = [t.stride(0), t.stride(1), t.stride(2)]
+    for name, st in zip(("q_stride", "k_stride", "v_stride", "o_stride"), strides):
+        getattr(d, name)[:] = list(st)
     return d
 
 

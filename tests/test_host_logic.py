@@ -632,6 +632,91 @@ def test_attention_kernel_selection_and_backward_workspace_without_gpu():
     assert 2 * img < w0 < 2 * img + 2 * 8 * 20 * 128 * 4 + 64 * 1024                     # + per-row statistics and the partial sums
 
 
+def test_attention_route_without_gpu():
+    """gta_attention's route from sizes alone (gta.attention_route: the fused call's flags, or None = the generic path).  The expected rows are
+    the routes the code before attention_route took: its gta_attention, run on the CPU with q.is_cuda reported True (so that it asked the
+    library what it asks for GPU inputs) and both paths intercepted."""
+    from gta_amd.gta import attention_route
+    WL = {     # (H, Nq, Tq, Nk, Tk, f_dims, so3 degree): the five BASELINE workloads, query sides of <= 256 rows, a layout without a fused kernel
+        "ms-enc": (8, 5, 1280, 5, 1280, {"se3": 48, "so3": 24, "so2": 24}, 2),
+        "ms-dec": (8, 5, 2560, 5, 1280, {"se3": 48, "so3": 24, "so2": 24}, 2),
+        "cl-enc": (6, 2, 600, 2, 600, {"se3": 32, "so2": 32}, 0),
+        "cl-dec": (6, 3, 2559, 2, 600, {"se3": 32, "so2": 32}, 0),
+        "dit": (16, 1, 1024, 1, 1024, {"so2": 64}, 0),
+        "cl-small": (6, 2, 256, 2, 600, {"se3": 32, "so2": 32}, 0),
+        "ms-small": (8, 1, 256, 5, 1280, {"se3": 48, "so3": 24, "so2": 24}, 2),
+        "t2": (4, 1, 512, 1, 512, {"se3": 32, "t2": 30, "triv": 2}, 0),
+    }
+    bf, f32 = torch.bfloat16, torch.float32
+    V, FK, X3 = "V_TRANSFORM", "FUSED_KV", "FP32_PRODUCTS"
+    GtaError = native.GtaError
+    cases = [  # (workload, dtype, options, flag names of the fused call / None: the generic path / the error raised)
+        ("ms-enc", bf, dict(), (V,)),
+        ("ms-enc", f32, dict(), (V,)),
+        ("ms-dec", bf, dict(), (V,)),
+        ("ms-dec", f32, dict(), (V,)),
+        ("cl-enc", bf, dict(), (V,)),
+        ("cl-enc", f32, dict(), (V,)),
+        ("cl-dec", bf, dict(), (V,)),
+        ("cl-dec", f32, dict(), (V,)),
+        ("dit", bf, dict(), (V,)),
+        ("dit", f32, dict(), (V,)),
+        ("ms-enc", bf, dict(needs_grad=True), (V,)),
+        ("cl-small", bf, dict(), (V, FK)),
+        ("ms-small", bf, dict(), (V, FK)),
+        ("t2", bf, dict(), None),
+        ("ms-enc", f32, dict(precise=True, kv_mode="auto"), (V, FK, X3)),
+        ("ms-enc", f32, dict(precise=True, kv_mode="auto", needs_grad=True), None),
+        ("ms-enc", f32, dict(precise=True, use_dma=False, needs_grad=True), None),
+        ("ms-enc", f32, dict(precise=True, pretransformed=True, needs_grad=True), (V, "PRETRANSFORMED", X3)),
+        ("ms-enc", f32, dict(precise=True, kv_cache=True), GtaError),
+        ("cl-enc", f32, dict(precise=True, kv_mode="auto"), (V, X3)),
+        ("cl-enc", f32, dict(precise=True, kv_mode="fused"), (V, FK, X3)),
+        ("cl-enc", f32, dict(precise=True, kv_mode="auto", needs_grad=True), (V, X3)),
+        ("cl-enc", f32, dict(precise=True, kv_mode="fused", needs_grad=True), None),
+        ("cl-enc", f32, dict(precise=True, use_dma=False), (V, FK, "NO_DMA", X3)),
+        ("cl-enc", f32, dict(precise=True, use_dma=False, needs_grad=True), (V, "NO_DMA", X3)),
+        ("cl-enc", f32, dict(precise=True, euclid=True, needs_grad=True), None),
+        ("cl-enc", f32, dict(precise=True, pretransformed=True, needs_grad=True), (V, "PRETRANSFORMED", X3)),
+        ("cl-enc", f32, dict(precise=True, kv_cache=True), (V, X3)),
+        ("cl-small", f32, dict(precise=True, kv_mode="auto"), (V, FK, X3)),
+        ("cl-small", f32, dict(precise=True, kv_mode="auto", needs_grad=True), (V, X3)),
+        ("dit", f32, dict(precise=True, kv_mode="auto", needs_grad=True), (V, X3)),
+        ("ms-small", f32, dict(precise=True, kv_mode="auto", needs_grad=True), None),
+        ("t2", f32, dict(precise=True, kv_mode="auto", needs_grad=True), None),
+        ("t2", f32, dict(precise=True, pretransformed=True), (V, "PRETRANSFORMED", X3)),
+        ("ms-enc", bf, dict(precise=True), GtaError),
+        ("ms-enc", bf, dict(kv_mode="bogus"), ValueError),
+        ("ms-enc", bf, dict(use_dma=False), (V, FK, "NO_DMA")),
+        ("ms-enc", bf, dict(kv_cache=True), (V,)),
+        ("ms-enc", bf, dict(kv_cache=True, kv_mode="fused"), (V,)),
+        ("t2", bf, dict(kv_cache=True), None),
+        ("ms-enc", bf, dict(pretransformed=True), (V, "PRETRANSFORMED")),
+        ("cl-small", bf, dict(pretransformed=True), (V, "PRETRANSFORMED", FK)),
+        ("ms-enc", bf, dict(euclid=True), None),
+        ("cl-enc", bf, dict(euclid=True), (V, "EUCLID")),
+        ("cl-small", bf, dict(v_transform=False), (FK,)),
+        ("ms-enc", bf, dict(kv_mode="prepass"), (V,)),
+        ("ms-enc", bf, dict(kv_mode="fused"), (V, FK)),
+        ("ms-enc", bf, dict(kv_mode="prepass_pg"), (V, "PERSIST")),
+        ("ms-enc", bf, dict(kv_mode="prepass_rows32"), (V, "ROWS32")),
+        ("ms-enc", bf, dict(kv_mode="prepass_fwd2"), (V, "FWD2_GENERIC", "ROWS32")),
+        ("ms-enc", bf, dict(kv_mode="prepass_item_cxx"), (V, "ITEM_CXX")),
+        ("ms-enc", bf, dict(kv_mode="prepass_bwd_keys32"), (V, "BWD_KEYS32")),
+        ("ms-enc", bf, dict(kv_mode="prepass_bwd_keys64"), (V, "BWD_KEYS64")),
+        ("ms-enc", bf, dict(kv_mode="prepass_bwd_split"), (V, "BWD_SPLIT")),
+        ("ms-enc", bf, dict(kv_mode="prepass_bwd_keys64_split"), (V, "BWD_KEYS64", "BWD_SPLIT")),
+    ]
+    for wl, dt, opts, want in cases:
+        H, Nq, Tq, Nk, Tk, f, L = WL[wl]
+        route = lambda: attention_route((1, H, Tq, sum(f.values())), Tk, dt, f, L, Nq, Nk, **opts)
+        if isinstance(want, type):
+            with pytest.raises(want):
+                route()
+        else:
+            assert route() == (None if want is None else sum(getattr(native, "FLAG_" + n) for n in want)), (wl, dt, opts)
+
+
 def test_bench_host_helpers():
     """bench.py's host-side helpers (r05): the container's CPU quota is read from the cgroup and bounds the thread counts the timed legs use;
     `precondition` runs its callable for the asked time in whole chunks; the workload table covers the five BASELINE workloads."""
