@@ -7,6 +7,7 @@
 #include "../../include/gta_hip.h"
 #include "gta_fwd_params.h"
 #include "gta_bwd_params.h"
+#include "gta_repgrad_params.h"
 
 // chunk-descriptor constants (mirrors gta_common.h, which is device-only)
 #define HALF_ID 0u
@@ -359,5 +360,86 @@ extern "C" int gta_attn_fwd_plain(const GtaAttnDesc* d, const void* q, const voi
     const long n_wg = (long)d->B * d->H * p.n_qtiles;
     int rc = gta_fwd_dispatch(p, padded_dh(d->dh), esz, true, (int)n_wg, (hipStream_t)stream);
     if (rc) return fail(rc, rc == GTA_E_LAUNCH ? hipGetErrorString(hipGetLastError()) : "no kernel instance");
+    return GTA_OK;
+}
+
+// -------------------------------------------------------------------------------------------------------------------------------
+// rep-gradient sums (gta_repgrad.hip)
+// -------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// the side's (T, N, tokens per workgroup, workgroups per view), or an error
+int repgrad_geometry(const GtaAttnDesc* d, int32_t side, int& T, int& N, int& tpb, long& chunks) {
+    if (!d) return fail(GTA_E_BADARG, "null descriptor");
+    if (d->abi_version != GTA_ABI_VERSION) return fail(GTA_E_BADARG, "abi_version mismatch");
+    if (side != 0 && side != 1) return fail(GTA_E_BADARG, "side must be 0 (query) or 1 (key)");
+    T = side ? d->Tk : d->Tq;
+    N = side ? d->Nk : d->Nq;
+    if (d->B <= 0 || d->H <= 0 || T <= 0 || N <= 0 || T % N) return fail(GTA_E_BADARG, "non-positive size or tokens not a multiple of views");
+    tpb = gta_repgrad_tpb(d->H);
+    if (!tpb) return fail(GTA_E_UNSUPPORTED, "rep-gradient sums serve at most 256 heads");
+    chunks = (T / N + tpb - 1) / tpb;
+    if ((long)d->B * N * chunks > 0x7fffffffL) return fail(GTA_E_UNSUPPORTED, "rep-gradient sums: grid too large");
+    return GTA_OK;
+}
+
+bool bad_operand(const void* ptr, const int64_t* st, int esz) {
+    return !ptr || !st || ((uintptr_t)ptr % esz) != 0 || st[0] < 0 || st[1] < 0 || st[2] < 0;
+}
+
+}  // namespace
+
+extern "C" int64_t gta_rep_grad_workspace_bytes(const GtaAttnDesc* d, int32_t side) {
+    int T, N, tpb;
+    long chunks;
+    if (int rc = repgrad_geometry(d, side, T, N, tpb, chunks)) return rc;
+    return (int64_t)d->B * N * chunks * 16 * (int64_t)sizeof(float);
+}
+
+extern "C" int gta_rep_grad_sums(const GtaAttnDesc* d, int32_t side, int32_t n_pairs,
+                                 const void* a0, const int64_t* a0_stride, const void* b0, const int64_t* b0_stride,
+                                 const void* a1, const int64_t* a1_stride, const void* b1, const int64_t* b1_stride,
+                                 float* view_sums, float* so2_sums, float* t2_sums,
+                                 void* workspace, int64_t workspace_bytes, void* stream) {
+    int T, N, tpb;
+    long chunks;
+    if (int rc = repgrad_geometry(d, side, T, N, tpb, chunks)) return rc;
+    if (d->dtype != GTA_DTYPE_F32 && d->dtype != GTA_DTYPE_BF16) return fail(GTA_E_BADARG, "dtype must be GTA_DTYPE_F32 or GTA_DTYPE_BF16");
+    if (n_pairs != 1 && n_pairs != 2) return fail(GTA_E_BADARG, "n_pairs must be 1 or 2");
+    if (!view_sums && !so2_sums && !t2_sums) return fail(GTA_E_BADARG, "no output requested");
+    const int esz = d->dtype == GTA_DTYPE_BF16 ? 2 : 4;
+    if (bad_operand(a0, a0_stride, esz) || bad_operand(b0, b0_stride, esz) ||
+        (n_pairs == 2 && (bad_operand(a1, a1_stride, esz) || bad_operand(b1, b1_stride, esz))))
+        return fail(GTA_E_BADARG, "null, misaligned or negatively strided operand");
+    if (d->d_triv < 0 || d->d_se3 < 0 || d->d_so3 < 0 || d->d_so2 < 0 || d->d_t2 < 0) return fail(GTA_E_LAYOUT, "negative slab size");
+    if (d->d_triv + d->d_se3 + d->d_so3 + d->d_so2 + d->d_t2 != d->dh) return fail(GTA_E_LAYOUT, "f_dims do not sum to dh");
+    const bool euclid = (d->flags & GTA_FLAG_EUCLID) != 0;
+    if (d->d_se3 % (euclid ? 3 : 4) || d->d_so2 % 2 || d->d_t2 % 3) return fail(GTA_E_LAYOUT, "se3 / so2 / t2 slab not a whole number of groups");
+    if ((view_sums && d->d_se3 == 0) || (so2_sums && d->d_so2 == 0) || (t2_sums && d->d_t2 == 0))
+        return fail(GTA_E_BADARG, "sums requested for an empty slab");
+    if (((uintptr_t)view_sums | (uintptr_t)so2_sums | (uintptr_t)t2_sums) % 4) return fail(GTA_E_BADARG, "misaligned output");
+    const int64_t need = (int64_t)d->B * N * chunks * 16 * (int64_t)sizeof(float);
+    if (view_sums && (!workspace || (uintptr_t)workspace % 4 || workspace_bytes < need))
+        return fail(GTA_E_BADARG, "view sums need a workspace of gta_rep_grad_workspace_bytes");
+    GtaRepGradParams p;
+    p.a[0] = a0; p.b[0] = b0;
+    p.a[1] = n_pairs == 2 ? a1 : a0; p.b[1] = n_pairs == 2 ? b1 : b0;
+    for (int i = 0; i < 3; ++i) {
+        p.as[0][i] = a0_stride[i]; p.bs[0][i] = b0_stride[i];
+        p.as[1][i] = n_pairs == 2 ? a1_stride[i] : a0_stride[i];
+        p.bs[1][i] = n_pairs == 2 ? b1_stride[i] : b0_stride[i];
+    }
+    p.npairs = n_pairs;
+    p.B = d->B; p.H = d->H; p.T = T; p.N = N; p.P = T / N;
+    p.tpb = tpb; p.chunks = (int)chunks;
+    p.off_se3 = d->d_triv;
+    p.n_se3 = view_sums ? d->d_se3 / (euclid ? 3 : 4) : 0;
+    p.off_so2 = d->d_triv + d->d_se3 + d->d_so3;
+    p.n_so2 = so2_sums ? d->d_so2 / 2 : 0;
+    p.off_t2 = p.off_so2 + d->d_so2;
+    p.n_t2 = t2_sums ? d->d_t2 / 3 : 0;
+    p.part = (float*)workspace; p.view_out = view_sums; p.so2_out = so2_sums; p.t2_out = t2_sums;
+    int rc = gta_repgrad_dispatch(p, esz, euclid, (hipStream_t)stream);
+    if (rc) return fail(rc, rc == GTA_E_LAUNCH ? hipGetErrorString(hipGetLastError()) : "grid too large");
     return GTA_OK;
 }

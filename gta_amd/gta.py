@@ -21,6 +21,7 @@ import os
 import torch
 
 from . import native
+from . import repgrad as _repgrad
 
 GROUP_ORDER = ("triv", "se3", "so3", "so2", "t2")   # gta.py:115
 
@@ -48,6 +49,15 @@ def make_SO2mats(coord: torch.Tensor, nfreqs: int, max_freqs=(1, 1), shared_freq
 def _pack_view(inv: Optional[torch.Tensor], rep: Optional[torch.Tensor], Ds) -> torch.Tensor:
     ref = inv if inv is not None else (rep if rep is not None else Ds[0])
     B, N = ref.shape[:2]
+    if native.wants_grad(inv, rep):
+        # built with torch ops so that the table's gradient (E / inv(E) slots) reaches the dense tensors; the D slots stay detached
+        z = torch.zeros(B, N, 16, device=ref.device, dtype=torch.float32)
+        tail = torch.zeros(B, N, native.VREP_STRIDE - 32, device=ref.device, dtype=torch.float32)
+        if Ds:
+            tail[..., native.VREP_D1 - 32:native.VREP_D1 - 23] = Ds[0].detach().reshape(B, N, 9)
+            if len(Ds) > 1:
+                tail[..., native.VREP_D2 - 32:native.VREP_D2 - 7] = Ds[1].detach().reshape(B, N, 25)
+        return torch.cat([z if inv is None else inv.reshape(B, N, 16).float(), z if rep is None else rep.reshape(B, N, 16).float(), tail], -1)
     out = torch.zeros(B, N, native.VREP_STRIDE, device=ref.device, dtype=torch.float32)
     if inv is not None:
         out[..., native.VREP_INV:native.VREP_INV + 16] = inv.detach().reshape(B, N, 16)
@@ -98,6 +108,10 @@ def pack_reps(reps: dict, f_dims: dict) -> dict:
     ``inv_se3rep_q``, ``so3rep_q/k`` lists, ``so2rep_q/k``, ``t2rep_q/k``; encoder.py:197,208-215,235-236,259).
     A table packed from reference tensors is tied to them (``*_src``): when the decoder replaces the q side of the
     shared dict (decoder.py:283-311), the table is rebuilt -- for all three kinds.
+
+    Reference tensors that require grad (poses, coordinates as autograd leaves): the view table is built with torch ops and never
+    cached (a cached one would belong to an earlier graph); the dense so2 / t2 tensors the operator applies are handed on as
+    ``grad_cs_*`` / ``grad_coord_*`` so that the backward returns their gradient in their own shape (gta_amd.repgrad).
     """
     need_view = f_dims.get("se3", 0) > 0 or f_dims.get("so3", 0) > 0
     need_so2 = f_dims.get("so2", 0) > 0
@@ -124,7 +138,10 @@ def pack_reps(reps: dict, f_dims: dict) -> dict:
             inv = reps.get("inv_se3rep_q") if side == "q" else None
             rep, so3 = reps.get(f"se3rep_{side}"), reps.get(f"so3rep_{side}")
             Ds = list(so3 or []) if f_dims.get("so3", 0) > 0 else []
-            out[f"vrep_{side}"] = cached(f"gta_vrep_{side}", (rep, inv, so3), lambda: _pack_view(inv, rep, Ds))
+            if native.wants_grad(inv, rep):
+                out[f"vrep_{side}"] = _pack_view(inv, rep, Ds)
+            else:
+                out[f"vrep_{side}"] = cached(f"gta_vrep_{side}", (rep, inv, so3), lambda: _pack_view(inv, rep, Ds))
     if f_dims.get("t2", 0) > 0:
         # make_T2mats (gta.py:72-89): T = [[1,0,0],[0,1,0],[cx,cy,1]] -> the kernel wants (cx, cy) per token
         for side in ("q", "k"):
@@ -132,10 +149,16 @@ def pack_reps(reps: dict, f_dims: dict) -> dict:
             out[f"coord_{side}"] = cached(
                 f"gta_coord_{side}", (T,),
                 lambda: torch.stack([T[..., 2, 0], T[..., 2, 1]], -1).detach().float().contiguous())
+            # the operator applies inv_t2rep_q on the q side and t2rep_k on the k side (gta.py:221-238,272-274)
+            src = reps.get("inv_t2rep_q") if side == "q" else T
+            if native.wants_grad(src):
+                out[f"grad_coord_{side}"] = src
     if need_so2:
         for side in ("q", "k"):
             R = reps.get(f"so2rep_{side}")
             out[f"cs_{side}"] = cached(f"gta_cs_{side}", (R,), lambda: _pack_so2(R))
+            if native.wants_grad(R):
+                out[f"grad_cs_{side}"] = R
     return out
 
 
@@ -222,7 +245,8 @@ class _GtaAttn(torch.autograd.Function):
     flash_events = None     # (start, end) torch.cuda.Event pair set by bench.py, else None
 
     @staticmethod
-    def forward(ctx, q, k, v, trans_coeff, tau, kv_cache, cfg, vrep_q, vrep_k, cs_q, cs_k):
+    def forward(ctx, q, k, v, trans_coeff, tau, kv_cache, cfg, vrep_q, vrep_k, cs_q, cs_k, *carriers):
+        # carriers: () or six tensors / None (gta_amd.repgrad.split_tables) whose gradients the backward returns
         f_dims, so3_degree, Nq, Nk, scale, flags = cfg
         dt = q.dtype
         if dt not in (torch.float32, torch.bfloat16):
@@ -288,6 +312,7 @@ class _GtaAttn(torch.autograd.Function):
         ctx.tc_shape = None if trans_coeff is None else trans_coeff.shape
         ctx.tc_dtype = None if trans_coeff is None else trans_coeff.dtype
         ctx.tau_meta = None if tau is None else (tau.shape, tau.dtype)
+        ctx.carriers = _repgrad.carrier_meta(carriers)
         return out
 
     @staticmethod
@@ -303,7 +328,18 @@ class _GtaAttn(torch.autograd.Function):
             dtc = None
         if dta is not None:
             dta = dta.reshape(ctx.tau_meta[0]).to(ctx.tau_meta[1])
-        return dq, dk, dv, dtc, dta, None, None, None, None, None, None
+        grads = ()
+        if ctx.carriers:
+            # gradients of the tables: a pass after the backward over (q, dq), (dout, out) and (dk, k), (dv, v) (gta_amd/repgrad.py)
+            meta = tuple(m if need else None for m, need in zip(ctx.carriers, ctx.needs_input_grad[11:]))
+            f_dims, so3_degree, Nq, Nk, scale, flags = ctx.cfg
+            desc = native.make_desc(q, k, v, out, f_dims, so3_degree, Nq, Nk, scale, flags)
+            do = _as_kernel_layout(dout.to(q.dtype))
+            vt = bool(flags & native.FLAG_V_TRANSFORM)
+            tables = dict(vrep_q=vrep_q, vrep_k=vrep_k, cs_q=cs_q, cs_k=cs_k)
+            grads = tuple(_repgrad.table_grads(desc, tables, meta, tc, ((q, dq), (do, out))[:1 + vt], ((dk, k), (dv, v))[:1 + vt],
+                                               direct=False))
+        return (dq, dk, dv, dtc, dta, None, None, None, None, None, None) + grads
 
 
 class _GenericAttn(torch.autograd.Function):
@@ -312,7 +348,7 @@ class _GenericAttn(torch.autograd.Function):
     adjoints (gta_rep_apply_bwd) around the fused backward on an identity layout."""
 
     @staticmethod
-    def forward(ctx, q, k, v, trans_coeff, tau, cfg, packed):
+    def forward(ctx, q, k, v, trans_coeff, tau, cfg, packed, *carriers):
         f_dims, so3_degree, scale, v_transform, euclid, precise = cfg
         dt = q.dtype
         if dt not in (torch.float32, torch.bfloat16):
@@ -352,6 +388,7 @@ class _GenericAttn(torch.autograd.Function):
         ctx.cfg, ctx.packed, ctx.flags = cfg, packed, flags
         ctx.tc_meta = None if not torch.is_tensor(trans_coeff) else (trans_coeff.shape, trans_coeff.dtype)
         ctx.tau_meta = None if not torch.is_tensor(tau) else (tau.shape, tau.dtype)
+        ctx.carriers = _repgrad.carrier_meta(carriers)
         ctx.save_for_backward(q, k, v, qp, kp, vp, op, lse, tc, ta)
         return out
 
@@ -441,14 +478,26 @@ class _GenericAttn(torch.autograd.Function):
         if need_tc:
             assert row_at[0] == n_rows
             dtc = row_buf.sum(dtype=torch.float64).to(ctx.tc_meta[1]).reshape(ctx.tc_meta[0])
-        return dq, dk, dv, dtc, dta, None, None
+        grads = ()
+        if ctx.carriers:
+            # gradients of the tables, in the transformed space: (q, dq'), (dout, o~) and (dk', k), (dv', v) (gta_amd/repgrad.py); under
+            # euclid dk' is the total one, with the key bias -|k'|^2/2 folded in as the adjoint above does (dy - dbias y)
+            meta = tuple(m if need else None for m, need in zip(ctx.carriers, ctx.needs_input_grad[7:]))
+            dqt, opt, dvt = dqp[..., :dh], op[..., :dh], dvp[..., :dh]
+            dkt = (dkp[..., :dh].float() - dbias[..., :Tk, None] * kp[..., :dh].float()).to(dt) if euclid else dkp[..., :dh]
+            do = dout if dout.stride(3) == 1 else dout.contiguous()
+            qpairs = ((q, dqt), (do, opt))[:1 + bool(v_transform)]
+            kpairs = ((dkt, k), (dvt, v))[:1 + bool(v_transform)]
+            qview = ((dqt, q), (do, opt))[:1 + bool(v_transform)] if euclid else None
+            grads = tuple(_repgrad.table_grads(desc, packed, meta, tc, qpairs, kpairs, direct=True, euclid=euclid, q_view_pairs=qview))
+        return (dq, dk, dv, dtc, dta, None, None) + grads
 
 
-def _generic_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, precise=False):
+def _generic_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, precise=False, carriers=()):
     """Generic path entry (forward + backward through _GenericAttn)."""
     tc = trans_coeff if torch.is_tensor(trans_coeff) else None
     ta = tau if torch.is_tensor(tau) else None
-    return _GenericAttn.apply(q, k, v, tc, ta, (f_dims, so3_degree, scale, v_transform, euclid, precise), packed)
+    return _GenericAttn.apply(q, k, v, tc, ta, (f_dims, so3_degree, scale, v_transform, euclid, precise), packed, *carriers)
 
 
 def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: int = 0,
@@ -472,22 +521,27 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
              full-image decode, trainer.py:137-181) stream them again without re-running the pre-pass."""
     if scale is None:
         scale = q.shape[-1] ** -0.5
-    if kv_cache is not None and torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (q, k, v, trans_coeff)):
+    # tables that require grad (poses / coordinates as autograd leaves): the kernels read detached tables, the gradients go to the carriers
+    packed, carriers = _repgrad.split_tables(packed)
+    if kv_cache is not None and torch.is_grad_enabled() and (carriers or any(torch.is_tensor(t) and t.requires_grad for t in (q, k, v, trans_coeff))):
         raise native.GtaError("kv_cache is an inference feature: call under torch.no_grad()")
+    if carriers and pretransformed:
+        raise native.GtaError("pretransformed=True: q, k, v already carry rho, so the tables get no gradient here")
     if isinstance(trans_coeff, (int, float)):
         trans_coeff = torch.tensor([float(trans_coeff)], device=q.device, dtype=torch.float32)
     if isinstance(tau, (int, float)):
         tau = None if float(tau) == 1.0 else torch.tensor([float(tau)], device=q.device, dtype=torch.float32)
-    needs_grad = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (q, k, v, trans_coeff, tau))
+    needs_grad = torch.is_grad_enabled() and (bool(carriers) or any(torch.is_tensor(t) and t.requires_grad for t in (q, k, v, trans_coeff, tau)))
     Nq, Nk = _views(f_dims, packed, q, k)
     flags = attention_route(tuple(q.shape), k.shape[2], q.dtype, f_dims, so3_degree, Nq, Nk, v_transform=v_transform, euclid=euclid,
                             pretransformed=pretransformed, use_dma=use_dma, kv_mode=kv_mode, kv_cache=kv_cache is not None,
                             precise=bool(precise), needs_grad=needs_grad)
     if flags is None:
-        return _generic_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, precise=bool(precise))
+        return _generic_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, precise=bool(precise),
+                                carriers=carriers)
     cfg = ({k_: int(v_) for k_, v_ in f_dims.items()}, int(so3_degree), Nq, Nk, float(scale), flags)
     return _GtaAttn.apply(q, k, v, trans_coeff, tau, kv_cache, cfg, packed.get("vrep_q"), packed.get("vrep_k"),
-                          packed.get("cs_q"), packed.get("cs_k"))
+                          packed.get("cs_q"), packed.get("cs_k"), *carriers)
 
 
 # kv_mode name -> flags of its tuning knob; every name but 'auto' and 'fused' asks for the two-stage plan ('prepass')

@@ -45,6 +45,7 @@ ABI_SYMBOLS = (
     "gta_strerror", "gta_abi_version", "gta_sizeof_attn_desc",
     "gta_debug_time_next_attention_kernel", "gta_debug_event_create", "gta_debug_event_destroy", "gta_debug_event_elapsed_ms",
     "gta_debug_profile_next_attention_kernel", "gta_debug_attention_kernel",
+    "gta_rep_grad_workspace_bytes", "gta_rep_grad_sums",
 )
 
 
@@ -119,6 +120,10 @@ def lib():
         L.gta_debug_profile_next_attention_kernel.restype = None
         L.gta_debug_attention_kernel.argtypes = [ctypes.POINTER(GtaAttnDesc), ctypes.POINTER(c_int32), ctypes.POINTER(c_int32)]
         L.gta_debug_attention_kernel.restype = ctypes.c_char_p
+        L.gta_rep_grad_workspace_bytes.argtypes = [ctypes.POINTER(GtaAttnDesc), c_int32]
+        L.gta_rep_grad_workspace_bytes.restype = c_int64
+        L.gta_rep_grad_sums.argtypes = ([ctypes.POINTER(GtaAttnDesc), c_int32, c_int32] + [c_void_p, ctypes.POINTER(c_int64)] * 4
+                                        + [c_void_p] * 4 + [c_int64, c_void_p])
         _lib = L
     return _lib
 
@@ -181,8 +186,21 @@ def check_scalar(name: str, t: Optional[torch.Tensor], device):
         raise GtaError(f"{name} must be a float32 tensor on {device} (it is read through a device pointer)")
 
 
+def wants_grad(*ts) -> bool:
+    """will a backward run through a call on these tensors (None and non-tensors ignored)?"""
+    return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in ts)
+
+
 def build_view_reps(transforms: torch.Tensor, so3_degree: int) -> torch.Tensor:
-    """extrinsics [B,N,4,4] -> packed per-view reps [B,N,VREP_STRIDE] (see gta_hip.h)."""
+    """extrinsics [B,N,4,4] -> packed per-view reps [B,N,VREP_STRIDE] (see gta_hip.h).  Differentiable in the extrinsics
+    (gta_amd.repgrad: the E and inv(E) slots; the Wigner-D slots carry no gradient, as in the reference)."""
+    if wants_grad(transforms):
+        from .repgrad import ViewReps
+        return ViewReps.apply(transforms, int(so3_degree))
+    return _build_view_reps(transforms, so3_degree)
+
+
+def _build_view_reps(transforms: torch.Tensor, so3_degree: int) -> torch.Tensor:
     _require_cuda(transforms)
     B, N = transforms.shape[:2]
     E = transforms.detach().to(torch.float32).contiguous()
@@ -194,7 +212,15 @@ def build_view_reps(transforms: torch.Tensor, so3_degree: int) -> torch.Tensor:
 
 def build_so2_table(coord: torch.Tensor, nfreqs: int, max_freq_h: float, max_freq_w: float,
                     shared_freqs: bool = False) -> torch.Tensor:
-    """coord [B,T,2] -> (cos, sin) table [B,T,2*nfreqs,2]."""
+    """coord [B,T,2] -> (cos, sin) table [B,T,2*nfreqs,2].  Differentiable in the coordinates (gta_amd.repgrad)."""
+    if wants_grad(coord):
+        from .repgrad import So2Table
+        return So2Table.apply(coord, int(nfreqs), float(max_freq_h), float(max_freq_w), bool(shared_freqs))
+    return _build_so2_table(coord, nfreqs, max_freq_h, max_freq_w, shared_freqs)
+
+
+def _build_so2_table(coord: torch.Tensor, nfreqs: int, max_freq_h: float, max_freq_w: float,
+                     shared_freqs: bool = False) -> torch.Tensor:
     _require_cuda(coord)
     B, T = coord.shape[:2]
     c = coord.detach().to(torch.float32).contiguous()
@@ -206,7 +232,15 @@ def build_so2_table(coord: torch.Tensor, nfreqs: int, max_freq_h: float, max_fre
 
 def build_reps(transforms: torch.Tensor, so3_degree: int, coord: torch.Tensor, nfreqs: int, max_freq_h: float,
                max_freq_w: float, shared_freqs: bool = False):
-    """build_view_reps + build_so2_table in one launch -> (vrep [B,N,72], cs [B,T,2F,2])."""
+    """build_view_reps + build_so2_table in one launch -> (vrep [B,N,72], cs [B,T,2F,2]); differentiable like those two."""
+    if wants_grad(transforms, coord):
+        from .repgrad import Reps
+        return Reps.apply(transforms, coord, int(so3_degree), int(nfreqs), float(max_freq_h), float(max_freq_w), bool(shared_freqs))
+    return _build_reps(transforms, so3_degree, coord, nfreqs, max_freq_h, max_freq_w, shared_freqs)
+
+
+def _build_reps(transforms: torch.Tensor, so3_degree: int, coord: torch.Tensor, nfreqs: int, max_freq_h: float,
+                max_freq_w: float, shared_freqs: bool = False):
     _require_cuda(transforms, coord)
     B, N = transforms.shape[:2]
     T = coord.shape[1]
@@ -329,3 +363,34 @@ def attn_fwd_plain(desc: GtaAttnDesc, q, k, v, key_bias, tau, out, lse):
     check(lib().gta_attn_fwd_plain(ctypes.byref(desc), _ptr(q), _ptr(k), _ptr(v), _ptr(key_bias),
                                    0 if key_bias is None else key_bias.shape[-1], _ptr(tau), _ptr(out), _ptr(lse),
                                    _stream()), "gta_attn_fwd_plain")
+
+
+def rep_grad_workspace_bytes(desc: GtaAttnDesc, side: int) -> int:
+    n = int(lib().gta_rep_grad_workspace_bytes(ctypes.byref(desc), int(side)))
+    check(min(n, 0), "gta_rep_grad_workspace_bytes")
+    return n
+
+
+def rep_grad_sums(desc: GtaAttnDesc, side: int, pairs, view: bool = False, so2: bool = False, t2: bool = False):
+    """Segmented sums of a b^T over the (a, b) pairs (one or two [B,H,T,dh] views of desc's dtype) -> fp32
+    (view [B,N,4,4], so2 [B,T,d_so2/2,2,2], t2 [B,T,3,3]), None where not asked (include/gta_hip.h: gta_rep_grad_sums)."""
+    flat = [t for ab in pairs for t in ab]
+    _require_cuda(*flat)
+    for t in flat:
+        if t.dim() != 4 or t.stride(3) != 1:
+            raise GtaError("gta_rep_grad_sums operands are [B,H,T,dh] views with unit channel stride")
+    B = desc.B
+    T, N = (desc.Tk, desc.Nk) if side else (desc.Tq, desc.Nq)
+    dev = flat[0].device
+    mk = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)
+    vo = mk(B, N, 4, 4) if view else None
+    so = mk(B, T, desc.d_so2 // 2, 2, 2) if so2 else None
+    to = mk(B, T, 3, 3) if t2 else None
+    ws = torch.empty(rep_grad_workspace_bytes(desc, side), device=dev, dtype=torch.uint8) if view else None
+    args = []
+    for i in range(2):
+        for t in (pairs[i] if i < len(pairs) else (None, None)):
+            args += [_ptr(t), None if t is None else (c_int64 * 3)(*t.stride()[:3])]
+    check(lib().gta_rep_grad_sums(ctypes.byref(desc), int(side), len(pairs), *args, _ptr(vo), _ptr(so), _ptr(to), _ptr(ws),
+                                  0 if ws is None else ws.numel(), _stream()), "gta_rep_grad_sums")
+    return vo, so, to

@@ -14,12 +14,20 @@ kernels read are stored:
 The encoder call sets q-side == k-side (self-attention); the decoder call overwrites only the
 q-side from ``target_transforms`` / ``target_coord`` and keeps the encoder's k-side
 (decoder.py:309-311,346), rebuilding ``*_k`` only when missing or under ``recompute_so2``
-(decoder.py:263-272).  The dead ``ray_to_se3`` branch (undefined ``ray2rotation``) and the
+(decoder.py:263-272).  The builders are differentiable in ``*_transforms`` and ``*_coord`` (gta_amd.repgrad):
+``loss.backward()`` reaches camera poses and patch coordinates like the reference's autograd does.  The dead ``ray_to_se3`` branch (undefined ``ray2rotation``) and the
 ``flattened_*`` tensors of the ``elementwise_mul`` ablation are not reproduced.
 """
 from __future__ import annotations
 
 from . import native
+
+
+def _coords(c):
+    """token coordinates of the t2 slab [B,T,2] fp32 -- still in the graph when they require grad (their gradient: gta_amd.repgrad)"""
+    import torch
+    out = c.reshape(c.shape[0], -1, 2).float().contiguous()
+    return out if (torch.is_grad_enabled() and c.requires_grad) else out.detach()
 
 
 def _so2(attn_kwargs, coord):
@@ -85,8 +93,7 @@ def pre_compute_reps_encoder(attn_kwargs: dict, extras: dict) -> dict:
         extras["gta_vrep_q"] = extras["gta_vrep_k"] = _so3_override(attn_kwargs, native.build_view_reps(extras["input_transforms"], L), L)
         extras["gta_so3_degree"] = L
     if f.get("t2", 0) > 0:                            # encoder.py:208-215: T2 reps are the raw token coordinates
-        c = extras["input_coord"]
-        extras["gta_coord_q"] = extras["gta_coord_k"] = c.reshape(c.shape[0], -1, 2).detach().float().contiguous()
+        extras["gta_coord_q"] = extras["gta_coord_k"] = _coords(extras["input_coord"])
     if attn_kwargs.get("elementwise_mul", False):
         T = extras["input_coord"].reshape(extras["input_coord"].shape[0], -1, 2).shape[1]
         fr, fi = _flattened(extras.get("gta_vrep_q") if f.get("se3", 0) > 0 else None, extras.get("gta_cs_q"), T)
@@ -109,11 +116,9 @@ def pre_compute_reps_decoder(attn_kwargs: dict, extras: dict) -> dict:
             extras["gta_vrep_k"] = native.build_view_reps(extras["input_transforms"], L)
         extras["gta_so3_degree"] = L
     if f.get("t2", 0) > 0:                            # decoder.py:283-290: q side only
-        c = extras["target_coord"]
-        extras["gta_coord_q"] = c.reshape(c.shape[0], -1, 2).detach().float().contiguous()
+        extras["gta_coord_q"] = _coords(extras["target_coord"])
         if "gta_coord_k" not in extras:
-            ci = extras["input_coord"]
-            extras["gta_coord_k"] = ci.reshape(ci.shape[0], -1, 2).detach().float().contiguous()
+            extras["gta_coord_k"] = _coords(extras["input_coord"])
     if attn_kwargs.get("elementwise_mul", False):
         T = extras["target_coord"].reshape(extras["target_coord"].shape[0], -1, 2).shape[1]
         fr, fi = _flattened(extras.get("gta_vrep_q") if f.get("se3", 0) > 0 else None, extras.get("gta_cs_q"), T)

@@ -170,7 +170,7 @@ int64_t gta_attn_fwd_workspace_bytes(const GtaAttnDesc* desc);
  *            NULL.  The logits are z = scale q'.k' / tau, so dL/dtau = -(1/tau) sum_ij dz_ij z_ij
  *            = -(1/tau) sum_i <q'_i, dq'_i> = -(1/tau) sum_i <q_i, dq_i>  (rho_q is linear): it falls out of
  *            the dQ kernel's epilogue, no extra pass over the tiles.
- *   No gradient is produced for the reps/poses (gta.py:194-198 detaches them; poses are data).
+ *   No gradient is produced for the reps/poses here: gta_rep_grad_sums is the separate pass that serves them.
  *   GTA_FLAG_FP32_PRODUCTS (r06; fp32 inputs, dh <= 64; other sizes: GTA_E_UNSUPPORTED -> gta_rep_apply + gta_attn_bwd_plain_f32): the fp32-faithful
  *            backward on the matrix cores -- every product of the five contractions as three bf16 MFMAs over hi / lo operand images (the
  *            arithmetic of the forward under the same flag); kv_images must then be the workspace of a forward run WITH the flag (four
@@ -212,6 +212,30 @@ int gta_rep_apply_bwd(const GtaAttnDesc* desc, int32_t mode, const void* x, cons
                       const void* dy, const int64_t* dy_stride, const float* vrep, const float* cs,
                       const float* coord, const float* trans_coeff, const float* dkey_bias, float bias_scale,
                       int64_t bias_pitch, void* dx, const int64_t* dx_stride, float* dtc_rows, void* stream);
+
+/* -------------------------------------------------------------------------------------------
+ * Gradients of the reps: camera poses and patch coordinates (what autograd over gta.py:134-279 gives the reference's
+ * se3rep / inv_se3rep / so2rep / t2rep tensors; the Wigner-D blocks stay detached, gta.py:194-197,267).  A pass after the
+ * backward, run only when a table needs a gradient: segmented outer-product sums
+ *     S = sum a b^T    over heads, the channel groups of a slab and (se3) the tokens of a view,
+ * of n_pairs (1 or 2) pairs (a, b) of [B,H,T,dh] tensors of desc->dtype through their (b,h,t) element strides (channel stride 1);
+ * T, N = Tq, Nq (side 0) or Tk, Nk (side 1).  Outputs (fp32, row-major, written -- not accumulated; NULL = not wanted, and then its
+ * slab's channels are not read):
+ *   view_sums [B, N, 4, 4]        se3 slab, 4-channel groups; under GTA_FLAG_EUCLID 3-channel groups with b homogenised by a
+ *                                 constant 1 (rows 0..2, columns 0..3; row 3 is zero);
+ *   so2_sums  [B, T, d_so2/2, 2, 2] per token and so2 block;
+ *   t2_sums   [B, T, 3, 3]        per token, over the t2 slab's 3-channel groups.
+ * The small-matrix algebra that turns the sums into d(table) is the caller's (gta_amd/repgrad.py).
+ * view_sums need a workspace of >= gta_rep_grad_workspace_bytes(desc, side) bytes (per-workgroup partials; a negative return is
+ * an error code).  Deterministic: no float atomics, fixed-order reductions.  Only desc->{abi_version, dtype, B, H, Tq/Tk, Nq/Nk,
+ * dh, d_*, flags & GTA_FLAG_EUCLID} are read.
+ * ------------------------------------------------------------------------------------------- */
+int64_t gta_rep_grad_workspace_bytes(const GtaAttnDesc* desc, int32_t side);
+int gta_rep_grad_sums(const GtaAttnDesc* desc, int32_t side, int32_t n_pairs,
+                      const void* a0, const int64_t* a0_stride, const void* b0, const int64_t* b0_stride,
+                      const void* a1, const int64_t* a1_stride, const void* b1, const int64_t* b1_stride,
+                      float* view_sums, float* so2_sums, float* t2_sums,
+                      void* workspace, int64_t workspace_bytes, void* stream);
 
 /* softmax((scale * q k^T + key_bias) / tau) v with no rep at all (the fused kernel on an identity layout).
  * key_bias: [B,H,bias_pitch] fp32, added to scale*q.k BEFORE the division by tau; bias_pitch a multiple of 64 >= Tk; or NULL.
