@@ -8,6 +8,7 @@
 #include "gta_fwd_params.h"
 #include "gta_bwd_params.h"
 #include "gta_repgrad_params.h"
+#include "gta_gen_params.h"
 
 // chunk-descriptor constants (mirrors gta_common.h, which is device-only)
 #define HALF_ID 0u
@@ -235,6 +236,84 @@ extern "C" int gta_attn_fwd(const GtaAttnDesc* d, const void* q, const void* k, 
     }
     rc = gta_fwd_dispatch(p, dhp, esz, !(d->flags & GTA_FLAG_NO_DMA), (int)n_wg, (hipStream_t)stream);
     if (rc) return fail(rc, rc == GTA_E_LAUNCH ? hipGetErrorString(hipGetLastError()) : "no kernel instance");
+    return GTA_OK;
+}
+
+
+// ---------------------------------------------------------------------------------------------
+// staged generic forward (gta_fwd_gen.hip): the two-stage plan for any f_dims layout
+// ---------------------------------------------------------------------------------------------
+namespace {
+// the layout rules of the generic path (gta_rep_apply), then what the staged kernels add
+int staged_layout(const GtaAttnDesc* d) {
+    if (d->d_triv < 0 || d->d_se3 < 0 || d->d_so3 < 0 || d->d_so2 < 0 || d->d_t2 < 0) return fail(GTA_E_LAYOUT, "negative slab size");
+    if (d->d_triv + d->d_se3 + d->d_so3 + d->d_so2 + d->d_t2 != d->dh) return fail(GTA_E_LAYOUT, "f_dims do not sum to dh");
+    const bool euclid = (d->flags & GTA_FLAG_EUCLID) != 0;
+    if (euclid && d->d_se3 % 3) return fail(GTA_E_LAYOUT, "under euclid_sim the se3 slab holds 3-vectors (gta.py:147)");
+    if (!euclid && d->d_se3 % 4) return fail(GTA_E_LAYOUT, "se3 slab must be a multiple of 4 channels (gta.py:161)");
+    if (d->d_so2 % 2) return fail(GTA_E_LAYOUT, "so2 slab must be a whole number of 2-channel blocks");
+    if (d->d_t2 % 3) return fail(GTA_E_LAYOUT, "t2 slab must be a multiple of 3 channels (gta.py:231)");
+    if (d->d_so3 > 0 && (d->so3_degree < 1 || d->so3_degree > 2)) return fail(GTA_E_UNSUPPORTED, "so3 of degree 1 or 2");
+    if (d->d_so3 > 0 && d->d_so3 % (d->so3_degree == 2 ? 8 : 3)) return fail(GTA_E_LAYOUT, "so3 slab must be r*sum(2l+1) channels (gta.py:182)");
+    if (d->dh % 8) return fail(GTA_E_UNSUPPORTED, "staged generic forward needs dh % 8 == 0 (gta_rep_apply + gta_attn_fwd_plain on padded channels)");
+    if (d->dh > 128) return fail(GTA_E_UNSUPPORTED, "staged generic forward needs dh <= 128");
+    if (d->flags & GTA_FLAG_FP32_PRODUCTS) return fail(GTA_E_UNSUPPORTED, "staged generic forward has no GTA_FLAG_FP32_PRODUCTS instances (gta_rep_apply + gta_attn_fwd_plain)");
+    if (d->flags & GTA_FLAG_PRETRANSFORMED) return fail(GTA_E_UNSUPPORTED, "staged generic forward applies rho itself: no GTA_FLAG_PRETRANSFORMED");
+    return GTA_OK;
+}
+}  // namespace
+
+extern "C" int gta_attn_fwd_staged_supported(const GtaAttnDesc* desc) {
+    if (!desc) return fail(GTA_E_BADARG, "null descriptor");
+    if (desc->abi_version != GTA_ABI_VERSION) return fail(GTA_E_BADARG, "abi_version mismatch");
+    if (int rc = staged_layout(desc)) return rc;      // layout first, as gta_attn_fwd_supported
+    return check_common(desc);
+}
+
+extern "C" int64_t gta_attn_fwd_staged_workspace_bytes(const GtaAttnDesc* desc) {
+    if (gta_attn_fwd_staged_supported(desc)) return 0;
+    return gta_gen_workspace_bytes(desc->B, desc->H, desc->Tk, padded_dh(desc->dh));
+}
+
+extern "C" int gta_attn_fwd_staged(const GtaAttnDesc* d, const void* q, const void* k, const void* v,
+                                   const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
+                                   const float* coord_q, const float* coord_k, const float* trans_coeff, const float* tau,
+                                   void* out, float* lse, void* workspace, int64_t workspace_bytes, void* stream) {
+    int rc = check_common(d);
+    if (rc) return rc;
+    if (!k || !v || ((!q || !out) && !(d->flags & GTA_FLAG_PREP_ONLY))) return fail(GTA_E_BADARG, "null q/k/v/out");
+    if ((rc = staged_layout(d))) return rc;
+    if ((d->d_se3 > 0 || d->d_so3 > 0) && (!vrep_q || !vrep_k)) return fail(GTA_E_BADARG, "se3/so3 slabs need vrep_q and vrep_k");
+    if (d->d_so2 > 0 && (!cs_q || !cs_k)) return fail(GTA_E_BADARG, "so2 slab needs cs_q and cs_k");
+    if (d->d_t2 > 0 && (!coord_q || !coord_k)) return fail(GTA_E_BADARG, "t2 slab needs coord_q and coord_k");
+    const int dhp = padded_dh(d->dh);
+    if (!workspace || workspace_bytes < gta_gen_workspace_bytes(d->B, d->H, d->Tk, dhp))
+        return fail(GTA_E_BADARG, "workspace smaller than gta_attn_fwd_staged_workspace_bytes()");
+    if ((uintptr_t)workspace % 256) return fail(GTA_E_BADARG, "workspace must be 256-byte aligned");
+    GtaGenParams p;
+    memset(&p, 0, sizeof p);
+    p.q = q; p.k = k; p.v = v; p.o = out; p.lse = lse;
+    p.img = workspace;
+    if (d->flags & GTA_FLAG_EUCLID) p.kbias = (float*)((char*)workspace + ((gta_gen_image_bytes(d->B, d->H, d->Tk, dhp) + 255) & ~255L));
+    p.vrep_q = vrep_q; p.vrep_k = vrep_k; p.cs_q = cs_q; p.cs_k = cs_k; p.coord_q = coord_q; p.coord_k = coord_k;
+    p.trans_coeff = trans_coeff; p.tau = tau;
+    p.q_sb = d->q_stride[0]; p.q_sh = d->q_stride[1]; p.q_st = d->q_stride[2];
+    p.k_sb = d->k_stride[0]; p.k_sh = d->k_stride[1]; p.k_st = d->k_stride[2];
+    p.v_sb = d->v_stride[0]; p.v_sh = d->v_stride[1]; p.v_st = d->v_stride[2];
+    p.o_sb = d->o_stride[0]; p.o_sh = d->o_stride[1]; p.o_st = d->o_stride[2];
+    p.B = d->B; p.H = d->H; p.Tq = d->Tq; p.Tk = d->Tk; p.Nq = d->Nq; p.Nk = d->Nk;
+    p.dh = d->dh; p.d_triv = d->d_triv; p.d_se3 = d->d_se3; p.d_so3 = d->d_so3; p.d_so2 = d->d_so2; p.d_t2 = d->d_t2; p.L = d->so3_degree;
+    p.euclid = (d->flags & GTA_FLAG_EUCLID) ? 1 : 0;
+    p.xv = (d->flags & GTA_FLAG_V_TRANSFORM) ? 1 : 0;
+    p.esz = d->dtype == GTA_DTYPE_BF16 ? 2 : 4;
+    p.n_qtiles = (d->Tq + 127) / 128;
+    p.n_tiles = (d->Tk + 63) / 64;
+    const long n_items = (long)d->B * d->H * p.n_qtiles;
+    if (n_items > 0x7fffffffL) return fail(GTA_E_UNSUPPORTED, "grid too large");
+    p.n_items = (int)n_items;
+    p.scale = d->scale;
+    rc = gta_gen_dispatch(p, dhp, !(d->flags & GTA_FLAG_KV_READY), !(d->flags & GTA_FLAG_PREP_ONLY), stream);
+    if (rc) return fail(rc, gta_gen_error());       // (the launchers read HIP's error, which clears it: they keep its text)
     return GTA_OK;
 }
 

@@ -500,6 +500,63 @@ def _generic_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scal
     return _GenericAttn.apply(q, k, v, tc, ta, (f_dims, so3_degree, scale, v_transform, euclid, precise), packed, *carriers)
 
 
+def generic_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree: int, Nq: int, Nk: int, *, v_transform: bool = True,
+                  euclid: bool = False, precise: bool = False, needs_grad: bool = False) -> str:
+    """How ``gta_attention`` runs a call that ``attention_route`` hands to the generic path (it answered None):
+    'staged' = the staged generic forward (``gta_attn_fwd_staged``: K/V pre-pass + one attention kernel, honours ``kv_cache``) when the
+               library serves the descriptor, no gradient is needed and the arithmetic is the default one;
+    'apply'  = ``_GenericAttn``: the rho-apply kernels around the plain attention kernel, with their adjoints for the backward.
+    Sizes alone decide, as in ``attention_route`` (the descriptor is probed at contiguous strides); needs no GPU."""
+    if needs_grad or precise or dtype not in (torch.float32, torch.bfloat16):
+        return "apply"
+    B, H, Tq, dh = q_shape
+    qs, ks = (H * Tq * dh, Tq * dh, dh), (H * Tk * dh, Tk * dh, dh)
+    flags = (native.FLAG_V_TRANSFORM if v_transform else 0) | (native.FLAG_EUCLID if euclid else 0)
+    probe = native.make_desc_from(dtype, q_shape, Tk, (qs, ks, ks, qs), f_dims, so3_degree, Nq, Nk, 1.0, flags)
+    return "staged" if native.attn_fwd_staged_supported(probe) == 0 else "apply"
+
+
+def _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, kv_cache=None):
+    """The generic path without a gradient: one pre-pass launch + one attention launch (``gta_attn_fwd_staged``), and the attention
+    launch alone on a call that finds its K'/V' images in ``kv_cache`` -- the contract of ``_GtaAttn``: images and plan key are stored by
+    the first call, later calls against another key set / plan raise ``GtaError``."""
+    dt = q.dtype
+    k, v = k.to(dt), v.to(dt)
+    q, k, v = _as_kernel_layout(q), _as_kernel_layout(k), _as_kernel_layout(v)
+    B, H, Tq, dh = q.shape
+    Tk = k.shape[2]
+    Nq, Nk = _views(f_dims, packed, q, k)
+    flags = (native.FLAG_V_TRANSFORM if v_transform else 0) | (native.FLAG_EUCLID if euclid else 0)
+    out = torch.empty(B, Tq, H, dh, device=q.device, dtype=dt).permute(0, 2, 1, 3)
+    lse = torch.empty(B, H, Tq, device=q.device, dtype=torch.float32)
+    tc = trans_coeff.detach().float().reshape(-1) if torch.is_tensor(trans_coeff) else None
+    ta = tau.detach().float().reshape(-1) if torch.is_tensor(tau) else None
+    desc = native.make_desc(q, k, v, out, f_dims, so3_degree, Nq, Nk, scale, flags)
+    _check_tables(q, k, f_dims, Nq, Nk, packed.get("vrep_q"), packed.get("vrep_k"), packed.get("cs_q"), packed.get("cs_k"),
+                  packed.get("coord_q"), packed.get("coord_k"), tc, ta)
+    need = native.attn_fwd_staged_workspace_bytes(desc)
+    # what the images depend on besides the keys, reps and trans_coeff (the caller's contract, see gta_attention): layout, dtype, key-side
+    # shape -- and under euclid the scale, which the cached key bias -0.5 scale |k'|^2 carries (the workspace's size does not depend on
+    # the query side)
+    plan_key = ("staged", bool(v_transform), bool(euclid), str(dt), B, H, Tk, dh,
+                tuple(sorted((g, int(n)) for g, n in f_dims.items() if n)), int(so3_degree), int(Nk), float(scale) if euclid else None)
+    if kv_cache is not None and kv_cache.get("images") is not None:
+        ws = kv_cache["images"]
+        if kv_cache.get("plan") != plan_key:
+            raise native.GtaError(f"kv_cache holds images written under another plan {kv_cache.get('plan')} (this call: {plan_key}): "
+                                  "use one cache dict per (key set, dtype, precise mode)")
+        if ws.numel() < need or ws.device != q.device:
+            raise native.GtaError("kv_cache holds images of a different key set")
+        desc.flags = flags | native.FLAG_KV_READY
+    else:
+        ws = torch.empty(need, device=q.device, dtype=torch.uint8)
+        if kv_cache is not None:
+            kv_cache["images"], kv_cache["plan"] = ws, plan_key
+    native.attn_fwd_staged(desc, q, k, v, packed.get("vrep_q"), packed.get("vrep_k"), packed.get("cs_q"), packed.get("cs_k"),
+                           packed.get("coord_q"), packed.get("coord_k"), tc, ta, out, lse, ws)
+    return out
+
+
 def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: int = 0,
                   trans_coeff=None, tau=None, scale: Optional[float] = None, v_transform: bool = True,
                   euclid: bool = False, pretransformed: bool = False, use_dma: bool = True,
@@ -518,7 +575,8 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
              instructions, 1/16 of the bf16 rate) -- the arithmetic of the reference's ``mixed_prec: False`` training.
     kv_cache: a dict owned by the caller (inference only).  The first call stores the K'/V' tile images of the
              pre-pass in it; later calls with the same keys, reps and trans_coeff (e.g. the next query chunk of a
-             full-image decode, trainer.py:137-181) stream them again without re-running the pre-pass."""
+             full-image decode, trainer.py:137-181) stream them again without re-running the pre-pass.  The layouts of the generic
+             path (t2, euclid, so3 of degree 1, unaligned slabs) honour it through the staged generic forward (``generic_route``)."""
     if scale is None:
         scale = q.shape[-1] ** -0.5
     # tables that require grad (poses / coordinates as autograd leaves): the kernels read detached tables, the gradients go to the carriers
@@ -537,6 +595,9 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
                             pretransformed=pretransformed, use_dma=use_dma, kv_mode=kv_mode, kv_cache=kv_cache is not None,
                             precise=bool(precise), needs_grad=needs_grad)
     if flags is None:
+        if generic_route(tuple(q.shape), k.shape[2], q.dtype, f_dims, so3_degree, Nq, Nk, v_transform=v_transform, euclid=euclid,
+                         precise=bool(precise), needs_grad=needs_grad) == "staged":
+            return _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, kv_cache)
         return _generic_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, precise=bool(precise),
                                 carriers=carriers)
     cfg = ({k_: int(v_) for k_, v_ in f_dims.items()}, int(so3_degree), Nq, Nk, float(scale), flags)

@@ -46,6 +46,7 @@ ABI_SYMBOLS = (
     "gta_debug_time_next_attention_kernel", "gta_debug_event_create", "gta_debug_event_destroy", "gta_debug_event_elapsed_ms",
     "gta_debug_profile_next_attention_kernel", "gta_debug_attention_kernel",
     "gta_rep_grad_workspace_bytes", "gta_rep_grad_sums",
+    "gta_attn_fwd_staged", "gta_attn_fwd_staged_supported", "gta_attn_fwd_staged_workspace_bytes",
 )
 
 
@@ -124,6 +125,10 @@ def lib():
         L.gta_rep_grad_workspace_bytes.restype = c_int64
         L.gta_rep_grad_sums.argtypes = ([ctypes.POINTER(GtaAttnDesc), c_int32, c_int32] + [c_void_p, ctypes.POINTER(c_int64)] * 4
                                         + [c_void_p] * 4 + [c_int64, c_void_p])
+        L.gta_attn_fwd_staged.argtypes = [ctypes.POINTER(GtaAttnDesc)] + [c_void_p] * 14 + [c_int64, c_void_p]
+        L.gta_attn_fwd_staged_supported.argtypes = [ctypes.POINTER(GtaAttnDesc)]
+        L.gta_attn_fwd_staged_workspace_bytes.argtypes = [ctypes.POINTER(GtaAttnDesc)]
+        L.gta_attn_fwd_staged_workspace_bytes.restype = c_int64
         _lib = L
     return _lib
 
@@ -300,6 +305,25 @@ def attn_fwd_workspace_bytes(desc: GtaAttnDesc) -> int:
 
 def attn_fwd_supported(desc: GtaAttnDesc) -> int:
     return lib().gta_attn_fwd_supported(ctypes.byref(desc))
+
+
+def attn_fwd_staged_supported(desc: GtaAttnDesc) -> int:
+    """0 when the staged generic forward (include/gta_hip.h: gta_attn_fwd_staged) serves desc, else a GTA_E_* code; needs no GPU"""
+    return lib().gta_attn_fwd_staged_supported(ctypes.byref(desc))
+
+
+def attn_fwd_staged_workspace_bytes(desc: GtaAttnDesc) -> int:
+    return int(lib().gta_attn_fwd_staged_workspace_bytes(ctypes.byref(desc)))
+
+
+def attn_fwd_staged(desc: GtaAttnDesc, q, k, v, vrep_q, vrep_k, cs_q, cs_k, coord_q, coord_k, trans_coeff, tau, out, lse,
+                    workspace: torch.Tensor):
+    """K/V pre-pass (skipped under FLAG_KV_READY) + attention kernel of the staged generic forward; workspace: uint8 CUDA tensor of
+    >= attn_fwd_staged_workspace_bytes(desc) bytes holding the K'/V' tile images (+ the euclid key bias)."""
+    _require_cuda(q, k, v, out, workspace)
+    check(lib().gta_attn_fwd_staged(ctypes.byref(desc), _ptr(q), _ptr(k), _ptr(v), _ptr(vrep_q), _ptr(vrep_k), _ptr(cs_q), _ptr(cs_k),
+                                    _ptr(coord_q), _ptr(coord_k), _ptr(trans_coeff), _ptr(tau), _ptr(out), _ptr(lse),
+                                    _ptr(workspace), workspace.numel(), _stream()), "gta_attn_fwd_staged")
 
 
 def launch_info(desc: GtaAttnDesc):

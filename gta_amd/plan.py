@@ -44,34 +44,43 @@ class RepPlan:
 
 
 class ForwardPlan:
-    """One fused-eligible attention shape, two-stage plan (K/V pre-pass + attention kernel).
+    """One attention shape, two-stage plan (K/V pre-pass + attention kernel): ``gta_attn_fwd`` for the layouts the fused kernels serve,
+    ``gta_attn_fwd_staged`` for the generic path's (t2 slab -- pass ``coord_q`` / ``coord_k`` [B,T,2] --, ``euclid=True``, so3 of
+    degree 1, unaligned slabs; dh % 8 == 0).
 
     q, k, v: example tensors [B,H,T,dh] (any strides with unit channel stride) -- later calls must use tensors of the
     same shape, dtype and strides.  ``out`` ([B,H,Tq,dh] view of [B,Tq,H,dh] memory), ``lse`` and the workspace belong
     to the plan and are overwritten by every call."""
 
     def __init__(self, q, k, v, f_dims: dict, *, so3_degree: int = 0, Nq: int = 1, Nk: int = 1,
-                 scale: Optional[float] = None, v_transform: bool = True, flags: int = 0):
+                 scale: Optional[float] = None, v_transform: bool = True, flags: int = 0, euclid: bool = False):
         native._require_cuda(q, k, v)
         B, H, Tq, dh = q.shape
         self.out = torch.empty(B, Tq, H, dh, device=q.device, dtype=q.dtype).permute(0, 2, 1, 3)
         self.lse = torch.empty(B, H, Tq, device=q.device, dtype=torch.float32)
-        fl = flags | (native.FLAG_V_TRANSFORM if v_transform else 0)
+        fl = flags | (native.FLAG_V_TRANSFORM if v_transform else 0) | (native.FLAG_EUCLID if euclid else 0)
         self.desc = native.make_desc(q, k, v, self.out, f_dims, so3_degree, Nq, Nk,
                                      float(scale if scale is not None else dh ** -0.5), fl)
         rc = native.attn_fwd_supported(self.desc)
-        if rc:
+        # layouts without a fused kernel (t2 slab, euclid, so3 of degree 1, unaligned slabs): the staged generic forward, where it serves them
+        rc_staged = native.attn_fwd_staged_supported(self.desc) if rc == -3 else rc
+        self._staged = rc == -3 and rc_staged == 0
+        if rc == -3 and rc_staged:                    # both entries refuse: the staged one spoke last, its reason is the library's message
+            native.check(rc_staged, "gta_attn_fwd_staged_supported")
+        elif rc and not self._staged:
             native.check(rc, "gta_attn_fwd_supported")
-        self.ws = torch.empty(native.attn_fwd_workspace_bytes(self.desc), device=q.device, dtype=torch.uint8)
+        self.ws = torch.empty(native.attn_fwd_staged_workspace_bytes(self.desc) if self._staged else native.attn_fwd_workspace_bytes(self.desc),
+                              device=q.device, dtype=torch.uint8)
         self._sig = (tuple(q.shape), tuple(q.stride()), tuple(k.shape), tuple(k.stride()), tuple(v.stride()), q.dtype)
         self._lib = native.lib()
         self._need_view = f_dims.get("se3", 0) > 0 or f_dims.get("so3", 0) > 0
         self._need_cs = f_dims.get("so2", 0) > 0
+        self._need_coord = f_dims.get("t2", 0) > 0
         self._shapes = ((B, Nq, native.VREP_STRIDE), (B, Nk, native.VREP_STRIDE), (B, Tq, f_dims.get("so2", 0) // 2, 2),
-                        (B, k.shape[2], f_dims.get("so2", 0) // 2, 2))
+                        (B, k.shape[2], f_dims.get("so2", 0) // 2, 2), (B, Tq, 2), (B, k.shape[2], 2))
 
     def __call__(self, q, k, v, vrep_q=None, vrep_k=None, cs_q=None, cs_k=None, trans_coeff=None, tau=None,
-                 flags_extra: int = 0):
+                 flags_extra: int = 0, coord_q=None, coord_k=None):
         if (tuple(q.shape), tuple(q.stride()), tuple(k.shape), tuple(k.stride()), tuple(v.stride()), q.dtype) != self._sig:
             raise native.GtaError("ForwardPlan: q/k/v differ from the planned shape / strides / dtype")
         if self._need_view:
@@ -80,6 +89,9 @@ class ForwardPlan:
         if self._need_cs:
             native.check_table("cs_q", cs_q, self._shapes[2], q.device)
             native.check_table("cs_k", cs_k, self._shapes[3], q.device)
+        if self._need_coord:
+            native.check_table("coord_q", coord_q, self._shapes[4], q.device)
+            native.check_table("coord_k", coord_k, self._shapes[5], q.device)
         # everything else that reaches the kernels as a raw pointer: the scalars, the tensors' device (the launch goes to the
         # CURRENT device's stream)
         native._require_cuda(q, k, v)
@@ -93,9 +105,14 @@ class ForwardPlan:
         if flags_extra:
             d.flags = base | flags_extra
         try:
-            native.check(self._lib.gta_attn_fwd(ctypes.byref(d), p(q), p(k), p(v), p(vrep_q), p(vrep_k), p(cs_q), p(cs_k),
-                                                p(trans_coeff), p(tau), p(self.out), p(self.lse), p(self.ws),
-                                                self.ws.numel(), native._stream()), "gta_attn_fwd")
+            if self._staged:
+                native.check(self._lib.gta_attn_fwd_staged(ctypes.byref(d), p(q), p(k), p(v), p(vrep_q), p(vrep_k), p(cs_q), p(cs_k),
+                                                           p(coord_q), p(coord_k), p(trans_coeff), p(tau), p(self.out), p(self.lse),
+                                                           p(self.ws), self.ws.numel(), native._stream()), "gta_attn_fwd_staged")
+            else:
+                native.check(self._lib.gta_attn_fwd(ctypes.byref(d), p(q), p(k), p(v), p(vrep_q), p(vrep_k), p(cs_q), p(cs_k),
+                                                    p(trans_coeff), p(tau), p(self.out), p(self.lse), p(self.ws),
+                                                    self.ws.numel(), native._stream()), "gta_attn_fwd")
         finally:
             d.flags = base
         return self.out

@@ -193,7 +193,7 @@ int gta_attn_bwd(const GtaAttnDesc* desc,
  * euclid similarity (GTA_FLAG_EUCLID; gta.py:146-156,251-253 + EuclidAttnFn layers.py:213-224),
  * so3 of degree 1, unaligned slabs.  Usage: q' = apply(mode 0), k' = apply(mode 1)
  * (+ key_bias under euclid), v' = apply(mode 1), o~ = gta_attn_fwd_plain(q',k',v',key_bias),
- * o = apply(mode 2).
+ * o = apply(mode 2) -- or, for a forward without gradient at dh % 8 == 0, the single entry gta_attn_fwd_staged below.
  *   x, y: [B,H,T,dh] through x_stride/y_stride (b,h,t), dtype from desc; T,N = Tq,Nq (modes 0,2) or Tk,Nk.
  *   coord [B,T,2]: the token coordinates of the t2 slab (make_T2mats, gta.py:72-89) or NULL.
  *   key_bias (mode 1, or NULL): [B,H,bias_pitch] <- -0.5 * bias_scale * |y|^2 per token.
@@ -212,6 +212,28 @@ int gta_rep_apply_bwd(const GtaAttnDesc* desc, int32_t mode, const void* x, cons
                       const void* dy, const int64_t* dy_stride, const float* vrep, const float* cs,
                       const float* coord, const float* trans_coeff, const float* dkey_bias, float bias_scale,
                       int64_t bias_pitch, void* dx, const int64_t* dx_stride, float* dtc_rows, void* stream);
+
+/* Staged generic forward: the five calls above as ONE entry -- a K/V pre-pass that writes K' and V' as bf16 tile images (and, under
+ * GTA_FLAG_EUCLID, the per-key bias -0.5 * scale * |k'|^2 in fp32, from the fp32 k') plus one attention kernel that applies rho_q in
+ * its prologue and rho_q^-1 in its epilogue, per row in LDS; no q', k', v' or o~ tensor is written (gta_fwd_gen.hip).  For every layout
+ * of the generic path with dh % 8 == 0 and dh <= 128, bf16 or fp32 inputs, the default arithmetic (operands rounded to bf16 once,
+ * after rho; fp32 accumulation and softmax).  Forward only: a gradient goes through the five calls and their adjoints.
+ *   gta_attn_fwd_staged_supported: 0, or GTA_E_LAYOUT for slabs that do not add up / are mis-sized, or GTA_E_UNSUPPORTED with the
+ *       reason in gta_strerror(): dh % 8 != 0, dh > 128, GTA_FLAG_FP32_PRODUCTS, GTA_FLAG_PRETRANSFORMED (those keep the five calls).
+ *   workspace: >= gta_attn_fwd_staged_workspace_bytes(desc) bytes (0 when unsupported), 256-byte aligned, [images | bias]; it depends
+ *       on B, H, Tk and dh only, so one workspace serves every query set against the same keys.  GTA_FLAG_KV_READY skips the pre-pass
+ *       and trusts the workspace, GTA_FLAG_PREP_ONLY runs the pre-pass alone -- exactly as in gta_attn_fwd.
+ *   coord_q [B,Tq,2], coord_k [B,Tk,2]: the t2 tables gta_rep_apply takes (NULL without a t2 slab); the other operands, the argument
+ *       checks and the error codes are those of gta_attn_fwd.  lse (or NULL): log sum_k exp((scale q'.k' + bias_k) / tau) per query
+ *       row -- the convention of gta_attn_fwd_plain with that key bias (the row-constant -scale |q'|^2 / 2 of the euclid similarity
+ *       is not in it).
+ * gta_attn_fwd_supported() keeps answering GTA_E_UNSUPPORTED for these layouts: that entry names the chunk-wise fused kernels. */
+int     gta_attn_fwd_staged_supported(const GtaAttnDesc* desc);
+int64_t gta_attn_fwd_staged_workspace_bytes(const GtaAttnDesc* desc);
+int gta_attn_fwd_staged(const GtaAttnDesc* desc, const void* q, const void* k, const void* v,
+                        const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
+                        const float* coord_q, const float* coord_k, const float* trans_coeff, const float* tau,
+                        void* out, float* lse, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* -------------------------------------------------------------------------------------------
  * Gradients of the reps: camera poses and patch coordinates (what autograd over gta.py:134-279 gives the reference's

@@ -229,17 +229,40 @@ def audit_attn64():
     return report, problems
 
 
+def audit_gen():
+    """The staged generic forward (gta_fwd_gen.hip): the pre-pass and both attention instances (with / without the euclid key bias) of every
+    head size must stay scratch-free -- the row transform walks a row's slabs with run-time trip counts, the one construct here that could
+    push a register array into scratch; the registers and the LDS of each instance are reported.  The LDS is dynamic (not in the assembly):
+    the figures restate GenPrepSmem / Smem2 + the bias slots, and gta_fwd_gen.hip pins every one of them with a static_assert, so a layout
+    change that this table misses does not compile."""
+    text = _asm("gta_fwd_gen.hip", ("-fno-slp-vectorize",))
+    report, problems = [], []
+    for name, groups, body, vgpr in _kernels(text, r"gta_gen_(prep|attn)_kernelILi(\d+)E(?:Lb(\d)E)?"):
+        kind, dhp, bias = re.search(r"gta_gen_(prep|attn)_kernelILi(\d+)E(?:Lb(\d)E)?", name).groups()
+        dhp = int(dhp)
+        lds = (2 * 64 * (dhp + 1) * 4 + 2 * 64 * dhp * 2) if kind == "prep" else 3 * 2 * 64 * dhp * 2 + (3 * 4 * 256 if bias == "1" else 0)
+        row = {"kernel": f"gta_gen_{kind}_kernel<{dhp}{', bias' if bias == '1' else ''}>", "vgpr": vgpr, "scratch": body.count("scratch_"),
+               "lds_bytes": lds, "sgpr_spill_writes": body.count("v_writelane")}
+        report.append(row)
+        if row["scratch"]:                                # (a hard failure, not a "perf:" warning: these kernels have no spill to tolerate)
+            problems.append(f"{row['kernel']}: {row['scratch']} scratch accesses")
+        if kind == "attn" and vgpr > (256 if dhp <= 96 else 512):
+            problems.append(f"perf: {row['kernel']}: {vgpr} VGPRs (two workgroups per CU at dh <= 96 need <= 256)")
+    return report, problems
+
+
 if __name__ == "__main__":
     rep, prob = audit()
     rep2, prob2 = audit_others()
     rep3, prob3 = audit_attn64()
     rep4, prob4 = audit_dkv64()
-    for r in rep + rep2 + rep3 + rep4:
+    rep5, prob5 = audit_gen()
+    for r in rep + rep2 + rep3 + rep4 + rep5:
         print(r)
     # (ADVICE r05) the build fails on the CORRECTNESS criteria only -- what hipcc does to the accumulator file around the generated statements, the
     # register-file split, statement and result-read counts; scratch and register counts are performance criteria sitting close to today's
     # compiler output: reported as warnings ("perf:"), with headroom
-    allp = prob + prob2 + prob3 + prob4
+    allp = prob + prob2 + prob3 + prob4 + prob5
     hard = [x for x in allp if not x.startswith("perf:")]
     print("warnings:", [x for x in allp if x.startswith("perf:")] or "none")
     print("problems:", hard or "none")
