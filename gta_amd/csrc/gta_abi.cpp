@@ -239,6 +239,50 @@ extern "C" int gta_attn_fwd(const GtaAttnDesc* d, const void* q, const void* k, 
     return GTA_OK;
 }
 
+// Per-scene key prefixes on the two-stage plan: the VARLEN instances of the pre-pass and of gta_fwd2_kernel (GtaFwdSel::varlen selects them in
+// gta_fwd2_dispatch), whatever attention kernel gta_fwd_select would give the shape.
+namespace {
+int varlen_flags(const GtaAttnDesc* d) {
+    if (d->flags & GTA_FLAG_FUSED_KV) return fail(GTA_E_UNSUPPORTED, "per-scene key prefixes run the two-stage plan: no GTA_FLAG_FUSED_KV");
+    if (d->flags & GTA_FLAG_FP32_PRODUCTS) return fail(GTA_E_UNSUPPORTED, "per-scene key prefixes have no GTA_FLAG_FP32_PRODUCTS instances");
+    if (d->flags & GTA_FLAG_PRETRANSFORMED) return fail(GTA_E_UNSUPPORTED, "per-scene key prefixes apply rho_k in the pre-pass: no GTA_FLAG_PRETRANSFORMED");
+    return GTA_OK;
+}
+}  // namespace
+
+extern "C" int gta_attn_fwd_varlen_supported(const GtaAttnDesc* desc) {
+    if (int rc = gta_attn_fwd_supported(desc)) return rc;
+    return varlen_flags(desc);
+}
+
+extern "C" int gta_attn_fwd_varlen(const GtaAttnDesc* d, const void* q, const void* k, const void* v,
+                                   const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
+                                   const float* trans_coeff, const float* tau, const int32_t* key_lens, void* out, float* lse,
+                                   void* workspace, int64_t workspace_bytes, void* stream) {
+    int rc = check_common(d);
+    if (rc) return rc;
+    if (!k || !v || ((!q || !out) && !(d->flags & GTA_FLAG_PREP_ONLY))) return fail(GTA_E_BADARG, "null q/k/v/out");
+    if (!key_lens) return fail(GTA_E_BADARG, "null key_lens");
+    if (!workspace) return fail(GTA_E_BADARG, "per-scene key prefixes need the workspace of gta_attn_fwd_workspace_bytes()");
+    GtaFwdParams p;
+    rc = fwd_params(p, d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, out, lse, workspace);
+    if (rc) return rc;
+    if ((rc = varlen_flags(d))) return rc;
+    if ((d->d_se3 > 0 || d->d_so3 > 0) && (!vrep_q || !vrep_k)) return fail(GTA_E_BADARG, "se3/so3 slabs need vrep_q and vrep_k");
+    if (d->d_so2 > 0 && (!cs_q || !cs_k)) return fail(GTA_E_BADARG, "so2 slab needs cs_q and cs_k");
+    const int dhp = padded_dh(d->dh), esz = d->dtype == GTA_DTYPE_BF16 ? 2 : 4;
+    GtaFwdSel s = gta_fwd_select(p, dhp, esz);          // (for the layout of the chunk table; the kernel is fixed)
+    s.kind = GTA_FWD_FWD2; s.coal = false; s.qtiles = false; s.rows = 128; s.name = "gta_fwd2_kernel"; s.varlen = true;
+    p.key_lens = key_lens;
+    if ((long)d->B * d->H * p.n_qtiles > 0x7fffffffL) return fail(GTA_E_UNSUPPORTED, "grid too large");
+    if (workspace_bytes < gta_fwd2_workspace_bytes(d->B, d->H, d->Tk, dhp, d->Nq, esz, false))
+        return fail(GTA_E_BADARG, "workspace smaller than gta_attn_fwd_workspace_bytes()");
+    if (d->H > 65535 || d->B > 65535) return fail(GTA_E_UNSUPPORTED, "B or H above 65535");
+    rc = gta_fwd2_dispatch(p, s, dhp, esz, !(d->flags & GTA_FLAG_KV_READY), !(d->flags & GTA_FLAG_PREP_ONLY), (hipStream_t)stream);
+    if (rc) return fail(rc, rc == GTA_E_LAUNCH ? hipGetErrorString(hipGetLastError()) : "no kernel instance");
+    return GTA_OK;
+}
+
 
 // ---------------------------------------------------------------------------------------------
 // staged generic forward (gta_fwd_gen.hip): the two-stage plan for any f_dims layout
@@ -275,10 +319,12 @@ extern "C" int64_t gta_attn_fwd_staged_workspace_bytes(const GtaAttnDesc* desc) 
     return gta_gen_workspace_bytes(desc->B, desc->H, desc->Tk, padded_dh(desc->dh));
 }
 
-extern "C" int gta_attn_fwd_staged(const GtaAttnDesc* d, const void* q, const void* k, const void* v,
-                                   const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
-                                   const float* coord_q, const float* coord_k, const float* trans_coeff, const float* tau,
-                                   void* out, float* lse, void* workspace, int64_t workspace_bytes, void* stream) {
+namespace {
+// both staged entries: key_lens == nullptr is gta_attn_fwd_staged
+int staged_call(const GtaAttnDesc* d, const void* q, const void* k, const void* v,
+                const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
+                const float* coord_q, const float* coord_k, const float* trans_coeff, const float* tau, const int32_t* key_lens,
+                void* out, float* lse, void* workspace, int64_t workspace_bytes, void* stream) {
     int rc = check_common(d);
     if (rc) return rc;
     if (!k || !v || ((!q || !out) && !(d->flags & GTA_FLAG_PREP_ONLY))) return fail(GTA_E_BADARG, "null q/k/v/out");
@@ -312,9 +358,28 @@ extern "C" int gta_attn_fwd_staged(const GtaAttnDesc* d, const void* q, const vo
     if (n_items > 0x7fffffffL) return fail(GTA_E_UNSUPPORTED, "grid too large");
     p.n_items = (int)n_items;
     p.scale = d->scale;
+    p.key_lens = key_lens;
     rc = gta_gen_dispatch(p, dhp, !(d->flags & GTA_FLAG_KV_READY), !(d->flags & GTA_FLAG_PREP_ONLY), stream);
     if (rc) return fail(rc, gta_gen_error());       // (the launchers read HIP's error, which clears it: they keep its text)
     return GTA_OK;
+}
+}  // namespace
+
+extern "C" int gta_attn_fwd_staged(const GtaAttnDesc* d, const void* q, const void* k, const void* v,
+                                   const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
+                                   const float* coord_q, const float* coord_k, const float* trans_coeff, const float* tau,
+                                   void* out, float* lse, void* workspace, int64_t workspace_bytes, void* stream) {
+    return staged_call(d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, coord_q, coord_k, trans_coeff, tau, nullptr, out, lse, workspace, workspace_bytes, stream);
+}
+
+extern "C" int gta_attn_fwd_staged_varlen_supported(const GtaAttnDesc* desc) { return gta_attn_fwd_staged_supported(desc); }
+
+extern "C" int gta_attn_fwd_staged_varlen(const GtaAttnDesc* d, const void* q, const void* k, const void* v,
+                                          const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
+                                          const float* coord_q, const float* coord_k, const float* trans_coeff, const float* tau,
+                                          const int32_t* key_lens, void* out, float* lse, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!key_lens) return fail(GTA_E_BADARG, "null key_lens");
+    return staged_call(d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, coord_q, coord_k, trans_coeff, tau, key_lens, out, lse, workspace, workspace_bytes, stream);
 }
 
 

@@ -283,4 +283,14 @@ constexpr int NSTAGE = 3;                // ring stages (K' + V' tile images eac
 constexpr bool PIPE1 = true;
 constexpr float BOUND_THR = 96.0f;     // exp2 arguments stay below this without looking at the scores
 
+// VARLEN instances: the valid keys of scene b, clamped to 1..Tk (no walk leaves the images whatever the tensor holds).  b is wave-uniform
+// (a work item, or a pre-pass tile, belongs to one scene): a scalar load, awaited here -- the ring's counted vmcnt waits never see it.
+GTA_DEV int key_len_of(const int32_t* key_lens, int b, int Tk) {
+    uint32_t x;
+    const int32_t* a = key_lens + __builtin_amdgcn_readfirstlane(b);
+    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(x) : "s"(a) : "memory");
+    const int n = (int)x;
+    return n < 1 ? 1 : n > Tk ? Tk : n;
+}
+
 }  // namespace

@@ -35,7 +35,7 @@
 #include <hip/hip_ext.h>
 #include "gta_fwd2_tile.h"
 
-int gta_prep_dispatch(const GtaFwdParams& p, int dhp, int esz, hipStream_t stream);                  // gta_prep.hip
+int gta_prep_dispatch(const GtaFwdParams& p, int dhp, int esz, bool varlen, hipStream_t stream);                  // gta_prep.hip
 int gta_qtiles_dispatch(const GtaFwdParams& p, hipStream_t stream);                                  // gta_fwd64.hip
 int gta_attn64_dispatch(const GtaFwdParams& p, const GtaFwdSel& s, int esz, hipStream_t stream);
 int gta_fwdc_dispatch(const GtaFwdParams& p, int layout, hipStream_t stream);                        // gta_fwd_cl.hip
@@ -69,9 +69,13 @@ GTA_DEV KArgs kargs() {
     return a;
 }
 
-template <int DHP, int ESZ, int LAYOUT, bool X3 = false>
+// VARLEN: the key side of scene b is the prefix of p.key_lens[b] tokens of its Tk (gta_attention's key_views).  A work item belongs to one
+// (b,h), so the prefix is wave-uniform: it replaces Tk in the tile count, the tail mask, the one-tile rule and the lazy-tail rule, and the
+// DMA stream carries the tile count of the item whose tiles it is requesting.  The workspace keeps the strides of the full Tk.
+template <int DHP, int ESZ, int LAYOUT, bool X3 = false, bool VARLEN = false>
 __global__ __launch_bounds__(256, (X3 ? 2 : DHP <= 64 ? 3 : 2)) void gta_fwd2_kernel(const GtaFwdParams p_kernarg) {
     static_assert(!X3 || (ESZ == 4 && DHP <= 64), "the fp32-faithful two-stage instances: fp32 inputs, dh <= 64");
+    static_assert(!(X3 && VARLEN), "no fp32-faithful VARLEN instances");
     using S = Smem2<DHP, X3>;
     // chunk descriptor: a compile-time constant for the shipped layouts (c is constant per unrolled item)
 #define GTA_DESC(c) (LAYOUT == GTA_LAYOUT_GENERIC ? pp->ctab[c] : gta_layout_desc(LAYOUT, c))
@@ -114,10 +118,12 @@ __global__ __launch_bounds__(256, (X3 ? 2 : DHP <= 64 ? 3 : 2)) void gta_fwd2_ke
 
     // ---- the K'/V' DMA stream: tiles of this workgroup's items in consumption order, ring stage = running index % 3 ----
     int dma_V = blockIdx.x, dma_t = 0, dma_st = 0;
+    int dma_nt = n_tiles;                 // (VARLEN) tiles of the item the stream is at
     const char* dma_img = nullptr;
     auto dma_img_of = [&](int V) -> const char* {
         KArgs pp = kargs();
         const int bh = item_of(V, n_items) / pp->n_qtiles;
+        if constexpr (VARLEN) dma_nt = (key_len_of(pp->key_lens, bh / pp->H, pp->Tk) + BN - 1) / BN;
         return (const char*)pp->kp + (long)bh * n_tiles * (long)S::STAGE;
     };
     if (dma_V < n_items) dma_img = dma_img_of(dma_V);
@@ -125,7 +131,9 @@ __global__ __launch_bounds__(256, (X3 ? 2 : DHP <= 64 ? 3 : 2)) void gta_fwd2_ke
         if (dma_V < n_items) {
             dma_stage<DHP, X3>(ring, dma_st, dma_img + (long)dma_t * S::STAGE, wave, lane);
             dma_st = dma_st == S::NST - 1 ? 0 : dma_st + 1;
-            if (++dma_t == n_tiles) {
+            bool wrap;                    // (if constexpr: the instances without VARLEN do not even capture dma_nt)
+            if constexpr (VARLEN) wrap = ++dma_t == dma_nt; else wrap = ++dma_t == n_tiles;
+            if (wrap) {
                 dma_t = 0;
                 dma_V += G;
                 if (dma_V < n_items) dma_img = dma_img_of(dma_V);
@@ -207,6 +215,13 @@ __global__ __launch_bounds__(256, (X3 ? 2 : DHP <= 64 ? 3 : 2)) void gta_fwd2_ke
             for (int i0 = 0; i0 < S::NST - 1; ++i0) dma_next(lane);
         }
     }
+    // (VARLEN) this item's key side: tk_i keys.  GTA_NT / GTA_TAIL / GTA_TK are what the tile loops use for n_tiles / has_tail / Tk
+    // (one value lives through the tile loop; tile count and tail flag are a shift and a mask away)
+    int tk_i = 0;
+    if constexpr (VARLEN) tk_i = key_len_of(pp->key_lens, b, pp->Tk);
+#define GTA_NT (VARLEN ? ((tk_i + BN - 1) >> 6) : n_tiles)
+#define GTA_TAIL (VARLEN ? ((tk_i & (BN - 1)) != 0) : has_tail)
+#define GTA_TK (VARLEN ? tk_i : pp->Tk)
     float* qrec = reinterpret_cast<float*>(smem + S::OFF_QREC) + par * pp->nrec * GTA_QREC;
     // ---- prologue, second half: view records -> LDS (this item's buffer), rho_q on the lane's chunks -> qf ----
     if (pp->vrep_q) {
@@ -438,12 +453,12 @@ __global__ __launch_bounds__(256, (X3 ? 2 : DHP <= 64 ? 3 : 2)) void gta_fwd2_ke
         // decision for tile j (sc = S'(j) relative to m_run): lazy-softmax full path only when needed
         {
             const float kn_j = __uint_as_float(kn_bits);
-            const bool tail = has_tail && j == n_tiles - 1;
+            const bool tail = GTA_TAIL && j == GTA_NT - 1;
             const bool need = (j == 0) || tail || (qn * kn_j - m_run > BOUND_THR);
             if (__builtin_amdgcn_ballot_w64(need) != 0) {
                 asm volatile("" ::: "memory");
                 l_run += rs0 + rs1; rs0 = 0.f; rs1 = 0.f;
-                softmax_rebase<DHP>(sc[0], sc[1], m_run, l_run, oacc, msplat, j == 0, tail, j * BN + 4 * lh, pp->Tk);
+                softmax_rebase<DHP>(sc[0], sc[1], m_run, l_run, oacc, msplat, j == 0, tail, j * BN + 4 * lh, GTA_TK);
             }
             s_fence1(sc);
         }
@@ -520,11 +535,11 @@ __global__ __launch_bounds__(256, (X3 ? 2 : DHP <= 64 ? 3 : 2)) void gta_fwd2_ke
     }
     {
         int j = 0;
-        for (; j + 2 < n_tiles; j += 2) {
+        for (; j + 2 < GTA_NT; j += 2) {
             step(sA, sB, j, std::false_type{});
             step(sB, sA, j + 1, std::false_type{});
         }
-        if (j + 2 == n_tiles) {
+        if (j + 2 == GTA_NT) {
             step(sA, sB, j, std::false_type{});
             step(sB, sA, j + 1, std::true_type{});
         } else {
@@ -533,7 +548,7 @@ __global__ __launch_bounds__(256, (X3 ? 2 : DHP <= 64 ? 3 : 2)) void gta_fwd2_ke
     }
     l_run += rs0 + rs1;
     } else
-    for (int j = 0; j < n_tiles; ++j) {
+    for (int j = 0; j < GTA_NT; ++j) {
         // tile j has landed (only the stream's next tile may still be in flight), everyone is past tile j-1.
         // (younger requests -- the next item's Q loads, this item's predecessor's stores -- only make the wait longer)
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"((S::NST - 2) * DMA_PER_WAVE) : "memory");
@@ -588,13 +603,13 @@ __global__ __launch_bounds__(256, (X3 ? 2 : DHP <= 64 ? 3 : 2)) void gta_fwd2_ke
             // overflows nor leaves a row all zero (-2.6 % cycles at cl-dec).  One-tile key sides keep the true row max: there this kernel
             // and the single-kernel plan agree to the last bits (the chunked decode's cached against uncached layers).
             const float kn_j = __uint_as_float(kn_bits);
-            const bool tail = has_tail && j == n_tiles - 1;
-            const int rem = pp->Tk & (BN - 1);
+            const bool tail = GTA_TAIL && j == GTA_NT - 1;
+            const int rem = GTA_TK & (BN - 1);
             const bool tail8 = tail && (rem & 7) == 0;
-            const bool need = (j == 0 && n_tiles == 1) || (tail && !tail8) || (qn * kn_j - m_run > BOUND_THR);
+            const bool need = (j == 0 && GTA_NT == 1) || (tail && !tail8) || (qn * kn_j - m_run > BOUND_THR);
             if (tail8) mask_tail8(s[0], s[1], __builtin_amdgcn_readfirstlane(rem >> 3));
             if (__builtin_amdgcn_ballot_w64(need) != 0)
-                softmax_rebase<DHP>(s[0], s[1], m_run, l_run, oacc, msplat, j == 0, tail && !tail8, j * BN + 4 * lh, pp->Tk);
+                softmax_rebase<DHP>(s[0], s[1], m_run, l_run, oacc, msplat, j == 0, tail && !tail8, j * BN + 4 * lh, GTA_TK);
             softmax_exp_pack(s[0], s[1], l_run, pf);
         }
 
@@ -677,6 +692,9 @@ __global__ __launch_bounds__(256, (X3 ? 2 : DHP <= 64 ? 3 : 2)) void gta_fwd2_ke
     GTA_STAMP(V, 4); GTA_STAMPR(V, 6); GTA_STAMP_HW(V);
     par ^= 1;
     }
+#undef GTA_NT
+#undef GTA_TAIL
+#undef GTA_TK
 #undef GTA_STAMP
 #undef GTA_STAMP_ON
 #undef GTA_STAMP_HW
@@ -685,11 +703,11 @@ __global__ __launch_bounds__(256, (X3 ? 2 : DHP <= 64 ? 3 : 2)) void gta_fwd2_ke
 #undef GTA_DESC
 }
 
-template <int DHP, int ESZ, int LAYOUT, bool X3 = false>
+template <int DHP, int ESZ, int LAYOUT, bool X3 = false, bool VARLEN = false>
 int launch_fwd2(const GtaFwdParams& p, hipStream_t stream) {
     using S = Smem2<DHP, X3>;
-    const void* kfn = reinterpret_cast<const void*>(&gta_fwd2_kernel<DHP, ESZ, LAYOUT, X3>);
-    if (int rc = gta_lds_optin<&gta_fwd2_kernel<DHP, ESZ, LAYOUT, X3>>(S::total(GTA_MAX_VIEWS))) return rc;
+    const void* kfn = reinterpret_cast<const void*>(&gta_fwd2_kernel<DHP, ESZ, LAYOUT, X3, VARLEN>);
+    if (int rc = gta_lds_optin<&gta_fwd2_kernel<DHP, ESZ, LAYOUT, X3, VARLEN>>(S::total(GTA_MAX_VIEWS))) return rc;
     int lds = S::total(p.vrep_q ? p.nrec : 0);
     // One workgroup per item, or (GTA_FLAG_PERSIST / the few-rounds rule below) a persistent grid of as many workgroups as are resident at once
     // (registers and LDS: two per CU at dh = 96, three at dh = 64), a multiple of 8 so that the virtual ids of a workgroup
@@ -720,7 +738,9 @@ int launch_fwd2(const GtaFwdParams& p, hipStream_t stream) {
         // full, and walking the items with the ring running on is the faster form (35.9 against 39.3 us); at every
         // shape of five and more rounds it is the slower one (profiles/r02/README.md).
         const bool few_rounds = p.n_items > g && p.n_items <= 2 * g;
-        if (((p.flags & GTA_FLAG_PERSIST) || few_rounds) && g >= 8 && g < grid) { grid = g; pl.per_cu = per_cu; }
+        // (the VARLEN instances keep one workgroup per item: their item stream handles per-item tile counts, but no shape has been
+        //  measured or tested on the persistent grid, whose gain rests on items of equal length)
+        if (!VARLEN && ((p.flags & GTA_FLAG_PERSIST) || few_rounds) && g >= 8 && g < grid) { grid = g; pl.per_cu = per_cu; }
     }
 #ifdef GTA_ABLATE
     if (const char* e = getenv("GTA_LDS_PAD")) {        // occupancy experiment: inflate LDS so fewer workgroups share a CU
@@ -732,11 +752,11 @@ int launch_fwd2(const GtaFwdParams& p, hipStream_t stream) {
     if (g_fwd2_ev_start && g_fwd2_ev_stop) {
         // profiling hook (bench.py): start / stop events taken from the dispatch itself -- no marker packets, so the
         // kernel's neighbours in the stream are not pushed apart the way two hipEventRecord calls push them (~3 us each)
-        hipExtLaunchKernelGGL((gta_fwd2_kernel<DHP, ESZ, LAYOUT, X3>), dim3((unsigned)grid), dim3(256), lds, stream,
+        hipExtLaunchKernelGGL((gta_fwd2_kernel<DHP, ESZ, LAYOUT, X3, VARLEN>), dim3((unsigned)grid), dim3(256), lds, stream,
                               (hipEvent_t)g_fwd2_ev_start, (hipEvent_t)g_fwd2_ev_stop, 0, pl);
         g_fwd2_ev_start = g_fwd2_ev_stop = nullptr;
     } else {
-        hipLaunchKernelGGL((gta_fwd2_kernel<DHP, ESZ, LAYOUT, X3>), dim3((unsigned)grid), dim3(256), lds, stream, pl);
+        hipLaunchKernelGGL((gta_fwd2_kernel<DHP, ESZ, LAYOUT, X3, VARLEN>), dim3((unsigned)grid), dim3(256), lds, stream, pl);
     }
     return hipGetLastError() == hipSuccess ? GTA_OK : GTA_E_LAUNCH;
 }
@@ -796,6 +816,18 @@ static int launch_flash(const GtaFwdParams& p, const GtaFwdSel& s, hipStream_t s
     return launch_fwd2<DHP, ESZ, GTA_LAYOUT_GENERIC>(p, stream);
 }
 
+// the VARLEN instances (s.varlen; they read p.key_lens): gta_fwd2_kernel only, default arithmetic, every layout launch_flash gives that kernel
+template <int DHP, int ESZ>
+static int launch_flash_varlen(const GtaFwdParams& p, const GtaFwdSel& s, hipStream_t stream) {
+    if (s.kind != GTA_FWD_FWD2) return GTA_E_UNSUPPORTED;
+    switch (s.layout) {
+        case GTA_LAYOUT_MS:  if (DHP == 96) return launch_fwd2<DHP, ESZ, (DHP == 96 ? GTA_LAYOUT_MS : GTA_LAYOUT_GENERIC), false, true>(p, stream); break;
+        case GTA_LAYOUT_CL:  if (DHP == 64) return launch_fwd2<DHP, ESZ, (DHP == 64 ? GTA_LAYOUT_CL : GTA_LAYOUT_GENERIC), false, true>(p, stream); break;
+        case GTA_LAYOUT_SO2: return launch_fwd2<DHP, ESZ, GTA_LAYOUT_SO2, false, true>(p, stream);
+    }
+    return launch_fwd2<DHP, ESZ, GTA_LAYOUT_GENERIC, false, true>(p, stream);
+}
+
 // prep (unless the caller says K'/V' images are already in the workspace) + attention kernel.
 int gta_fwd2_dispatch(GtaFwdParams& p, const GtaFwdSel& s, int dhp, int esz, bool run_prep, bool run_flash, hipStream_t stream) {
     p.n_qtiles = (p.Tq + 127) / 128;
@@ -805,9 +837,19 @@ int gta_fwd2_dispatch(GtaFwdParams& p, const GtaFwdSel& s, int dhp, int esz, boo
     int rc = GTA_OK;
     // the q-side rep tiles (rho_q / rho_q^-1 on the matrix cores) only where this call's attention kernel uses them
     if (!run_flash || !s.qtiles) p.qtiles = nullptr;
-    if (run_prep) rc = gta_prep_dispatch(p, dhp, esz, stream);
+    if (s.varlen && !p.key_lens) return GTA_E_BADARG;
+    if (run_prep) rc = gta_prep_dispatch(p, dhp, esz, s.varlen, stream);
     else if (p.qtiles) rc = gta_qtiles_dispatch(p, stream);
     if (rc != GTA_OK || !run_flash) return rc;
+    if (s.varlen) {
+        switch (dhp) {
+            case 32: return esz == 2 ? launch_flash_varlen<32, 2>(p, s, stream) : launch_flash_varlen<32, 4>(p, s, stream);
+            case 64: return esz == 2 ? launch_flash_varlen<64, 2>(p, s, stream) : launch_flash_varlen<64, 4>(p, s, stream);
+            case 96: return esz == 2 ? launch_flash_varlen<96, 2>(p, s, stream) : launch_flash_varlen<96, 4>(p, s, stream);
+            case 128: return esz == 2 ? launch_flash_varlen<128, 2>(p, s, stream) : launch_flash_varlen<128, 4>(p, s, stream);
+        }
+        return GTA_E_UNSUPPORTED;
+    }
     switch (dhp) {
         case 32: return esz == 2 ? launch_flash<32, 2>(p, s, stream) : launch_flash<32, 4>(p, s, stream);
         case 64: return esz == 2 ? launch_flash<64, 2>(p, s, stream) : launch_flash<64, 4>(p, s, stream);

@@ -98,7 +98,9 @@ struct GenPrepSmem {
     static_assert(OFF_IMGK % 16 == 0, "image alignment");
 };
 
-template <int DHP>
+// VARLEN (both kernels): scene b's keys are the prefix of p.key_lens[b] tokens -- the pre-pass skips the tiles past it and treats the rows
+// of its last tile past it as it treats the rows past Tk (zero rows, bias 0, no table read); the attention kernel walks and masks by it.
+template <int DHP, bool VARLEN = false>
 __global__ __launch_bounds__(256) void gta_gen_prep_kernel(const GtaGenParams p) {
     using S = GenPrepSmem<DHP>;
     constexpr int CHP = S::CHP;
@@ -115,25 +117,32 @@ __global__ __launch_bounds__(256) void gta_gen_prep_kernel(const GtaGenParams p)
         b = r / p.n_tiles;
         j = r - b * p.n_tiles;
     }
+    int tk_b = 0;
+    if constexpr (VARLEN) {
+        tk_b = key_len_of(p.key_lens, b, p.Tk);
+        if (j * BN >= tk_b) return;
+    }
+#define GTA_TKB (VARLEN ? tk_b : p.Tk)
     const int dh = p.dh, rowf = dh + 1;
     float* sk = reinterpret_cast<float*>(smem + S::OFF_SK);
     float* sv = reinterpret_cast<float*>(smem + S::OFF_SV);
     const char* kg = (const char*)p.k + ((long)b * p.k_sb + (long)h * p.k_sh) * p.esz;
     const char* vg = (const char*)p.v + ((long)b * p.v_sb + (long)h * p.v_sh) * p.esz;
-    gen_rows_in<256>(sk, kg, p.k_st * p.esz, j * BN, p.Tk, BN, dh, p.esz, tid);
-    gen_rows_in<256>(sv, vg, p.v_st * p.esz, j * BN, p.Tk, BN, dh, p.esz, tid);
+    gen_rows_in<256>(sk, kg, p.k_st * p.esz, j * BN, GTA_TKB, BN, dh, p.esz, tid);
+    gen_rows_in<256>(sv, vg, p.v_st * p.esz, j * BN, GTA_TKB, BN, dh, p.esz, tid);
     __syncthreads();
     // rho_k: lane == key row; the rows past Tk stay zero rows (score 0 and bias 0: the attention kernel masks them)
     const int t = j * BN + lane;
     if (wave == 0) {
         ApplyParams a = gen_row_params(p, 1);
         a.key_bias = p.kbias;
-        if (t < p.Tk) apply_row(a, b, h, t, LIn{sk + lane * rowf}, LOut{sk + lane * rowf});
+        if (t < GTA_TKB) apply_row(a, b, h, t, LIn{sk + lane * rowf}, LOut{sk + lane * rowf});
         else if (p.kbias) p.kbias[((long)b * p.H + h) * a.bias_pitch + t] = 0.f;
     } else if (wave == 1 && p.xv) {
         const ApplyParams a = gen_row_params(p, 1);
-        if (t < p.Tk) apply_row(a, b, h, t, LIn{sv + lane * rowf}, LOut{sv + lane * rowf});
+        if (t < GTA_TKB) apply_row(a, b, h, t, LIn{sv + lane * rowf}, LOut{sv + lane * rowf});
     }
+#undef GTA_TKB
     __syncthreads();
     // fp32 rows -> bf16 images: an 8-channel chunk per wave and iteration, lane == key row (odd row pitch: conflict-free reads)
 #pragma unroll
@@ -165,7 +174,7 @@ GTA_DEV void gen_bias_dma(uint32_t lds, const float* src, int lane) {
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2" ::"s"(lds), "v"((unsigned)lane * 4u), "s"(src) : "memory");
 }
 
-template <int DHP, bool BIAS>
+template <int DHP, bool BIAS, bool VARLEN = false>
 __global__ __launch_bounds__(256, (DHP <= 96 ? 2 : 1)) void gta_gen_attn_kernel(const GtaGenParams p) {
     using S = Smem2<DHP>;
     constexpr int CHP = S::CHP, KS = DHP / 16, DB = DHP / 32, BM = S::BM;
@@ -182,6 +191,14 @@ __global__ __launch_bounds__(256, (DHP <= 96 ? 2 : 1)) void gta_gen_attn_kernel(
     const int b = bh / p.H, h = bh - b * p.H, q0 = qt * BM;
     const float inv_tau = 1.0f / (p.tau ? *p.tau : 1.0f);
     const float qscale = p.scale * LOG2E * inv_tau, bsc = LOG2E * inv_tau;
+    // (VARLEN) this item's key side: tk_b keys in nt_b tiles; the workspace keeps the strides of n_tiles
+    int tk_b = 0, nt_b = 0;
+    if constexpr (VARLEN) {
+        tk_b = key_len_of(p.key_lens, b, p.Tk);
+        nt_b = (tk_b + BN - 1) / BN;
+    }
+#define GTA_NT (VARLEN ? nt_b : n_tiles)
+#define GTA_TK (VARLEN ? tk_b : p.Tk)
 
     // ---- prologue: this wave's 32 query rows -> LDS, rho_q per row (fp32, in place), bf16 B fragments ----
     float* srow = reinterpret_cast<float*>(smem) + wave * 32 * rowf;
@@ -212,7 +229,7 @@ __global__ __launch_bounds__(256, (DHP <= 96 ? 2 : 1)) void gta_gen_attn_kernel(
     const char* img = (const char*)p.img + (long)bh * n_tiles * (long)S::STAGE;
     const float* kb = BIAS ? p.kbias + (long)bh * n_tiles * BN : nullptr;
     auto dma_next = [&]() {
-        if (dma_t < n_tiles) {
+        if (dma_t < GTA_NT) {
             dma_stage<DHP>(ring, dma_st, img + (long)dma_t * S::STAGE, wave, lane);
             if constexpr (BIAS) gen_bias_dma(lds_addr(bias_ring + (dma_st * 4 + wave) * GEN_BIAS_SLOT), kb + dma_t * BN, lane);
             dma_st = dma_st == S::NST - 1 ? 0 : dma_st + 1;
@@ -249,12 +266,12 @@ __global__ __launch_bounds__(256, (DHP <= 96 ? 2 : 1)) void gta_gen_attn_kernel(
     for (int d = 0; d < DB; ++d)
 #pragma unroll
         for (int i = 0; i < 16; ++i) oacc[d][i] = 0.f;
-    const bool has_tail = (p.Tk & (BN - 1)) != 0;
+    const bool has_tail = (GTA_TK & (BN - 1)) != 0;
 
-    for (int j = 0; j < n_tiles; ++j) {
+    for (int j = 0; j < GTA_NT; ++j) {
         // tile j has landed (only the stream's next tile may still be in flight), everyone is past tile j - 1
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"((S::NST - 2) * DMA_PER_WAVE) : "memory");
-        if (dma_t >= n_tiles) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // (the stream has ended: nothing younger to count on)
+        if (dma_t >= GTA_NT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // (the stream has ended: nothing younger to count on)
         __builtin_amdgcn_s_barrier();
         dma_next();
         const char* kf = ring + cons_st * S::STAGE;
@@ -298,7 +315,7 @@ __global__ __launch_bounds__(256, (DHP <= 96 ? 2 : 1)) void gta_gen_attn_kernel(
 
         // online softmax with the true row max of every tile (a bias is unbounded below: the lazy bound of gta_fwd2_kernel does not hold)
         bf16x8_t pf[2][2];
-        softmax_rebase<DHP>(s[0], s[1], m_run, l_run, oacc, msplat, j == 0, has_tail && j == n_tiles - 1, j * BN + 4 * lh, p.Tk);
+        softmax_rebase<DHP>(s[0], s[1], m_run, l_run, oacc, msplat, j == 0, has_tail && j == GTA_NT - 1, j * BN + 4 * lh, GTA_TK);
         softmax_exp_pack(s[0], s[1], l_run, pf);
 
         // ---- O^T += V'^T P^T, slab-major; reads stay one slab ahead (LDS returns in order) ----
@@ -345,6 +362,8 @@ __global__ __launch_bounds__(256, (DHP <= 96 ? 2 : 1)) void gta_gen_attn_kernel(
         char* og = (char*)p.o + ((long)b * p.o_sb + (long)h * p.o_sh) * p.esz;
         gen_rows_out<64>(srow, og, p.o_st * p.esz, t0, p.Tq, 32, dh, p.esz, lane);
     }
+#undef GTA_NT
+#undef GTA_TK
 }
 
 // what HIP said about the launch that failed: reading the error clears it, so the reader keeps the text for the caller's message
@@ -359,25 +378,25 @@ int gen_hip_status(int rc_on_error) {
     return rc_on_error;
 }
 
-template <int DHP>
+template <int DHP, bool VARLEN>
 int launch_gen_prep(const GtaGenParams& p, hipStream_t stream) {
     using S = GenPrepSmem<DHP>;
-    if (int rc = gta_lds_optin<&gta_gen_prep_kernel<DHP>>(S::TOTAL)) { gen_hip_status(rc); return rc; }
+    if (int rc = gta_lds_optin<&gta_gen_prep_kernel<DHP, VARLEN>>(S::TOTAL)) { gen_hip_status(rc); return rc; }
     const long rows = (long)p.B * p.n_tiles;
     const long grid = (rows + 7) / 8 * 8 * p.H;
     if (grid > 0x7fffffffL) { g_gen_error = "pre-pass grid too large"; return GTA_E_UNSUPPORTED; }
-    hipLaunchKernelGGL((gta_gen_prep_kernel<DHP>), dim3((unsigned)grid), dim3(256), S::TOTAL, stream, p);
+    hipLaunchKernelGGL((gta_gen_prep_kernel<DHP, VARLEN>), dim3((unsigned)grid), dim3(256), S::TOTAL, stream, p);
     return gen_hip_status(GTA_E_LAUNCH);
 }
 
 template <int DHP, bool BIAS>
 constexpr int gen_attn_lds() { return Smem2<DHP>::RING_BYTES + (BIAS ? Smem2<DHP>::NST * 4 * GEN_BIAS_SLOT : 0); }
 
-template <int DHP, bool BIAS>
+template <int DHP, bool BIAS, bool VARLEN>
 int launch_gen_attn(const GtaGenParams& p, hipStream_t stream) {
     constexpr int lds = gen_attn_lds<DHP, BIAS>();
-    if (int rc = gta_lds_optin<&gta_gen_attn_kernel<DHP, BIAS>>(lds)) { gen_hip_status(rc); return rc; }
-    hipLaunchKernelGGL((gta_gen_attn_kernel<DHP, BIAS>), dim3((unsigned)p.n_items), dim3(256), lds, stream, p);
+    if (int rc = gta_lds_optin<&gta_gen_attn_kernel<DHP, BIAS, VARLEN>>(lds)) { gen_hip_status(rc); return rc; }
+    hipLaunchKernelGGL((gta_gen_attn_kernel<DHP, BIAS, VARLEN>), dim3((unsigned)p.n_items), dim3(256), lds, stream, p);
     return gen_hip_status(GTA_E_LAUNCH);
 }
 
@@ -392,10 +411,16 @@ static_assert(gen_attn_lds<32, true>() == 27648 && gen_attn_lds<64, true>() == 5
 
 template <int DHP>
 int gen_dispatch(const GtaGenParams& p, bool run_prep, bool run_attn, hipStream_t stream) {
+    if (p.key_lens) {                                     // the VARLEN instances (gta_attn_fwd_staged_varlen)
+        if (run_prep)
+            if (int rc = launch_gen_prep<DHP, true>(p, stream)) return rc;
+        if (!run_attn) return GTA_OK;
+        return p.kbias ? launch_gen_attn<DHP, true, true>(p, stream) : launch_gen_attn<DHP, false, true>(p, stream);
+    }
     if (run_prep)
-        if (int rc = launch_gen_prep<DHP>(p, stream)) return rc;
+        if (int rc = launch_gen_prep<DHP, false>(p, stream)) return rc;
     if (!run_attn) return GTA_OK;
-    return p.kbias ? launch_gen_attn<DHP, true>(p, stream) : launch_gen_attn<DHP, false>(p, stream);
+    return p.kbias ? launch_gen_attn<DHP, true, false>(p, stream) : launch_gen_attn<DHP, false, false>(p, stream);
 }
 
 }  // namespace

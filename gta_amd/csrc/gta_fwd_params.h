@@ -10,7 +10,13 @@ struct GtaFwdParams {
     const float* vrep_q; const float* vrep_k;   // [B,N,GTA_VREP_STRIDE]
     const float* cs_q; const float* cs_k;       // [B,T,nso2,2] (cos,sin)
     const float* trans_coeff; const float* tau; // device scalars or null
-    const float* kbias; long kbias_pitch;       // optional additive per-key bias (log2 units), [B,H,pitch]
+    // One slot, two readers that never meet.  kbias: optional additive per-key bias (log2 units), [B,H,pitch] -- read by the single-kernel
+    // forward alone (gta_fwd_kernel under gta_attn_fwd_plain).  key_lens: valid keys per scene (a prefix of Tk), [B] int32 on the device --
+    // read by the VARLEN instances of the two-stage plan alone (gta_kv_prep_kernel, gta_fwd2_kernel), which GtaFwdSel::varlen selects (never the
+    // pointer: a bias that reached the two-stage dispatch would otherwise be read as lengths).  The block
+    // stays 96 dwords, so the hidden arguments behind it (the grid size the item loops read) stay put and every other instance compiles as before.
+    union { const float* kbias; const int32_t* key_lens; };
+    long kbias_pitch;
     long q_sb, q_sh, q_st, k_sb, k_sh, k_st, v_sb, v_sh, v_st, o_sb, o_sh, o_st;  // element strides
     int B, H, Tq, Tk, Nq, Nk, Pq, Pk;           // P* = tokens per view
     float invPq, invPk;
@@ -40,6 +46,7 @@ struct GtaFwdSel {
     bool qtiles;                                // the attention kernel reads the q-side rep tiles (p.qtiles)
     int rows;                                   // query rows per work item
     const char* name;                           // the kernel's own name
+    bool varlen = false;                        // the VARLEN instances of the pre-pass and of gta_fwd2_kernel: p.key_lens is the slot's reader (gta_attn_fwd_varlen sets it)
 };
 // p: the argument block with the operands of the call (p.kp = the workspace or null; p.kn, p.qtiles inside it)
 GtaFwdSel gta_fwd_select(const GtaFwdParams& p, int dhp, int esz);

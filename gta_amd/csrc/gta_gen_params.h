@@ -16,9 +16,10 @@ struct GtaGenParams {
     int euclid, xv, esz;                        // GTA_FLAG_EUCLID, GTA_FLAG_V_TRANSFORM, bytes per element of q/k/v/out
     int n_qtiles, n_items, n_tiles;             // 128-row query tiles per (b,h); B * H * n_qtiles; 64-key tiles per (b,h)
     float scale;
+    const int32_t* key_lens;                    // VARLEN instances: valid keys per scene (a prefix of Tk), [B] int32 on the device; else null (last: no other field moves)
 };
 
 long gta_gen_image_bytes(int B, int H, int Tk, int dhp);
 long gta_gen_workspace_bytes(int B, int H, int Tk, int dhp);
-int gta_gen_dispatch(const GtaGenParams& p, int dhp, bool run_prep, bool run_attn, void* stream);
+int gta_gen_dispatch(const GtaGenParams& p, int dhp, bool run_prep, bool run_attn, void* stream);      // (p.key_lens set: the VARLEN instances)
 const char* gta_gen_error();               // after a failed gta_gen_dispatch on this thread: HIP's own words for it (static storage)

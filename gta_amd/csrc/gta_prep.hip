@@ -41,9 +41,16 @@ GTA_DEV void dma_piece(const char* lds_dst, const char* src) {
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(__builtin_amdgcn_readfirstlane(lds)), "v"(src) : "memory");
 }
 
-template <int DHP, int ESZ, bool X3 = false>
+// VARLEN: scene b's keys are the prefix of p.key_lens[b] tokens.  Tiles past it are skipped (nobody reads them); the rows of its last tile
+// past it are zero rows of both images and stay out of the key norm -- the path of the rows past Tk, which loads no raw row and no
+// (cos, sin) pair of such a token (the addresses are clamped into the prefix).  The records of ALL Nk views are still copied to LDS,
+// those of padded views included: they are loaded but never used, since no valid row belongs to such a view.  So nothing a padded token
+// or view holds (NaN included) reaches the workspace.  The scene's images
+// and norms are then byte for byte those of a call on the scene alone with its key side cut to the prefix.
+template <int DHP, int ESZ, bool X3 = false, bool VARLEN = false>
 __global__ __launch_bounds__(256) void gta_kv_prep_kernel(const GtaFwdParams p) {
     static_assert(!X3 || ESZ == 4, "split-bf16 images are for fp32 inputs");
+    static_assert(!(X3 && VARLEN), "no fp32-faithful VARLEN instances");
     using S = PrepSmem<DHP, ESZ, X3>;
     constexpr int CHP = S::CHP, U = S::RAW_UNITS;
     constexpr int IMG = BN * DHP * 2;                       // bytes of one bf16 tile image
@@ -86,6 +93,12 @@ __global__ __launch_bounds__(256) void gta_kv_prep_kernel(const GtaFwdParams p) 
         b = r / n_tiles;
         j = r - b * n_tiles;
     }
+    int tk_b = 0;                                        // (VARLEN) GTA_TKB: the key count the rows of this tile are held against
+    if constexpr (VARLEN) {
+        tk_b = key_len_of(p.key_lens, b, p.Tk);
+        if (j * BN >= tk_b) return;
+    }
+#define GTA_TKB (VARLEN ? tk_b : p.Tk)
 
     const char* kg = (const char*)p.k + ((long)b * p.k_sb + (long)h * p.k_sh) * ESZ;
     const char* vg = (const char*)p.v + ((long)b * p.v_sb + (long)h * p.v_sh) * ESZ;
@@ -110,8 +123,8 @@ __global__ __launch_bounds__(256) void gta_kv_prep_kernel(const GtaFwdParams p) 
     // ... and this row's (cos, sin) pairs of the so2 chunks this wave will handle (lane == key row)
     const int r = lane;
     const int t_raw = j * BN + r;
-    const bool valid = t_raw < p.Tk;
-    const int t = valid ? t_raw : p.Tk - 1;
+    const bool valid = t_raw < GTA_TKB;
+    const int t = valid ? t_raw : GTA_TKB - 1;
     f32x4_t cs_pre[CHP / 4][2] = {};
     if (p.cs_k) {
         const float* cs_base = p.cs_k + ((long)b * p.Tk + t) * 2 * p.nso2;
@@ -140,7 +153,7 @@ __global__ __launch_bounds__(256) void gta_kv_prep_kernel(const GtaFwdParams p) 
             gu = gu < 0 ? gu + U : gu;
             gu = gu < real_units ? gu : real_units - 1;
             int gr = j * BN + r;
-            gr = gr < p.Tk ? gr : p.Tk - 1;
+            gr = gr < GTA_TKB ? gr : GTA_TKB - 1;
 #if defined(GTA_PREP_ABL) && GTA_PREP_ABL >= 4       // (levels 4, 5: no loads)
             if (p.Tk < 0)
 #endif
@@ -311,28 +324,38 @@ __global__ __launch_bounds__(256) void gta_kv_prep_kernel(const GtaFwdParams p) 
     }
     store_image(smem + S::OFF_IMGV, gimg + IMG);
     if constexpr (X3) store_image(smem + S::OFF_IMGV_LO, gimg + 3 * IMG);
+#undef GTA_TKB
 }
 
-template <int DHP, int ESZ, bool X3 = false>
+template <int DHP, int ESZ, bool X3 = false, bool VARLEN = false>
 int launch_prep(const GtaFwdParams& p, hipStream_t stream) {
     using S = PrepSmem<DHP, ESZ, X3>;
-    if (int rc = gta_lds_optin<&gta_kv_prep_kernel<DHP, ESZ, X3>>(S::total(GTA_MAX_VIEWS))) return rc;
+    if (int rc = gta_lds_optin<&gta_kv_prep_kernel<DHP, ESZ, X3, VARLEN>>(S::total(GTA_MAX_VIEWS))) return rc;
     const int n_tiles = (p.Tk + BN - 1) / BN;
     const long rows = (long)p.B * n_tiles;
     long grid = (rows + 7) / 8 * 8 * p.H;
     if (p.qtiles && p.vrep_q) grid += ((long)p.B * p.Nq + 7) / 8 * 8;        // the q-side tile builders (see the kernel's head)
     if (grid > 0x7fffffffL) return GTA_E_UNSUPPORTED;
-    hipLaunchKernelGGL((gta_kv_prep_kernel<DHP, ESZ, X3>), dim3((unsigned)grid), dim3(256), S::total(p.vrep_k ? p.Nk : 0), stream, p);
+    hipLaunchKernelGGL((gta_kv_prep_kernel<DHP, ESZ, X3, VARLEN>), dim3((unsigned)grid), dim3(256), S::total(p.vrep_k ? p.Nk : 0), stream, p);
     return hipGetLastError() == hipSuccess ? GTA_OK : GTA_E_LAUNCH;
 }
 }  // namespace
 
-int gta_prep_dispatch(const GtaFwdParams& p, int dhp, int esz, hipStream_t stream) {
+int gta_prep_dispatch(const GtaFwdParams& p, int dhp, int esz, bool varlen, hipStream_t stream) {
     if (p.flags & GTA_FLAG_FP32_PRODUCTS) {             // split-bf16 images (gta_x3_takes: fp32 inputs, dh <= 64)
         if (esz != 4) return GTA_E_UNSUPPORTED;
         switch (dhp) {
             case 32: return launch_prep<32, 4, true>(p, stream);
             case 64: return launch_prep<64, 4, true>(p, stream);
+        }
+        return GTA_E_UNSUPPORTED;
+    }
+    if (varlen) {                                       // the VARLEN instances (gta_attn_fwd_varlen): p.key_lens is theirs
+        switch (dhp) {
+            case 32: return esz == 2 ? launch_prep<32, 2, false, true>(p, stream) : launch_prep<32, 4, false, true>(p, stream);
+            case 64: return esz == 2 ? launch_prep<64, 2, false, true>(p, stream) : launch_prep<64, 4, false, true>(p, stream);
+            case 96: return esz == 2 ? launch_prep<96, 2, false, true>(p, stream) : launch_prep<96, 4, false, true>(p, stream);
+            case 128: return esz == 2 ? launch_prep<128, 2, false, true>(p, stream) : launch_prep<128, 4, false, true>(p, stream);
         }
         return GTA_E_UNSUPPORTED;
     }

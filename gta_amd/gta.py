@@ -265,32 +265,8 @@ class _GtaAttn(torch.autograd.Function):
                       k_side=not (flags & native.FLAG_PRETRANSFORMED))
         ws = None
         if not (flags & (native.FLAG_FUSED_KV | native.FLAG_PRETRANSFORMED)):
-            # what the images of a cache depend on: the key side's shape and layout, the dtype (bf16 / fp32 inputs pick different instances) and the
-            # arithmetic mode -- the fp32-faithful plan stores FOUR images per tile [K'hi | V'hi | K'lo | V'lo], the default plan two: a cache
-            # written under one plan must never be streamed under the other (the byte-size check alone let that through)
-            plan_key = (bool(flags & native.FLAG_FP32_PRODUCTS), bool(flags & native.FLAG_V_TRANSFORM), str(dt), B, H, int(k.shape[2]), dh,
-                        tuple(sorted((g, int(n)) for g, n in f_dims.items() if n)), int(so3_degree), int(Nk))
-            if kv_cache is not None and kv_cache.get("images") is not None:
-                # K'/V' tile images of an earlier call against the same keys (chunked decode): skip the pre-pass
-                ws = kv_cache["images"]
-                if kv_cache.get("plan") != plan_key:
-                    raise native.GtaError(f"kv_cache holds images written under another plan {kv_cache.get('plan')} (this call: {plan_key}): "
-                                          "use one cache dict per (key set, dtype, precise mode)")
-                if ws.numel() < native.attn_fwd_workspace_bytes(desc) or ws.device != q.device:
-                    raise native.GtaError("kv_cache holds images of a different key set")
-                desc.flags = flags | native.FLAG_KV_READY
-            else:
-                need = native.attn_fwd_workspace_bytes(desc)
-                if kv_cache is not None:
-                    # the workspace's tail (query-side operand tiles) grows with the number of QUERY views: a cache serves later query
-                    # sets against the same keys, so it is sized by asking the library for the most views a call can have (the size
-                    # rule -- which instances carry a tail, how large a tile is -- stays the library's)
-                    widest = type(desc).from_buffer_copy(desc)
-                    widest.Nq = widest.Tq = native.MAX_VIEWS
-                    need = max(need, native.attn_fwd_workspace_bytes(widest))
-                ws = torch.empty(need, device=q.device, dtype=torch.uint8)
-                if kv_cache is not None:
-                    kv_cache["images"], kv_cache["plan"] = ws, plan_key
+            plan_key = _plan_key_fused(flags, dt, B, H, k.shape[2], dh, f_dims, so3_degree, Nk)
+            ws = _two_stage_workspace(desc, flags, plan_key, kv_cache, q.device)
         if ws is not None and _GtaAttn.flash_events is not None and not (desc.flags & native.FLAG_KV_READY):
             # instrumentation (bench.py): bracket the attention kernel alone with stream events
             desc.flags = flags | native.FLAG_PREP_ONLY
@@ -501,25 +477,142 @@ def _generic_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scal
 
 
 def generic_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree: int, Nq: int, Nk: int, *, v_transform: bool = True,
-                  euclid: bool = False, precise: bool = False, needs_grad: bool = False) -> str:
+                  euclid: bool = False, precise: bool = False, needs_grad: bool = False, key_views: bool = False) -> str:
     """How ``gta_attention`` runs a call that ``attention_route`` hands to the generic path (it answered None):
     'staged' = the staged generic forward (``gta_attn_fwd_staged``: K/V pre-pass + one attention kernel, honours ``kv_cache``) when the
                library serves the descriptor, no gradient is needed and the arithmetic is the default one;
     'apply'  = ``_GenericAttn``: the rho-apply kernels around the plain attention kernel, with their adjoints for the backward.
-    Sizes alone decide, as in ``attention_route`` (the descriptor is probed at contiguous strides); needs no GPU."""
+    Sizes alone decide, as in ``attention_route`` (the descriptor is probed at contiguous strides); needs no GPU.
+    key_views=True (the call comes with per-scene view counts): 'staged' means its varlen entry (``gta_attn_fwd_staged_varlen``), and a
+    call that would be 'apply' raises ``GtaError`` instead -- ``_GenericAttn`` has no key mask."""
+    if key_views:
+        _key_views_refusals(needs_grad=needs_grad, precise=precise)
     if needs_grad or precise or dtype not in (torch.float32, torch.bfloat16):
+        if key_views:
+            raise native.GtaError(f"key_views: unsupported dtype {dtype} (use float32 or bfloat16)")
         return "apply"
     B, H, Tq, dh = q_shape
     qs, ks = (H * Tq * dh, Tq * dh, dh), (H * Tk * dh, Tk * dh, dh)
     flags = (native.FLAG_V_TRANSFORM if v_transform else 0) | (native.FLAG_EUCLID if euclid else 0)
     probe = native.make_desc_from(dtype, q_shape, Tk, (qs, ks, ks, qs), f_dims, so3_degree, Nq, Nk, 1.0, flags)
+    if key_views:
+        rc = native.attn_fwd_staged_varlen_supported(probe)
+        if rc != 0:
+            raise native.GtaError("key_views: this layout is served by the rho-apply route (_GenericAttn) alone, which has no key mask: "
+                                  f"gta_attn_fwd_staged_varlen_supported: {native.lib().gta_strerror(rc).decode()}")
+        return "staged"
     return "staged" if native.attn_fwd_staged_supported(probe) == 0 else "apply"
 
 
-def _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, kv_cache=None):
+def _key_views_refusals(*, needs_grad=False, precise=False, pretransformed=False, kv_mode="auto"):
+    """what a call with ``key_views`` cannot be combined with: said here, before anything is launched, instead of running a route without the mask"""
+    if needs_grad:
+        raise native.GtaError("key_views is forward-only (no backward with per-scene key prefixes yet): call under torch.no_grad()")
+    if precise:
+        raise native.GtaError("key_views has no precise=True (fp32-faithful) instances")
+    if pretransformed:
+        raise native.GtaError("key_views with pretransformed=True: the key mask lives in the K/V pre-pass, which that mode skips")
+    if kv_mode == "fused":
+        raise native.GtaError("key_views runs the two-stage plan: kv_mode='fused' has no per-scene key mask")
+
+
+def check_key_views(key_views, B: int, Nk: Optional[int]) -> Tuple[int, ...]:
+    """Host-side validation of per-scene view counts (a sequence or a CPU integer tensor of length B, each in 1..Nk) -> a tuple of ints.
+    Nothing here touches the device, so there is no sync."""
+    if torch.is_tensor(key_views):
+        if key_views.is_cuda:
+            raise native.GtaError("key_views must be a host sequence or a CPU tensor (validating a device tensor would sync)")
+        if key_views.is_floating_point() or key_views.is_complex() or key_views.dtype == torch.bool or key_views.dim() != 1:
+            raise native.GtaError("key_views must be a 1-D integer tensor")
+        key_views = key_views.tolist()
+    try:
+        vals = tuple(key_views)
+    except TypeError:
+        raise native.GtaError("key_views must be a sequence of B view counts") from None
+    if any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) for x in vals):
+        raise native.GtaError(f"key_views must hold integers, got {vals}")
+    vals = tuple(int(x) for x in vals)
+    if len(vals) != B:
+        raise native.GtaError(f"key_views has {len(vals)} entries for a batch of {B} scenes")
+    if Nk is None:
+        raise native.GtaError("key_views needs the number of key views Nk, which the view tables give (vrep_k): this layout has no "
+                              "se3 / so3 slab and so no view structure")
+    bad = [x for x in vals if x < 1 or x > Nk]
+    if bad:
+        raise native.GtaError(f"key_views entries must lie in 1..Nk = 1..{Nk}, got {vals}")
+    return vals
+
+
+def key_lens_tensor(key_views: Tuple[int, ...], Pk: int, device) -> torch.Tensor:
+    """[B] int32 on ``device``: the valid key TOKENS per scene (view-major tokens: a prefix), what the varlen entries read"""
+    return torch.tensor([n * Pk for n in key_views], dtype=torch.int32).to(device, non_blocking=True)
+
+
+def _plan_key_fused(flags, dt, B, H, Tk, dh, f_dims, so3_degree, Nk):
+    """what the images of a cache depend on: the key side's shape and layout, the dtype (bf16 / fp32 inputs pick different instances) and the
+    arithmetic mode -- the fp32-faithful plan stores FOUR images per tile [K'hi | V'hi | K'lo | V'lo], the default plan two: a cache
+    written under one plan must never be streamed under the other (the byte-size check alone let that through).  A call with
+    key_views appends the view counts."""
+    return (bool(flags & native.FLAG_FP32_PRODUCTS), bool(flags & native.FLAG_V_TRANSFORM), str(dt), B, H, int(Tk), dh,
+            tuple(sorted((g, int(n)) for g, n in f_dims.items() if n)), int(so3_degree), int(Nk))
+
+
+def _two_stage_workspace(desc, flags, plan_key, kv_cache, device):
+    """The K'/V' workspace of a two-stage call (``_GtaAttn`` and ``_varlen_forward`` alike): a fresh one -- stored in ``kv_cache`` with its
+    plan key when there is a cache --, or the cache's images, with GTA_FLAG_KV_READY set in ``desc``; images written under another plan or
+    for another key set raise ``GtaError``."""
+    if kv_cache is not None and kv_cache.get("images") is not None:
+        # K'/V' tile images of an earlier call against the same keys (chunked decode): skip the pre-pass
+        ws = kv_cache["images"]
+        if kv_cache.get("plan") != plan_key:
+            raise native.GtaError(f"kv_cache holds images written under another plan {kv_cache.get('plan')} (this call: {plan_key}): "
+                                  "use one cache dict per (key set, dtype, precise mode)")
+        if ws.numel() < native.attn_fwd_workspace_bytes(desc) or ws.device != device:
+            raise native.GtaError("kv_cache holds images of a different key set")
+        desc.flags = flags | native.FLAG_KV_READY
+        return ws
+    need = native.attn_fwd_workspace_bytes(desc)
+    if kv_cache is not None:
+        # the workspace's tail (query-side operand tiles) grows with the number of QUERY views: a cache serves later query
+        # sets against the same keys, so it is sized by asking the library for the most views a call can have (the size
+        # rule -- which instances carry a tail, how large a tile is -- stays the library's)
+        widest = type(desc).from_buffer_copy(desc)
+        widest.Nq = widest.Tq = native.MAX_VIEWS
+        need = max(need, native.attn_fwd_workspace_bytes(widest))
+    ws = torch.empty(need, device=device, dtype=torch.uint8)
+    if kv_cache is not None:
+        kv_cache["images"], kv_cache["plan"] = ws, plan_key
+    return ws
+
+
+def _varlen_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, flags, key_views, key_lens, kv_cache=None):
+    """The fused layouts with per-scene key prefixes, no gradient: ``gta_attn_fwd_varlen`` -- the two-stage plan's pre-pass and
+    gta_fwd2_kernel in their VARLEN instances.  ``kv_cache`` as in ``_GtaAttn``; its plan key carries the view counts."""
+    dt = q.dtype
+    k, v = k.to(dt), v.to(dt)
+    q, k, v = _as_kernel_layout(q), _as_kernel_layout(k), _as_kernel_layout(v)
+    B, H, Tq, dh = q.shape
+    Tk = k.shape[2]
+    Nq, Nk = _views(f_dims, packed, q, k)
+    out = torch.empty(B, Tq, H, dh, device=q.device, dtype=dt).permute(0, 2, 1, 3)
+    lse = torch.empty(B, H, Tq, device=q.device, dtype=torch.float32)
+    tc = trans_coeff.detach().float().reshape(-1) if torch.is_tensor(trans_coeff) else None
+    ta = tau.detach().float().reshape(-1) if torch.is_tensor(tau) else None
+    desc = native.make_desc(q, k, v, out, f_dims, so3_degree, Nq, Nk, scale, flags)
+    _check_tables(q, k, f_dims, Nq, Nk, packed.get("vrep_q"), packed.get("vrep_k"), packed.get("cs_q"), packed.get("cs_k"), None, None, tc, ta)
+    plan_key = _plan_key_fused(flags, dt, B, H, Tk, dh, f_dims, so3_degree, Nk) + (tuple(key_views),)
+    ws = _two_stage_workspace(desc, flags, plan_key, kv_cache, q.device)
+    native.attn_fwd_varlen(desc, q, k, v, packed.get("vrep_q"), packed.get("vrep_k"), packed.get("cs_q"), packed.get("cs_k"), tc, ta,
+                           key_lens, out, lse, ws)
+    return out
+
+
+def _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, kv_cache=None, key_views=None,
+                    key_lens=None):
     """The generic path without a gradient: one pre-pass launch + one attention launch (``gta_attn_fwd_staged``), and the attention
     launch alone on a call that finds its K'/V' images in ``kv_cache`` -- the contract of ``_GtaAttn``: images and plan key are stored by
-    the first call, later calls against another key set / plan raise ``GtaError``."""
+    the first call, later calls against another key set / plan raise ``GtaError``.  ``key_views`` (validated) with ``key_lens`` (device):
+    the varlen entry, and the view counts join the plan key."""
     dt = q.dtype
     k, v = k.to(dt), v.to(dt)
     q, k, v = _as_kernel_layout(q), _as_kernel_layout(k), _as_kernel_layout(v)
@@ -540,6 +633,8 @@ def _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale
     # the query side)
     plan_key = ("staged", bool(v_transform), bool(euclid), str(dt), B, H, Tk, dh,
                 tuple(sorted((g, int(n)) for g, n in f_dims.items() if n)), int(so3_degree), int(Nk), float(scale) if euclid else None)
+    if key_views is not None:
+        plan_key = plan_key + (tuple(key_views),)
     if kv_cache is not None and kv_cache.get("images") is not None:
         ws = kv_cache["images"]
         if kv_cache.get("plan") != plan_key:
@@ -552,6 +647,10 @@ def _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale
         ws = torch.empty(need, device=q.device, dtype=torch.uint8)
         if kv_cache is not None:
             kv_cache["images"], kv_cache["plan"] = ws, plan_key
+    if key_views is not None:
+        native.attn_fwd_staged_varlen(desc, q, k, v, packed.get("vrep_q"), packed.get("vrep_k"), packed.get("cs_q"), packed.get("cs_k"),
+                                      packed.get("coord_q"), packed.get("coord_k"), tc, ta, key_lens, out, lse, ws)
+        return out
     native.attn_fwd_staged(desc, q, k, v, packed.get("vrep_q"), packed.get("vrep_k"), packed.get("cs_q"), packed.get("cs_k"),
                            packed.get("coord_q"), packed.get("coord_k"), tc, ta, out, lse, ws)
     return out
@@ -560,7 +659,8 @@ def _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale
 def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: int = 0,
                   trans_coeff=None, tau=None, scale: Optional[float] = None, v_transform: bool = True,
                   euclid: bool = False, pretransformed: bool = False, use_dma: bool = True,
-                  kv_mode: str = "auto", kv_cache: Optional[dict] = None, precise: Optional[bool] = None) -> torch.Tensor:
+                  kv_mode: str = "auto", kv_cache: Optional[dict] = None, precise: Optional[bool] = None,
+                  key_views=None, key_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Fused GTA attention on packed reps.  q [B,H,Tq,dh], k/v [B,H,Tk,dh] -> out [B,H,Tq,dh].
 
     kv_mode: 'prepass' = K/V rep pre-pass + lean attention kernel (two launches; at dh = 96 in the MSN layout the attention kernel is
@@ -576,7 +676,17 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
     kv_cache: a dict owned by the caller (inference only).  The first call stores the K'/V' tile images of the
              pre-pass in it; later calls with the same keys, reps and trans_coeff (e.g. the next query chunk of a
              full-image decode, trainer.py:137-181) stream them again without re-running the pre-pass.  The layouts of the generic
-             path (t2, euclid, so3 of degree 1, unaligned slabs) honour it through the staged generic forward (``generic_route``)."""
+             path (t2, euclid, so3 of degree 1, unaligned slabs) honour it through the staged generic forward (``generic_route``).
+    key_views: per-scene numbers of valid input views -- a host sequence or CPU integer tensor of length B, each in 1..Nk (None: every
+             scene has all Nk).  Scene b attends over its first ``key_views[b]`` views (tokens are view-major, so over a prefix of its
+             keys); whatever k, v and the key-side tables hold for the other views is never used.  out and LSE are those of the call on
+             that scene alone with its key side cut to the prefix, and the padded key tiles are skipped, not computed.  Inference only,
+             default arithmetic, two-stage plan (fused layouts) or staged route (generic layouts); anything else raises ``GtaError``.
+             In self-attention the output rows of padded views are unspecified.  ``key_lens``: the ready-made device tensor of
+             ``key_lens_tensor`` for these view counts (``ForwardPlan`` keeps one); built per call when None.
+    """
+    if key_lens is not None and key_views is None:
+        raise native.GtaError("key_lens comes with the key_views it was built from")
     if scale is None:
         scale = q.shape[-1] ** -0.5
     # tables that require grad (poses / coordinates as autograd leaves): the kernels read detached tables, the gradients go to the carriers
@@ -591,9 +701,23 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
         tau = None if float(tau) == 1.0 else torch.tensor([float(tau)], device=q.device, dtype=torch.float32)
     needs_grad = torch.is_grad_enabled() and (bool(carriers) or any(torch.is_tensor(t) and t.requires_grad for t in (q, k, v, trans_coeff, tau)))
     Nq, Nk = _views(f_dims, packed, q, k)
+    if key_views is not None:
+        key_views = check_key_views(key_views, q.shape[0], Nk if "vrep_k" in packed else None)
+        if k.shape[2] % Nk:
+            raise native.GtaError(f"key_views: {k.shape[2]} key tokens do not split evenly into {Nk} views")
     flags = attention_route(tuple(q.shape), k.shape[2], q.dtype, f_dims, so3_degree, Nq, Nk, v_transform=v_transform, euclid=euclid,
                             pretransformed=pretransformed, use_dma=use_dma, kv_mode=kv_mode, kv_cache=kv_cache is not None,
-                            precise=bool(precise), needs_grad=needs_grad)
+                            precise=bool(precise), needs_grad=needs_grad, key_views=key_views is not None)
+    if key_views is not None:
+        if flags is None:
+            generic_route(tuple(q.shape), k.shape[2], q.dtype, f_dims, so3_degree, Nq, Nk, v_transform=v_transform, euclid=euclid,
+                          precise=bool(precise), needs_grad=needs_grad, key_views=True)          # ('staged', or it raises)
+        if key_lens is None:
+            key_lens = key_lens_tensor(key_views, k.shape[2] // Nk, q.device)
+        if flags is not None:
+            return _varlen_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, flags, key_views, key_lens, kv_cache)
+        return _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, kv_cache,
+                               key_views=key_views, key_lens=key_lens)
     if flags is None:
         if generic_route(tuple(q.shape), k.shape[2], q.dtype, f_dims, so3_degree, Nq, Nk, v_transform=v_transform, euclid=euclid,
                          precise=bool(precise), needs_grad=needs_grad) == "staged":
@@ -623,14 +747,30 @@ KV_MODES = {
 
 def attention_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree: int, Nq: int, Nk: int, *, v_transform: bool = True,
                     euclid: bool = False, pretransformed: bool = False, use_dma: bool = True, kv_mode: str = "auto",
-                    kv_cache: bool = False, precise: bool = False, needs_grad: bool = False) -> Optional[int]:
+                    kv_cache: bool = False, precise: bool = False, needs_grad: bool = False, key_views: bool = False) -> Optional[int]:
     """How ``gta_attention`` runs a call: the descriptor flags of the fused path, or None for the generic one (rho-apply kernels around the
     plain attention kernel).  q_shape = (B, H, Tq, dh); Tk keys; dtype of q.
 
     Sizes alone decide: the library is asked about a descriptor at contiguous strides, and its answers do not depend on strides that pass
-    its row-alignment check -- those and the ones ``_as_kernel_layout`` hands the kernels both do."""
+    its row-alignment check -- those and the ones ``_as_kernel_layout`` hands the kernels both do.
+
+    key_views=True (the call comes with per-scene view counts): the flags are those of ``gta_attn_fwd_varlen`` -- always the two-stage plan,
+    whatever ``kv_mode`` 'auto' would pick for the shape -- or None for the generic layouts (``generic_route`` then answers for its varlen
+    entry); the combinations that have no masked kernel raise ``GtaError``."""
     if kv_mode not in KV_MODES:
         raise ValueError(f"kv_mode {kv_mode!r}")
+    if key_views:
+        _key_views_refusals(needs_grad=needs_grad, precise=precise, pretransformed=pretransformed, kv_mode=kv_mode)
+        flags = (KV_MODES[kv_mode] | (native.FLAG_V_TRANSFORM if v_transform else 0) | (native.FLAG_EUCLID if euclid else 0)
+                 | (0 if use_dma else native.FLAG_NO_DMA))
+        B, H, Tq, dh = q_shape
+        qs, ks = (H * Tq * dh, Tq * dh, dh), (H * Tk * dh, Tk * dh, dh)
+        probe = native.make_desc_from(dtype, q_shape, Tk, (qs, ks, ks, qs), f_dims, so3_degree, Nq, Nk, 1.0, flags)
+        if native.attn_fwd_supported(probe) == -3:         # GTA_E_UNSUPPORTED: a generic layout
+            return None
+        # a fused layout: what the varlen entry refuses now is a flag (GTA_FLAG_FUSED_KV, ...), and that is said, not routed elsewhere
+        native.check(native.attn_fwd_varlen_supported(probe), "gta_attn_fwd_varlen_supported")
+        return flags
     flags = (KV_MODES[kv_mode] | (native.FLAG_V_TRANSFORM if v_transform else 0) | (native.FLAG_EUCLID if euclid else 0)
              | (native.FLAG_PRETRANSFORMED if pretransformed else 0) | (0 if use_dma else native.FLAG_NO_DMA))
     if precise:
@@ -684,7 +824,7 @@ def _closure_has_tau(attn_fn) -> bool:
 
 
 def multihead_geometric_transform_attention(q, k, v, attn_fn=None, f_dims=None, reps=None,
-                                            trans_coeff=1.0, v_transform=True, euclid=False, **kwargs):
+                                            trans_coeff=1.0, v_transform=True, euclid=False, key_views=None, **kwargs):
     """Drop-in for gta.py:92-279.  Returns ``(out_t, None)``.
 
     Args mirror the reference: q [B,H,Nq*Tq,C]; k, v [B,H,Nk*Tk,C]; ``f_dims`` the slab sizes;
@@ -699,6 +839,8 @@ def multihead_geometric_transform_attention(q, k, v, attn_fn=None, f_dims=None, 
 
     Arithmetic: products run on the bf16 MFMA with fp32 accumulation for fp32 inputs too (rho and the softmax are
     fp32); see DESIGN.md section 7 for the measured gap to the fp32 reference.
+
+    ``key_views``: per-scene numbers of valid input views (``gta_attention``); inference only.
     """
     if f_dims is None or reps is None:
         raise TypeError("f_dims and reps are required")
@@ -714,7 +856,7 @@ def multihead_geometric_transform_attention(q, k, v, attn_fn=None, f_dims=None, 
     out = gta_attention(q, k, v, f_dims, packed, so3_degree=_so3_degree(f_dims, packed, reps),
                         trans_coeff=trans_coeff, tau=tau, scale=scale, v_transform=v_transform, euclid=euclid,
                         use_dma=kwargs.get("use_dma", True), kv_mode=kwargs.get("kv_mode", "auto"),
-                        precise=kwargs.get("precise"))
+                        precise=kwargs.get("precise"), **({"key_views": key_views} if key_views is not None else {}))
     return out, None
 
 

@@ -158,6 +158,8 @@ class Attention(nn.Module):
         B, H, Tq, dh = q.shape
         tau = self.attend.tau if self.attend is not None else None
         if self.elementwise_mul:                                          # layers.py:410-419
+            if extras.get("key_views") is not None:
+                raise _gta.native.GtaError("key_views: the elementwise_mul ablation has no per-scene key mask")
             ex = dict(vecrep_q=self.rep_to_vec(extras["flattened_rep_q"]), vecrep_k=self.rep_to_vec(extras["flattened_rep_k"]),
                       vecinvrep_q=self.rep_to_vec(extras["flattened_invrep_q"]))
             out, _ = _gta.multihead_vecrep_attention(q, k, v, attn_fn=self, extras=ex, tau=tau)
@@ -167,13 +169,18 @@ class Attention(nn.Module):
                 attn = _gta.attention_map(ex["vecrep_q"][:, None] * q, ex["vecrep_k"][:, None] * k, {"triv": dh}, {},
                                           tau=tau, scale=self.scale)
             return out, attn
+        # per-scene numbers of valid input views (srt.TransformingSRT's input_views): absent by default
+        key_views = extras.get("key_views") if extras is not None else None
+        if key_views is not None and return_attmap:
+            raise _gta.native.GtaError("key_views with return_attmap: the dense attention map has no per-scene key mask")
         packed = _gta.pack_reps(extras, self.f_dims)
         out = _gta.gta_attention(
             q, k, v, self.f_dims, packed,
             so3_degree=_gta._so3_degree(self.f_dims, packed, extras),
             trans_coeff=self.trans_coeff, tau=tau,
             scale=self.scale, v_transform=self.method_args.get("v_transform", True), euclid=self.euclid,
-            kv_cache=kv_cache, precise=self.precise and q.dtype == torch.float32 and kv_cache is None)
+            kv_cache=kv_cache, precise=self.precise and q.dtype == torch.float32 and kv_cache is None,
+            **({"key_views": key_views} if key_views is not None else {}))
         out = out.permute(0, 2, 1, 3).reshape(B, Tq, H * dh)              # free: out is [B,Tq,H,dh] in memory
         attn = None
         if return_attmap:                                                  # layers.py:441-442

@@ -47,6 +47,7 @@ ABI_SYMBOLS = (
     "gta_debug_profile_next_attention_kernel", "gta_debug_attention_kernel",
     "gta_rep_grad_workspace_bytes", "gta_rep_grad_sums",
     "gta_attn_fwd_staged", "gta_attn_fwd_staged_supported", "gta_attn_fwd_staged_workspace_bytes",
+    "gta_attn_fwd_varlen", "gta_attn_fwd_varlen_supported", "gta_attn_fwd_staged_varlen", "gta_attn_fwd_staged_varlen_supported",
 )
 
 
@@ -129,6 +130,11 @@ def lib():
         L.gta_attn_fwd_staged_supported.argtypes = [ctypes.POINTER(GtaAttnDesc)]
         L.gta_attn_fwd_staged_workspace_bytes.argtypes = [ctypes.POINTER(GtaAttnDesc)]
         L.gta_attn_fwd_staged_workspace_bytes.restype = c_int64
+        # per-scene key prefixes: the signatures above with key_lens ([B] int32, device) in front of out
+        L.gta_attn_fwd_varlen.argtypes = [ctypes.POINTER(GtaAttnDesc)] + [c_void_p] * 13 + [c_int64, c_void_p]
+        L.gta_attn_fwd_varlen_supported.argtypes = [ctypes.POINTER(GtaAttnDesc)]
+        L.gta_attn_fwd_staged_varlen.argtypes = [ctypes.POINTER(GtaAttnDesc)] + [c_void_p] * 15 + [c_int64, c_void_p]
+        L.gta_attn_fwd_staged_varlen_supported.argtypes = [ctypes.POINTER(GtaAttnDesc)]
         _lib = L
     return _lib
 
@@ -324,6 +330,42 @@ def attn_fwd_staged(desc: GtaAttnDesc, q, k, v, vrep_q, vrep_k, cs_q, cs_k, coor
     check(lib().gta_attn_fwd_staged(ctypes.byref(desc), _ptr(q), _ptr(k), _ptr(v), _ptr(vrep_q), _ptr(vrep_k), _ptr(cs_q), _ptr(cs_k),
                                     _ptr(coord_q), _ptr(coord_k), _ptr(trans_coeff), _ptr(tau), _ptr(out), _ptr(lse),
                                     _ptr(workspace), workspace.numel(), _stream()), "gta_attn_fwd_staged")
+
+
+def _check_key_lens(key_lens, B: int, device):
+    if (not torch.is_tensor(key_lens) or key_lens.dtype != torch.int32 or key_lens.device != device or key_lens.dim() != 1
+            or key_lens.numel() != B or not key_lens.is_contiguous()):
+        raise GtaError(f"key_lens must be a contiguous int32 tensor of shape ({B},) on {device}")
+
+
+def attn_fwd_varlen_supported(desc: GtaAttnDesc) -> int:
+    """0 when gta_attn_fwd_varlen (per-scene key prefixes on the two-stage plan) serves desc, else a GTA_E_* code; needs no GPU"""
+    return lib().gta_attn_fwd_varlen_supported(ctypes.byref(desc))
+
+
+def attn_fwd_staged_varlen_supported(desc: GtaAttnDesc) -> int:
+    return lib().gta_attn_fwd_staged_varlen_supported(ctypes.byref(desc))
+
+
+def attn_fwd_varlen(desc: GtaAttnDesc, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, key_lens, out, lse, workspace: torch.Tensor):
+    """``attn_fwd`` on the two-stage plan with scene b attending over its first key_lens[b] key tokens ([B] int32 on the device);
+    workspace: uint8 CUDA tensor of >= attn_fwd_workspace_bytes(desc) bytes (sized by Tk, not by the prefixes)."""
+    _require_cuda(q, k, v, out, workspace, key_lens)
+    _check_key_lens(key_lens, desc.B, workspace.device)
+    check(lib().gta_attn_fwd_varlen(ctypes.byref(desc), _ptr(q), _ptr(k), _ptr(v), _ptr(vrep_q), _ptr(vrep_k), _ptr(cs_q), _ptr(cs_k),
+                                    _ptr(trans_coeff), _ptr(tau), _ptr(key_lens), _ptr(out), _ptr(lse),
+                                    _ptr(workspace), workspace.numel(), _stream()), "gta_attn_fwd_varlen")
+
+
+def attn_fwd_staged_varlen(desc: GtaAttnDesc, q, k, v, vrep_q, vrep_k, cs_q, cs_k, coord_q, coord_k, trans_coeff, tau, key_lens, out, lse,
+                           workspace: torch.Tensor):
+    """``attn_fwd_staged`` with per-scene key prefixes (see ``attn_fwd_varlen``)."""
+    _require_cuda(q, k, v, out, workspace, key_lens)
+    _check_key_lens(key_lens, desc.B, workspace.device)
+    check(lib().gta_attn_fwd_staged_varlen(ctypes.byref(desc), _ptr(q), _ptr(k), _ptr(v), _ptr(vrep_q), _ptr(vrep_k), _ptr(cs_q),
+                                           _ptr(cs_k), _ptr(coord_q), _ptr(coord_k), _ptr(trans_coeff), _ptr(tau), _ptr(key_lens),
+                                           _ptr(out), _ptr(lse), _ptr(workspace), workspace.numel(), _stream()),
+          "gta_attn_fwd_staged_varlen")
 
 
 def launch_info(desc: GtaAttnDesc):

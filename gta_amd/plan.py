@@ -50,25 +50,41 @@ class ForwardPlan:
 
     q, k, v: example tensors [B,H,T,dh] (any strides with unit channel stride) -- later calls must use tensors of the
     same shape, dtype and strides.  ``out`` ([B,H,Tq,dh] view of [B,Tq,H,dh] memory), ``lse`` and the workspace belong
-    to the plan and are overwritten by every call."""
+    to the plan and are overwritten by every call.
+
+    ``key_views``: per-scene numbers of valid input views (``gta_attention``), fixed when the plan is built: validated on the host and
+    turned into the device tensor of key lengths once (``key_lens``); every call then goes through the varlen entry of its family."""
 
     def __init__(self, q, k, v, f_dims: dict, *, so3_degree: int = 0, Nq: int = 1, Nk: int = 1,
-                 scale: Optional[float] = None, v_transform: bool = True, flags: int = 0, euclid: bool = False):
+                 scale: Optional[float] = None, v_transform: bool = True, flags: int = 0, euclid: bool = False, key_views=None):
         native._require_cuda(q, k, v)
         B, H, Tq, dh = q.shape
+        self.key_views = self.key_lens = None
+        if key_views is not None:
+            from .gta import check_key_views, key_lens_tensor
+            self.key_views = check_key_views(key_views, B, Nk)
+            if k.shape[2] % Nk:
+                raise native.GtaError(f"key_views: {k.shape[2]} key tokens do not split evenly into {Nk} views")
         self.out = torch.empty(B, Tq, H, dh, device=q.device, dtype=q.dtype).permute(0, 2, 1, 3)
         self.lse = torch.empty(B, H, Tq, device=q.device, dtype=torch.float32)
         fl = flags | (native.FLAG_V_TRANSFORM if v_transform else 0) | (native.FLAG_EUCLID if euclid else 0)
         self.desc = native.make_desc(q, k, v, self.out, f_dims, so3_degree, Nq, Nk,
                                      float(scale if scale is not None else dh ** -0.5), fl)
         rc = native.attn_fwd_supported(self.desc)
+        if rc == 0 and self.key_views is not None:
+            # a fused layout: what the varlen entry refuses is a flag (GTA_FLAG_FUSED_KV, GTA_FLAG_FP32_PRODUCTS, GTA_FLAG_PRETRANSFORMED) -- that
+            # raises with its reason; only a layout without a fused kernel goes on to the staged entry
+            native.check(native.attn_fwd_varlen_supported(self.desc), "gta_attn_fwd_varlen_supported")
         # layouts without a fused kernel (t2 slab, euclid, so3 of degree 1, unaligned slabs): the staged generic forward, where it serves them
-        rc_staged = native.attn_fwd_staged_supported(self.desc) if rc == -3 else rc
+        staged_supported = native.attn_fwd_staged_supported if self.key_views is None else native.attn_fwd_staged_varlen_supported
+        rc_staged = staged_supported(self.desc) if rc == -3 else rc
         self._staged = rc == -3 and rc_staged == 0
         if rc == -3 and rc_staged:                    # both entries refuse: the staged one spoke last, its reason is the library's message
-            native.check(rc_staged, "gta_attn_fwd_staged_supported")
+            native.check(rc_staged, "gta_attn_fwd_staged_supported" if self.key_views is None else "gta_attn_fwd_staged_varlen_supported")
         elif rc and not self._staged:
             native.check(rc, "gta_attn_fwd_supported")
+        if self.key_views is not None:
+            self.key_lens = key_lens_tensor(self.key_views, k.shape[2] // Nk, q.device)
         self.ws = torch.empty(native.attn_fwd_staged_workspace_bytes(self.desc) if self._staged else native.attn_fwd_workspace_bytes(self.desc),
                               device=q.device, dtype=torch.uint8)
         self._sig = (tuple(q.shape), tuple(q.stride()), tuple(k.shape), tuple(k.stride()), tuple(v.stride()), q.dtype)
@@ -105,7 +121,16 @@ class ForwardPlan:
         if flags_extra:
             d.flags = base | flags_extra
         try:
-            if self._staged:
+            if self.key_lens is not None and self._staged:
+                native.check(self._lib.gta_attn_fwd_staged_varlen(ctypes.byref(d), p(q), p(k), p(v), p(vrep_q), p(vrep_k), p(cs_q), p(cs_k),
+                                                                  p(coord_q), p(coord_k), p(trans_coeff), p(tau), p(self.key_lens),
+                                                                  p(self.out), p(self.lse), p(self.ws), self.ws.numel(), native._stream()),
+                             "gta_attn_fwd_staged_varlen")
+            elif self.key_lens is not None:
+                native.check(self._lib.gta_attn_fwd_varlen(ctypes.byref(d), p(q), p(k), p(v), p(vrep_q), p(vrep_k), p(cs_q), p(cs_k),
+                                                           p(trans_coeff), p(tau), p(self.key_lens), p(self.out), p(self.lse), p(self.ws),
+                                                           self.ws.numel(), native._stream()), "gta_attn_fwd_varlen")
+            elif self._staged:
                 native.check(self._lib.gta_attn_fwd_staged(ctypes.byref(d), p(q), p(k), p(v), p(vrep_q), p(vrep_k), p(cs_q), p(cs_k),
                                                            p(coord_q), p(coord_k), p(trans_coeff), p(tau), p(self.out), p(self.lse),
                                                            p(self.ws), self.ws.numel(), native._stream()), "gta_attn_fwd_staged")

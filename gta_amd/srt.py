@@ -171,21 +171,29 @@ class TransformingSRT(nn.Module):
             x, rays = x.flatten(1, 2), rays.flatten(1, 2)
         return self.decoder(z, x, rays, extras)
 
-    def forward(self, input_images, input_camera_pos, input_rays, target_camera_pos, target_rays, extras=None):
+    def forward(self, input_images, input_camera_pos, input_rays, target_camera_pos, target_rays, extras=None, input_views=None):
+        """``input_views``: per-scene numbers of valid input views (a host sequence of length B, each in 1..N) for batches that mix
+        view counts: scene b's first ``input_views[b]`` views are its input, the rest of its [N, ...] slots is padding that no valid
+        token ever attends to -- in the encoder's self-attention and in the decoder's cross-attention (``gta_attention``'s
+        ``key_views``).  Inference only: call under ``torch.no_grad()``."""
         extras = {} if extras is None else extras
+        if input_views is not None:
+            extras = dict(extras)                      # the caller's dict never carries these counts into a later call (as render_image)
+            extras["key_views"] = input_views
         z, extras = self.encoder(input_images, input_camera_pos, input_rays, extras)
         return self.decode(z, target_camera_pos, target_rays, extras=extras)
 
 
 @torch.no_grad()
-def render_image(model: "TransformingSRT", z, camera_pos, rays, extras, max_num_rays: int = 8192, reuse_kv: bool = True):
+def render_image(model: "TransformingSRT", z, camera_pos, rays, extras, max_num_rays: int = 8192, reuse_kv: bool = True, input_views=None):
     """Full-image decode of one target view per scene, in query chunks (trainer.py:137-181).
 
     z [B,K,C] scene tokens from ``model.encoder`` (whose call also left the key-side reps in ``extras``);
     camera_pos [B,3]; rays [B,h,w,3]; ``extras['target_transforms']`` [B,1,4,4] is the pose of the rendered view.
     Returns ``(img [B,h,w,3], {})``.  The reference re-projects K/V and re-applies rho_k for every chunk of every
     layer; here (``reuse_kv``) each cross-attention layer keeps its K/V projection and its K'/V' tile images across
-    the chunks (GTA_FLAG_KV_READY), so a chunk costs the query side plus the attention kernel only."""
+    the chunks (GTA_FLAG_KV_READY), so a chunk costs the query side plus the attention kernel only.
+    ``input_views``: per-scene numbers of valid input views (``TransformingSRT.forward``); the cached images are then the masked ones."""
     from .gta import make_2dcoord
     B, h, w = rays.shape[:3]
     coord = torch.from_numpy(make_2dcoord(h, w)).to(z.device).flatten(0, 1)[None].expand(B, -1, -1)   # [B,h*w,2]
@@ -193,6 +201,8 @@ def render_image(model: "TransformingSRT", z, camera_pos, rays, extras, max_num_
     cam = camera_pos[:, None].expand(-1, rays.shape[1], -1)
     img = torch.zeros(B, h * w, 3, dtype=camera_pos.dtype, device=camera_pos.device)
     ex = dict(extras)                                  # the caller's dict keeps its own target_* entries
+    if input_views is not None:
+        ex["key_views"] = input_views
     if reuse_kv:
         ex["gta_kv_cache"] = {}
     for i in range(0, h * w, max_num_rays):

@@ -235,6 +235,32 @@ int gta_attn_fwd_staged(const GtaAttnDesc* desc, const void* q, const void* k, c
                         const float* coord_q, const float* coord_k, const float* trans_coeff, const float* tau,
                         void* out, float* lse, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Per-scene key prefixes (gta_attention's key_views): scene b attends over its first key_lens[b] key tokens only -- with view-major
+ * tokens, over its first key_lens[b] / Pk views.  key_lens: [B] int32 on the device, in TOKENS, each in 1..Tk (the kernels clamp to that
+ * range; the Python layer validates on the host).  K, V and the key-side tables keep their [B, Tk, ...] / [B, Nk, ...] shapes; what lies at
+ * or past the prefix is never used, so it may hold anything, NaN and Inf included: rows of k, v, cs_k, coord_k there are not loaded; the
+ * vrep_k records of padded views are loaded with the others (they must be readable memory) and enter no result.
+ * out and lse of scene b are those of the same call on that scene alone with its key side cut to the prefix -- bit for bit where that
+ * call runs the same kernel family -- and the tiles past the prefix are neither built nor streamed.  Forward only.
+ *   gta_attn_fwd_varlen: the two-stage plan of gta_attn_fwd with the VARLEN instances of its pre-pass and of the 32-rows-per-wave attention kernel, gta_fwd2_kernel -- always that
+ *       kernel, whatever gta_attn_fwd would pick for the shape.  *_supported: what gta_attn_fwd_supported answers, and GTA_E_UNSUPPORTED
+ *       with the reason in gta_strerror() for GTA_FLAG_FUSED_KV, GTA_FLAG_FP32_PRODUCTS and GTA_FLAG_PRETRANSFORMED.
+ *   gta_attn_fwd_staged_varlen: the same for gta_attn_fwd_staged (any layout with dh % 8 == 0); *_supported: gta_attn_fwd_staged_supported.
+ *   workspace: required (NULL: GTA_E_BADARG), sized by gta_attn_fwd_workspace_bytes / gta_attn_fwd_staged_workspace_bytes -- by Tk, not by
+ *       the prefixes; the images of scene b occupy the first ceil(key_lens[b] / 64) tiles of its slot.  GTA_FLAG_PREP_ONLY and
+ *       GTA_FLAG_KV_READY as in the entries without key_lens; a GTA_FLAG_KV_READY call must come with the key_lens the images were built under.
+ *   key_lens == NULL: GTA_E_BADARG.  Every other argument, check and error code: as in gta_attn_fwd / gta_attn_fwd_staged. */
+int gta_attn_fwd_varlen_supported(const GtaAttnDesc* desc);
+int gta_attn_fwd_varlen(const GtaAttnDesc* desc, const void* q, const void* k, const void* v,
+                        const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
+                        const float* trans_coeff, const float* tau, const int32_t* key_lens, void* out, float* lse,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+int gta_attn_fwd_staged_varlen_supported(const GtaAttnDesc* desc);
+int gta_attn_fwd_staged_varlen(const GtaAttnDesc* desc, const void* q, const void* k, const void* v,
+                               const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
+                               const float* coord_q, const float* coord_k, const float* trans_coeff, const float* tau,
+                               const int32_t* key_lens, void* out, float* lse, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* -------------------------------------------------------------------------------------------
  * Gradients of the reps: camera poses and patch coordinates (what autograd over gta.py:134-279 gives the reference's
  * se3rep / inv_se3rep / so2rep / t2rep tensors; the Wigner-D blocks stay detached, gta.py:194-197,267).  A pass after the

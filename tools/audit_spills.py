@@ -26,19 +26,28 @@ def audit():
                         "--cuda-device-only", "-o", out, src], check=True, stderr=subprocess.DEVNULL)
         text = open(out).read()
     report, problems = [], []
-    for m in re.finditer(r"^(_ZN\w*gta_fwd2_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)E\w+):", text, re.M):
+    for m in re.finditer(r"^(_ZN\w*gta_fwd2_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)ELb(\d)E\w+):", text, re.M):
         x3 = m.group(5) == "1"          # the fp32-faithful instances (split-bf16 operands): two workgroups per CU, 256 registers
-        name, key = m.group(1), (int(m.group(2)), int(m.group(3)), int(m.group(4))) + (("x3",) if x3 else ())
+        varlen = m.group(6) == "1"      # the instances with per-scene key prefixes (gta_attn_fwd_varlen): held to the rules of their twins
+        name, key = m.group(1), (int(m.group(2)), int(m.group(3)), int(m.group(4))) + (("x3",) if x3 else ()) + (("varlen",) if varlen else ())
         body = text[m.start():text.index(".Lfunc_end", m.start())]
         meta = text[text.index(".amdhsa_kernel " + name):][:4000]
         vgpr = int(re.search(r"\.amdhsa_next_free_vgpr\s+(\d+)", meta).group(1))
         row = {"instance": key, "vgpr": vgpr, "scratch": body.count("scratch_"), "sgpr_spill_writes": body.count("v_writelane"),
                "sgpr_spill_reads": body.count("v_readlane")}
         report.append(row)
-        if (key in SHIPPED or (x3 and key[:3] in SHIPPED)) and row["scratch"]:
+        if (key in SHIPPED or ((x3 or varlen) and key[:3] in SHIPPED)) and row["scratch"]:
+            problems.append(f"perf: gta_fwd2_kernel<{key}> has {row['scratch']} scratch accesses")
+        elif varlen and key[0] <= 64 and row["scratch"]:          # (every layout of the new instances at dh <= 64, not the shipped ones alone)
             problems.append(f"perf: gta_fwd2_kernel<{key}> has {row['scratch']} scratch accesses")
         if key[0] <= 64 and vgpr > (256 if x3 else 168):
             problems.append(f"perf: gta_fwd2_kernel<{key}> needs {vgpr} VGPRs: the dh <= 64 instances must allow three waves per SIMD")
+    # a VARLEN instance never has more scratch accesses than its twin without the key prefix (a comparison inside one compiler run, so a hard
+    # criterion, not a "perf:" one: it needs no headroom)
+    scratch = {r["instance"]: r["scratch"] for r in report}
+    for key, n in scratch.items():
+        if key[-1] == "varlen" and key[:-1] in scratch and n > scratch[key[:-1]]:
+            problems.append(f"gta_fwd2_kernel<{key}> has {n} scratch accesses, its twin without VARLEN {scratch[key[:-1]]}")
     # the dh = 64 bf16 instance (gta_fwd_cl.hip, r06): three workgroups per CU, no scratch anywhere
     text = _asm("gta_fwd_cl.hip", ("-fno-slp-vectorize",))
     for name, (layout,), body, vgpr in _kernels(text, r"gta_fwdc_kernelILi(\d+)E"):
@@ -75,8 +84,9 @@ def audit_others():
     one step's 32 MFMAs) free of scratch accesses."""
     report, problems = [], []
     text = _asm("gta_prep.hip", ("-fno-slp-vectorize",))
-    for name, (dhp, esz), body, vgpr in _kernels(text, r"gta_kv_prep_kernelILi(\d+)ELi(\d+)E"):
-        row = {"kernel": f"gta_kv_prep_kernel<{dhp},{esz}>", "vgpr": vgpr, "scratch": body.count("scratch_")}
+    for name, (dhp, esz, x3, varlen), body, vgpr in _kernels(text, r"gta_kv_prep_kernelILi(\d+)ELi(\d+)ELb(\d)ELb(\d)E"):
+        row = {"kernel": f"gta_kv_prep_kernel<{dhp},{esz}{', x3' if x3 == '1' else ''}{', varlen' if varlen == '1' else ''}>", "vgpr": vgpr,
+               "scratch": body.count("scratch_")}
         report.append(row)
         if row["scratch"]:
             problems.append(f"perf: {row['kernel']}: {row['scratch']} scratch accesses")
@@ -237,11 +247,13 @@ def audit_gen():
     change that this table misses does not compile."""
     text = _asm("gta_fwd_gen.hip", ("-fno-slp-vectorize",))
     report, problems = [], []
-    for name, groups, body, vgpr in _kernels(text, r"gta_gen_(prep|attn)_kernelILi(\d+)E(?:Lb(\d)E)?"):
-        kind, dhp, bias = re.search(r"gta_gen_(prep|attn)_kernelILi(\d+)E(?:Lb(\d)E)?", name).groups()
+    for name, groups, body, vgpr in _kernels(text, r"gta_gen_(prep|attn)_kernelILi(\d+)E(?:Lb(\d)E)(?:Lb(\d)E)?"):
+        # template arguments: prep <DHP, VARLEN>, attn <DHP, BIAS, VARLEN>
+        kind, dhp, b1, b2 = re.search(r"gta_gen_(prep|attn)_kernelILi(\d+)E(?:Lb(\d)E)(?:Lb(\d)E)?", name).groups()
+        bias, varlen = (b1, b2) if kind == "attn" else ("0", b1)
         dhp = int(dhp)
         lds = (2 * 64 * (dhp + 1) * 4 + 2 * 64 * dhp * 2) if kind == "prep" else 3 * 2 * 64 * dhp * 2 + (3 * 4 * 256 if bias == "1" else 0)
-        row = {"kernel": f"gta_gen_{kind}_kernel<{dhp}{', bias' if bias == '1' else ''}>", "vgpr": vgpr, "scratch": body.count("scratch_"),
+        row = {"kernel": f"gta_gen_{kind}_kernel<{dhp}{', bias' if bias == '1' else ''}{', varlen' if varlen == '1' else ''}>", "vgpr": vgpr, "scratch": body.count("scratch_"),
                "lds_bytes": lds, "sgpr_spill_writes": body.count("v_writelane")}
         report.append(row)
         if row["scratch"]:                                # (a hard failure, not a "perf:" warning: these kernels have no spill to tolerate)
