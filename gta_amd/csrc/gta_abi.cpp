@@ -24,6 +24,7 @@ long gta_fwd2_image_bytes(int B, int H, int Tk, int dhp, bool x3);
 int gta_fwd2_lds_bytes(int dhp, int nq);
 int gta_fwd2_dispatch(GtaFwdParams& p, const GtaFwdSel& s, int dhp, int esz, bool run_prep, bool run_flash, hipStream_t stream);
 int gta_bwd_dispatch(const GtaBwdParams& p, int dhp, int esz, hipStream_t stream);
+int gta_bwd_varlen_dispatch(const GtaBwdParams& p, const int32_t* key_lens, const int32_t* q_lens, int dhp, int esz, hipStream_t stream);
 
 namespace {
 
@@ -413,15 +414,21 @@ extern "C" int64_t gta_attn_bwd_workspace_bytes(const GtaAttnDesc* desc) {
     return bwd_layout(desc).total;
 }
 
-extern "C" int gta_attn_bwd(const GtaAttnDesc* d, const void* q, const void* k, const void* v, const void* out,
-                            const void* dout, const float* lse, const float* vrep_q, const float* vrep_k,
-                            const float* cs_q, const float* cs_k, const float* trans_coeff, const float* tau,
-                            const void* kv_images, void* dq, void* dk, void* dv, const int64_t* dqkv_stride,
-                            const int64_t* dout_stride, float* dtrans_coeff, float* dtau, void* workspace,
-                            int64_t workspace_bytes,
-                            void* stream) {
+namespace {
+// both backward entries.  varlen (gta_attn_bwd_varlen) is the explicit selector of the VARLEN instances -- never "key_lens is non-null"
+int bwd_call(const GtaAttnDesc* d, const void* q, const void* k, const void* v, const void* out,
+             const void* dout, const float* lse, const float* vrep_q, const float* vrep_k,
+             const float* cs_q, const float* cs_k, const float* trans_coeff, const float* tau,
+             bool varlen, const int32_t* key_lens, const int32_t* q_lens,
+             const void* kv_images, void* dq, void* dk, void* dv, const int64_t* dqkv_stride,
+             const int64_t* dout_stride, float* dtrans_coeff, float* dtau, void* workspace,
+             int64_t workspace_bytes, void* stream) {
     int rc = check_common(d);
     if (rc) return rc;
+    if (varlen) {
+        if (!key_lens) return fail(GTA_E_BADARG, "null key_lens");
+        if ((rc = varlen_flags(d))) return rc;
+    }
     if (!q || !k || !v || !out || !dout || !lse || !dq || !dk || !dv || !dqkv_stride || !dout_stride || !workspace)
         return fail(GTA_E_BADARG, "null argument");
     if (d->flags & GTA_FLAG_PRETRANSFORMED) return fail(GTA_E_UNSUPPORTED, "backward of the pretransformed mode");
@@ -444,7 +451,12 @@ extern "C" int gta_attn_bwd(const GtaAttnDesc* d, const void* q, const void* k, 
         GtaFwdParams f;
         fwd_params(f, d, nullptr, k, v, nullptr, vrep_k, nullptr, cs_k, trans_coeff, nullptr, nullptr, nullptr, nullptr);
         f.kp = ws + L.off_kv;
-        rc = gta_fwd2_dispatch(f, gta_fwd_select(f, dhp, esz), dhp, esz, true, false, (hipStream_t)stream);
+        GtaFwdSel s = gta_fwd_select(f, dhp, esz);
+        if (varlen) {                      // the VARLEN instance of the pre-pass: the images of gta_attn_fwd_varlen under the same key_lens
+            s.varlen = true;
+            f.key_lens = key_lens;
+        }
+        rc = gta_fwd2_dispatch(f, s, dhp, esz, true, false, (hipStream_t)stream);
         if (rc) return fail(rc, "K/V pre-pass launch failed");
         kv_images = ws + L.off_kv;
     }
@@ -468,9 +480,35 @@ extern "C" int gta_attn_bwd(const GtaAttnDesc* d, const void* q, const void* k, 
     p.Pq = d->Tq / d->Nq; p.Pk = d->Tk / d->Nk; p.invPq = 1.0f / (float)p.Pq; p.invPk = 1.0f / (float)p.Pk;
     p.dh = d->dh; p.nso2 = d->d_so2 / 2; p.flags = d->flags; p.scale = d->scale;
     if (d->H > 65535 || d->B > 65535) return fail(GTA_E_UNSUPPORTED, "B or H above 65535");
-    rc = gta_bwd_dispatch(p, dhp, esz, (hipStream_t)stream);
+    rc = varlen ? gta_bwd_varlen_dispatch(p, key_lens, q_lens, dhp, esz, (hipStream_t)stream) : gta_bwd_dispatch(p, dhp, esz, (hipStream_t)stream);
     if (rc) return fail(rc, rc == GTA_E_LAUNCH ? hipGetErrorString(hipGetLastError()) : "no kernel instance");
     return GTA_OK;
+}
+}  // namespace
+
+extern "C" int gta_attn_bwd(const GtaAttnDesc* d, const void* q, const void* k, const void* v, const void* out,
+                            const void* dout, const float* lse, const float* vrep_q, const float* vrep_k,
+                            const float* cs_q, const float* cs_k, const float* trans_coeff, const float* tau,
+                            const void* kv_images, void* dq, void* dk, void* dv, const int64_t* dqkv_stride,
+                            const int64_t* dout_stride, float* dtrans_coeff, float* dtau, void* workspace,
+                            int64_t workspace_bytes,
+                            void* stream) {
+    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, false, nullptr, nullptr, kv_images, dq, dk, dv,
+                    dqkv_stride, dout_stride, dtrans_coeff, dtau, workspace, workspace_bytes, stream);
+}
+
+// Backward with per-scene prefixes: the VARLEN instances of the compiled backward kernels (gta_bwd.hip), never the generated streams
+extern "C" int gta_attn_bwd_varlen_supported(const GtaAttnDesc* desc) { return gta_attn_fwd_varlen_supported(desc); }
+
+extern "C" int gta_attn_bwd_varlen(const GtaAttnDesc* d, const void* q, const void* k, const void* v, const void* out,
+                                   const void* dout, const float* lse, const float* vrep_q, const float* vrep_k,
+                                   const float* cs_q, const float* cs_k, const float* trans_coeff, const float* tau,
+                                   const int32_t* key_lens, const int32_t* q_lens,
+                                   const void* kv_images, void* dq, void* dk, void* dv, const int64_t* dqkv_stride,
+                                   const int64_t* dout_stride, float* dtrans_coeff, float* dtau, void* workspace,
+                                   int64_t workspace_bytes, void* stream) {
+    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, true, key_lens, q_lens, kv_images, dq, dk, dv,
+                    dqkv_stride, dout_stride, dtrans_coeff, dtau, workspace, workspace_bytes, stream);
 }
 
 

@@ -173,6 +173,27 @@ GTA_DEV float wg_sum256(float v, float* scratch /*>= 4 floats LDS*/, int tid) {
 }
 
 // ================================================================================================
+// VARLEN instances (gta_attn_bwd_varlen): per-scene prefixes on both sides.  key_lens / q_lens: [B] int32 token counts on the device (q_lens may
+// be null: every query row is live), passed as trailing kernel arguments -- GtaBwdParams and the argument block of every other kernel stay as
+// they are.  A work item belongs to one (b, h), so a length is read once per item and is wave-uniform.  Workspace strides (image bases, statistics)
+// stay those of the full Tq / Tk; only the walks' lengths and the masks follow the prefixes.
+// ================================================================================================
+GTA_DEV int len_of(const int32_t* lens, int b, int T) {
+    if (!lens) return T;
+    const int n = __builtin_amdgcn_readfirstlane(lens[b]);
+    return n < 1 ? 1 : n > T ? T : n;
+}
+// zeros to rows [t0, t_end) (at most 128) of one head's gradient: the padded rows of a VARLEN call (the gradients come from torch.empty)
+template <int ESZ>
+GTA_DEV void store_zero_rows(char* g, long row_stride_bytes, int t0, int t_end, int ch_real, int tid) {
+    const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int i = tid; i < 128 * ch_real; i += 256) {
+        const int r = i / ch_real, c = i - r * ch_real;
+        if (t0 + r < t_end) g_store_chunk<ESZ>(g + (long)(t0 + r) * row_stride_bytes, c, z);
+    }
+}
+
+// ================================================================================================
 // 1. q-side pre-pass
 // ================================================================================================
 // X3 = the fp32-faithful instances (GTA_FLAG_FP32_PRODUCTS, fp32 inputs, dh <= 64; r06): a tile is FOUR images [Q''hi | dO~hi | Q''lo | dO~lo]
@@ -196,8 +217,17 @@ struct BPrepSmem {
     static int total(int nviews) { return OFF_REC + nviews * BREC * 4; }
 };
 
-template <int DHP, int ESZ, bool X3 = false>
-__global__ __launch_bounds__(256) void gta_bwd_prep_kernel(const GtaBwdParams p) {
+// VARLEN (with q_lens): rows at or past the scene's query prefix give zero image rows and statistics (-1e30, 0) -- P = 0 and dS = 0 for them in
+// both walks --, load nothing of their own (q, dout, out, lse, cs_q: the addresses are clamped into the prefix) and add no term to the partial.
+// Tiles wholly past the prefix are still written (all zero): the dQ walk of a block that straddles the prefix reads its second tile.
+// The VARLEN instances alone take the trailing argument (LENS = const int32_t*: q_lens); without it LENS is empty and the kernel's signature
+// and argument block are what they were.
+GTA_DEV const int32_t* first_len() { return nullptr; }
+GTA_DEV const int32_t* first_len(const int32_t* a) { return a; }
+template <int DHP, int ESZ, bool X3 = false, bool VARLEN = false, class... LENS>
+__global__ __launch_bounds__(256) void gta_bwd_prep_kernel(const GtaBwdParams p, LENS... lens) {
+    static_assert(!(X3 && VARLEN), "no fp32-faithful VARLEN instances");
+    static_assert(sizeof...(LENS) == (VARLEN ? 1 : 0), "q_lens comes with VARLEN");
     using S = BPrepSmem<DHP, ESZ, X3>;
     constexpr int CHP = DHP / 8, U = S::U, IMG = S::IMG;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -215,14 +245,17 @@ __global__ __launch_bounds__(256) void gta_bwd_prep_kernel(const GtaBwdParams p)
         b = r / n_qt;
         j = r - b * n_qt;
     }
+    int tq_b = 0;                                        // (VARLEN) GTA_TQB: the row count the rows of this tile are held against
+    if constexpr (VARLEN) tq_b = len_of(first_len(lens...), b, p.Tq);
+#define GTA_TQB (VARLEN ? tq_b : p.Tq)
     const int ch_real = p.dh >> 3, real_units = p.dh * ESZ / 16;
 
     const char* qg = (const char*)p.q + ((long)b * p.q_sb + (long)h * p.q_sh) * ESZ;
     const char* dog = (const char*)p.dout + ((long)b * p.do_sb + (long)h * p.do_sh) * ESZ;
     const char* og = (const char*)p.out + ((long)b * p.o_sb + (long)h * p.o_sh) * ESZ;
-    dma_raw_tile<U>(smem + S::OFF_RQ, qg, p.q_st * ESZ, j * BN, p.Tq, real_units, wave, lane);
-    dma_raw_tile<U>(smem + S::OFF_RDO, dog, p.do_st * ESZ, j * BN, p.Tq, real_units, wave, lane);
-    dma_raw_tile<U>(smem + S::OFF_RO, og, p.o_st * ESZ, j * BN, p.Tq, real_units, wave, lane);
+    dma_raw_tile<U>(smem + S::OFF_RQ, qg, p.q_st * ESZ, j * BN, GTA_TQB, real_units, wave, lane);
+    dma_raw_tile<U>(smem + S::OFF_RDO, dog, p.do_st * ESZ, j * BN, GTA_TQB, real_units, wave, lane);
+    dma_raw_tile<U>(smem + S::OFF_RO, og, p.o_st * ESZ, j * BN, GTA_TQB, real_units, wave, lane);
 
     float* rec = reinterpret_cast<float*>(smem + S::OFF_REC);
     float* dsum = reinterpret_cast<float*>(smem + S::OFF_D);
@@ -234,8 +267,8 @@ __global__ __launch_bounds__(256) void gta_bwd_prep_kernel(const GtaBwdParams p)
     const float qscale = p.scale * LOG2E / (p.tau ? *p.tau : 1.0f);
     const int r = lane;
     const int t_raw = j * BN + r;
-    const bool valid = t_raw < p.Tq;
-    const int t = valid ? t_raw : p.Tq - 1;
+    const bool valid = t_raw < GTA_TQB;
+    const int t = valid ? t_raw : GTA_TQB - 1;
     const int n = view_of(t, p.Pq, p.invPq);
     const float* rc = rec + n * BREC;
     float dpart = 0.f, dcpart = 0.f;
@@ -351,10 +384,11 @@ __global__ __launch_bounds__(256) void gta_bwd_prep_kernel(const GtaBwdParams p)
     float* st = p.stats + tile * 128;
     if (tid < 64) {
         const int tt = j * BN + tid;
-        st[tid] = tt < p.Tq ? -(p.lse[((long)b * p.H + h) * p.Tq + tt] * LOG2E) : -1e30f;
-        st[64 + tid] = tt < p.Tq ? -((dsum[tid] + dsum[64 + tid]) + (dsum[128 + tid] + dsum[192 + tid])) : 0.f;
+        st[tid] = tt < GTA_TQB ? -(p.lse[((long)b * p.H + h) * p.Tq + tt] * LOG2E) : -1e30f;
+        st[64 + tid] = tt < GTA_TQB ? -((dsum[tid] + dsum[64 + tid]) + (dsum[128 + tid] + dsum[192 + tid])) : 0.f;
     }
     if (tid == 0) p.dc_partial[p.dc_off_prep + tile] = dc_wg;
+#undef GTA_TQB
 }
 
 // ================================================================================================
@@ -398,9 +432,11 @@ GTA_DEV void dma_stats(float* dst, const float* src, int wave, int lane) {
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2" ::"s"(lds), "v"((unsigned)lane * 4u), "s"(src + 64 * (wave & 1)) : "memory");
 }
 
-template <int DHP, int ESZ>
+// VARLEN: the walk runs over the ceil(Tk_b / 64) key tiles of the scene's prefix and masks the last one against Tk_b (the image rows past the
+// prefix are zero, which alone would leave P = exp2(-lse2) there); query rows at or past Tq_b store zeros and read nothing of their own.
+template <int DHP, int ESZ, bool VARLEN = false>
 // (body: workgroup L of nwg of this kernel's grid -- its own launch, or its share of the joint launch gta_bwd_dqkv_kernel)
-GTA_DEV void bwd_dq_body(const GtaBwdParams& p, char* smem, const int L, const int nwg) {
+GTA_DEV void bwd_dq_body(const GtaBwdParams& p, char* smem, const int L, const int nwg, const int32_t* key_lens = nullptr, const int32_t* q_lens = nullptr) {
     using S = DqSmem<DHP>;
     constexpr int CHP = S::CHP, KS = DHP / 16, DB = DHP / 32, BM = 128;
     constexpr int DMA_PER_WAVE = S::STAGE / 1024 / 4;
@@ -421,6 +457,23 @@ GTA_DEV void bwd_dq_body(const GtaBwdParams& p, char* smem, const int L, const i
     const int n_tiles = (p.Tk + BN - 1) / BN;
     const int n_qt64 = (p.Tq + BN - 1) / BN;
     const int ch_real = p.dh >> 3;
+    int tk_b = 0, tq_b = 0;                               // (VARLEN) this item's prefixes
+    if constexpr (VARLEN) {
+        tk_b = len_of(key_lens, b, p.Tk);
+        tq_b = len_of(q_lens, b, p.Tq);
+        if (q0 >= tq_b) {                                 // a block wholly past the query prefix (workgroup-uniform): zeros, before any DMA or barrier
+            store_zero_rows<ESZ>((char*)p.dq + ((long)b * p.dq_sb + (long)h * p.dq_sh) * ESZ, p.dq_st * ESZ, q0, q0 + BM < p.Tq ? q0 + BM : p.Tq, ch_real, tid);
+            if (tid == 0) {
+                p.dc_partial[p.dc_off_dq + w] = 0.f;
+                if (p.dt_partial) p.dt_partial[w] = 0.f;
+            }
+            return;
+        }
+    }
+    // GTA_NT / GTA_TK / GTA_TQ: what the walk and the masks use for n_tiles / Tk / Tq (the image BASES keep the tile counts of the full sizes)
+#define GTA_NT (VARLEN ? ((tk_b + BN - 1) >> 6) : n_tiles)
+#define GTA_TK (VARLEN ? tk_b : p.Tk)
+#define GTA_TQ (VARLEN ? tq_b : p.Tq)
     char* ring = smem + S::OFF_RING;
     float* rec = reinterpret_cast<float*>(smem + S::OFF_REC);
     const char* kvimg = (const char*)p.kvimg + ((long)b * p.H + h) * n_tiles * (long)S::STAGE;
@@ -432,7 +485,7 @@ GTA_DEV void bwd_dq_body(const GtaBwdParams& p, char* smem, const int L, const i
     dma_linear4<S::STAGE>(ring + S::STAGE, (const char*)p.qimg + qtile0 * S::STAGE, wave, lane);
     if (n_my_qt == 2) dma_linear4<S::STAGE>(ring + 2 * S::STAGE, (const char*)p.qimg + (qtile0 + 1) * S::STAGE, wave, lane);
 
-    const int t_last = (q0 + BM - 1 < p.Tq ? q0 + BM - 1 : p.Tq - 1);
+    const int t_last = (q0 + BM - 1 < GTA_TQ ? q0 + BM - 1 : GTA_TQ - 1);
     const int n_first = q0 / p.Pq;
     const int n_cnt = t_last / p.Pq - n_first + 1;
     const float tc = p.trans_coeff ? *p.trans_coeff : 1.0f;
@@ -470,7 +523,7 @@ GTA_DEV void bwd_dq_body(const GtaBwdParams& p, char* smem, const int L, const i
         }
     }
     __syncthreads();
-    if (n_tiles > 1) dma_linear4<S::STAGE>(ring + S::STAGE, kvimg + (long)S::STAGE, wave, lane);
+    if (GTA_NT > 1) dma_linear4<S::STAGE>(ring + S::STAGE, kvimg + (long)S::STAGE, wave, lane);
 
     f32x16_t dq[DB];
 #pragma unroll
@@ -498,10 +551,10 @@ GTA_DEV void bwd_dq_body(const GtaBwdParams& p, char* smem, const int L, const i
     auto tile_step = [&](int j, auto STC, auto TAILC) __attribute__((always_inline)) {
         constexpr int ST = decltype(STC)::value;
         constexpr bool TAIL = decltype(TAILC)::value;
-        if (j + 1 < n_tiles) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_PER_WAVE) : "memory");
+        if (j + 1 < GTA_NT) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_PER_WAVE) : "memory");
         else                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        if (j + 2 < n_tiles) dma_linear4<S::STAGE>(ring + (ST < 0 ? (j + 2) % NSTAGE : (ST + 2) % NSTAGE) * S::STAGE, kvimg + (long)(j + 2) * S::STAGE, wave, lane);
+        if (j + 2 < GTA_NT) dma_linear4<S::STAGE>(ring + (ST < 0 ? (j + 2) % NSTAGE : (ST + 2) % NSTAGE) * S::STAGE, kvimg + (long)(j + 2) * S::STAGE, wave, lane);
         const char* kf = ring + (ST < 0 ? j % NSTAGE : ST) * S::STAGE;
         const char* vf = kf + S::IMG;
 
@@ -533,15 +586,15 @@ GTA_DEV void bwd_dq_body(const GtaBwdParams& p, char* smem, const int L, const i
         };
         tr_reads(0, 0);
         // P = exp2(S - lse2);  dS = P (dP - D);  keys past Tk contribute nothing
-        const bool tail = TAIL && (j == n_tiles - 1) && (p.Tk & (BN - 1));
+        const bool tail = TAIL && (j == GTA_NT - 1) && (GTA_TK & (BN - 1));
         const int kbase = j * BN + 4 * lh;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             float p0 = __builtin_amdgcn_exp2f(s0[r]), p1 = __builtin_amdgcn_exp2f(s1[r]);
             if (tail) {
                 const int key = kbase + (r & 3) + 8 * (r >> 2);
-                if (key >= p.Tk) p0 = 0.f;
-                if (key + 32 >= p.Tk) p1 = 0.f;
+                if (key >= GTA_TK) p0 = 0.f;
+                if (key + 32 >= GTA_TK) p1 = 0.f;
             }
             s0[r] = p0 * e0[r];
             s1[r] = p1 * e1[r];
@@ -569,13 +622,13 @@ GTA_DEV void bwd_dq_body(const GtaBwdParams& p, char* smem, const int L, const i
         };
     {
         int j = 0;
-        for (; j + NSTAGE < n_tiles; j += NSTAGE) {          // (never the last tile)
+        for (; j + NSTAGE < GTA_NT; j += NSTAGE) {          // (never the last tile)
             tile_step(j, std::integral_constant<int, 0>{}, std::false_type{});
             tile_step(j + 1, std::integral_constant<int, 1>{}, std::false_type{});
             tile_step(j + 2, std::integral_constant<int, 2>{}, std::false_type{});
         }
 #pragma unroll 1
-        for (; j < n_tiles; ++j) tile_step(j, std::integral_constant<int, -1>{}, std::true_type{});
+        for (; j < GTA_NT; ++j) tile_step(j, std::integral_constant<int, -1>{}, std::true_type{});
     }
 
     // ---- epilogue: dq = A_q^T (c1 dQ') ; d trans_coeff through A_q ----
@@ -603,7 +656,10 @@ GTA_DEV void bwd_dq_body(const GtaBwdParams& p, char* smem, const int L, const i
         const int c = item >> 1;
         const int r = lane + 64 * (item & 1);
         const int t = q0 + r;
-        if (c < ch_real && t < p.Tq) {
+        if (VARLEN && c < ch_real && t >= tq_b && t < p.Tq) {       // a row past the query prefix: zeros, nothing of the row is read
+            const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            g_store_chunk<ESZ>(dqg + (long)t * p.dq_st * ESZ, c, z);
+        } else if (c < ch_real && t < GTA_TQ) {
             const uint32_t desc = p.ctab[c];
             float x[1][8];
             const f32x4_t a = *reinterpret_cast<const f32x4_t*>(ost + r * S::OROW + 8 * c);
@@ -641,6 +697,9 @@ GTA_DEV void bwd_dq_body(const GtaBwdParams& p, char* smem, const int L, const i
         const float dt_wg = wg_sum256(dtpart, reinterpret_cast<float*>(smem + S::OFF_SCR), tid);
         if (tid == 0) p.dt_partial[w] = dt_wg;
     }
+#undef GTA_NT
+#undef GTA_TK
+#undef GTA_TQ
 }
 
 // ================================================================================================
@@ -665,8 +724,10 @@ struct DkvSmem {
     static constexpr int total(int nviews) { return OFF_REC + nviews * BREC * 4; }
 };
 
-template <int DHP, int ESZ>
-GTA_DEV void bwd_dkv_body(const GtaBwdParams& p, char* smem, const int L, const int nwg) {
+// VARLEN: a block of 128 keys wholly past the scene's prefix reads no image (those workspace tiles were never written) and stores zeros; a block
+// that straddles it holds ceil((Tk_b - k0) / 64) tiles and stores zeros for its keys past the prefix; the Q''/dO~ walk ends at ceil(Tq_b / 64) tiles.
+template <int DHP, int ESZ, bool VARLEN = false>
+GTA_DEV void bwd_dkv_body(const GtaBwdParams& p, char* smem, const int L, const int nwg, const int32_t* key_lens = nullptr, const int32_t* q_lens = nullptr) {
     using S = DkvSmem<DHP>;
     constexpr int CHP = S::CHP, KS = DHP / 16, DB = DHP / 32, BK = 128;
     constexpr int DMA_PER_WAVE = S::STAGE / 1024 / 4;
@@ -687,12 +748,28 @@ GTA_DEV void bwd_dkv_body(const GtaBwdParams& p, char* smem, const int L, const 
     const int n_kt64 = (p.Tk + BN - 1) / BN;
     const int n_qt = (p.Tq + BN - 1) / BN;
     const int ch_real = p.dh >> 3;
+    int tk_b = 0, tq_b = 0;                               // (VARLEN) this item's prefixes
+    if constexpr (VARLEN) {
+        tk_b = len_of(key_lens, b, p.Tk);
+        tq_b = len_of(q_lens, b, p.Tq);
+        if (k0 >= tk_b) {                                 // a block wholly past the key prefix (workgroup-uniform): zeros, before any DMA or barrier
+            const int t_end = k0 + BK < p.Tk ? k0 + BK : p.Tk;
+            store_zero_rows<ESZ>((char*)p.dk + ((long)b * p.dk_sb + (long)h * p.dk_sh) * ESZ, p.dk_st * ESZ, k0, t_end, ch_real, tid);
+            store_zero_rows<ESZ>((char*)p.dv + ((long)b * p.dv_sb + (long)h * p.dv_sh) * ESZ, p.dv_st * ESZ, k0, t_end, ch_real, tid);
+            if (tid == 0) p.dc_partial[p.dc_off_dkv + w] = 0.f;
+            return;
+        }
+    }
+    // GTA_KT / GTA_QT / GTA_TK: what the walk and the masks use for n_kt64 / n_qt / Tk (the image and statistics BASES keep the full sizes' counts)
+#define GTA_KT (VARLEN ? ((tk_b + BN - 1) >> 6) : n_kt64)
+#define GTA_QT (VARLEN ? ((tq_b + BN - 1) >> 6) : n_qt)
+#define GTA_TK (VARLEN ? tk_b : p.Tk)
     char* ring = smem + S::OFF_RING;
     float* stats = reinterpret_cast<float*>(smem + S::OFF_STATS);
     float* rec = reinterpret_cast<float*>(smem + S::OFF_REC);
 
     const long ktile0 = ((long)b * p.H + h) * n_kt64 + 2 * kt;
-    const int n_my_kt = (2 * kt + 1 < n_kt64) ? 2 : 1;
+    const int n_my_kt = (2 * kt + 1 < GTA_KT) ? 2 : 1;
     const char* qimg = (const char*)p.qimg + ((long)b * p.H + h) * n_qt * (long)S::STAGE;
     const float* gstats = p.stats + ((long)b * p.H + h) * n_qt * 128;
     dma_linear4<S::STAGE>(smem + S::OFF_KV, (const char*)p.kvimg + ktile0 * S::STAGE, wave, lane);
@@ -700,7 +777,7 @@ GTA_DEV void bwd_dkv_body(const GtaBwdParams& p, char* smem, const int L, const 
     dma_linear4<S::STAGE>(ring, qimg, wave, lane);
     dma_stats(stats, gstats, wave, lane);
 
-    const int t_last = (k0 + BK - 1 < p.Tk ? k0 + BK - 1 : p.Tk - 1);
+    const int t_last = (k0 + BK - 1 < GTA_TK ? k0 + BK - 1 : GTA_TK - 1);
     const int n_first = k0 / p.Pk;
     const int n_cnt = t_last / p.Pk - n_first + 1;
     const float tc = p.trans_coeff ? *p.trans_coeff : 1.0f;
@@ -732,7 +809,7 @@ GTA_DEV void bwd_dkv_body(const GtaBwdParams& p, char* smem, const int L, const 
         }
     }
     __syncthreads();      // every wave holds its K'/V' fragments: ring stages 1..2 are free
-    if (n_qt > 1) {
+    if (GTA_QT > 1) {
         dma_linear4<S::STAGE>(ring + S::STAGE, qimg + (long)S::STAGE, wave, lane);
         dma_stats(stats + 128, gstats + 128, wave, lane);
     }
@@ -768,13 +845,13 @@ GTA_DEV void bwd_dkv_body(const GtaBwdParams& p, char* smem, const int L, const 
         // tile j's images and statistics have landed when only tile j + 1's (requested one tile ago) are in flight.  No compiler-visible
         // load in the loop: one would be waited for with vmcnt(0) -- the compiler does not count the DMA -- and drain the request
         // made two tiles ahead after one
-        if (j + 1 < n_qt) {
+        if (j + 1 < GTA_QT) {
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DMA_PER_WAVE + 1) : "memory");
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         __builtin_amdgcn_s_barrier();
-        if (j + 2 < n_qt) {
+        if (j + 2 < GTA_QT) {
             dma_linear4<S::STAGE>(ring + (ST < 0 ? (j + 2) % NSTAGE : (ST + 2) % NSTAGE) * S::STAGE, qimg + (long)(j + 2) * S::STAGE, wave, lane);
             dma_stats(stats + (ST < 0 ? (j + 2) % NSTAGE : (ST + 2) % NSTAGE) * 128, gstats + (long)(j + 2) * 128, wave, lane);
         }
@@ -850,13 +927,13 @@ GTA_DEV void bwd_dkv_body(const GtaBwdParams& p, char* smem, const int L, const 
         };
     {
         int j = 0;
-        for (; j + NSTAGE <= n_qt; j += NSTAGE) {
+        for (; j + NSTAGE <= GTA_QT; j += NSTAGE) {
             tile_step(j, std::integral_constant<int, 0>{});
             tile_step(j + 1, std::integral_constant<int, 1>{});
             tile_step(j + 2, std::integral_constant<int, 2>{});
         }
 #pragma unroll 1
-        for (; j < n_qt; ++j) tile_step(j, std::integral_constant<int, -1>{});
+        for (; j < GTA_QT; ++j) tile_step(j, std::integral_constant<int, -1>{});
     }
 
     // ---- epilogue: dk = B_k^T (ln2 dK'), dv = B_k^T dV' ; d trans_coeff through B_k ----
@@ -894,7 +971,10 @@ GTA_DEV void bwd_dkv_body(const GtaBwdParams& p, char* smem, const int L, const 
             const int c = item >> 1;
             const int r = lane + 64 * (item & 1);
             const int t = k0 + r;
-            if (c < ch_real && t < p.Tk) {
+            if (VARLEN && c < ch_real && t >= tk_b && t < p.Tk) {   // a key past the prefix: zeros, nothing of the key is read
+                const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                g_store_chunk<ESZ>(outg + (long)t * out_st, c, z);
+            } else if (c < ch_real && t < GTA_TK) {
                 const uint32_t desc = p.ctab[c];
                 float x[1][8];
                 const f32x4_t a = *reinterpret_cast<const f32x4_t*>(ost + r * S::OROW + 8 * c);
@@ -921,6 +1001,9 @@ GTA_DEV void bwd_dkv_body(const GtaBwdParams& p, char* smem, const int L, const 
     }
     const float dc_wg = wg_sum256(dcpart, reinterpret_cast<float*>(smem + S::OFF_SCR), tid);
     if (tid == 0) p.dc_partial[p.dc_off_dkv + w] = dc_wg;
+#undef GTA_KT
+#undef GTA_QT
+#undef GTA_TK
 }
 
 // the two compiled kernels, and both in ONE launch (as gta_bwd_dqkv64_kernel for the generated pair, below: they depend on the q-side pre-pass
@@ -935,6 +1018,17 @@ template <int DHP, int ESZ>
 __global__ __launch_bounds__(256, (DHP > 96 ? 1 : 2)) void gta_bwd_dkv_kernel(const GtaBwdParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     bwd_dkv_body<DHP, ESZ>(p, smem, blockIdx.x, gridDim.x);
+}
+// the VARLEN instances: always two launches (the joint launch's n_dkv % 8 == 0 rule would make the form depend on the shape for no measured gain)
+template <int DHP, int ESZ>
+__global__ __launch_bounds__(256, (DHP > 96 ? 1 : 2)) void gta_bwd_dq_varlen_kernel(const GtaBwdParams p, const int32_t* key_lens, const int32_t* q_lens) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    bwd_dq_body<DHP, ESZ, true>(p, smem, blockIdx.x, gridDim.x, key_lens, q_lens);
+}
+template <int DHP, int ESZ>
+__global__ __launch_bounds__(256, (DHP > 96 ? 1 : 2)) void gta_bwd_dkv_varlen_kernel(const GtaBwdParams p, const int32_t* key_lens, const int32_t* q_lens) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    bwd_dkv_body<DHP, ESZ, true>(p, smem, blockIdx.x, gridDim.x, key_lens, q_lens);
 }
 template <int DHP, int ESZ>
 __global__ __launch_bounds__(256, (DHP > 96 ? 1 : 2)) void gta_bwd_dqkv_kernel(const GtaBwdParams p, const int n_dq) {
@@ -1907,7 +2001,42 @@ int run_bwd(const GtaBwdParams& p, hipStream_t stream) {
     return hipGetLastError() == hipSuccess ? GTA_OK : GTA_E_LAUNCH;
 }
 
+// gta_attn_bwd_varlen: the VARLEN instances of the compiled kernels, whatever run_bwd would select for the shape (never the generated streams)
+template <int DHP, int ESZ>
+int run_bwd_varlen(const GtaBwdParams& p, const int32_t* key_lens, const int32_t* q_lens, hipStream_t stream) {
+    const int n_qt = (p.Tq + BN - 1) / BN;
+    if (int rc = gta_lds_optin<&gta_bwd_prep_kernel<DHP, ESZ, false, true, const int32_t*>>(BPrepSmem<DHP, ESZ>::total(GTA_MAX_VIEWS))) return rc;
+    if (int rc = gta_lds_optin<&gta_bwd_dq_varlen_kernel<DHP, ESZ>>(DqSmem<DHP>::total(GTA_MAX_VIEWS))) return rc;
+    if (int rc = gta_lds_optin<&gta_bwd_dkv_varlen_kernel<DHP, ESZ>>(DkvSmem<DHP>::total(GTA_MAX_VIEWS))) return rc;
+    const long prep_grid = ((long)p.B * n_qt + 7) / 8 * 8 * p.H;
+    const long n_dq = (long)p.B * p.H * ((p.Tq + 127) / 128), n_dkv = (long)p.B * p.H * ((p.Tk + 127) / 128);
+    if (prep_grid > 0x7fffffffL || n_dq > 0x7fffffffL || n_dkv > 0x7fffffffL) return GTA_E_UNSUPPORTED;
+    const int lds_prep = BPrepSmem<DHP, ESZ>::total(p.vrep_q ? p.Nq : 0);
+    const int lds_dq = DqSmem<DHP>::total(p.vrep_q ? p.Nq : 0), lds_dkv = DkvSmem<DHP>::total(p.vrep_k ? p.Nk : 0);
+    hipLaunchKernelGGL((gta_bwd_prep_kernel<DHP, ESZ, false, true, const int32_t*>), dim3((unsigned)prep_grid), dim3(256), lds_prep, stream, p, q_lens);
+    hipLaunchKernelGGL((gta_bwd_dq_varlen_kernel<DHP, ESZ>), dim3((unsigned)n_dq), dim3(256), lds_dq, stream, p, key_lens, q_lens);
+    hipLaunchKernelGGL((gta_bwd_dkv_varlen_kernel<DHP, ESZ>), dim3((unsigned)n_dkv), dim3(256), lds_dkv, stream, p, key_lens, q_lens);
+    if (p.dtrans_coeff)
+        hipLaunchKernelGGL(gta_reduce_kernel, dim3(1), dim3(1024), 0, stream, p.dc_partial, p.dc_total, p.dtrans_coeff, (const float*)nullptr);
+    if (p.dtau)
+        hipLaunchKernelGGL(gta_reduce_kernel, dim3(1), dim3(1024), 0, stream, p.dt_partial, (int)n_dq, p.dtau, p.tau);
+    return hipGetLastError() == hipSuccess ? GTA_OK : GTA_E_LAUNCH;
+}
+
 }  // namespace
+
+int gta_bwd_varlen_dispatch(const GtaBwdParams& p, const int32_t* key_lens, const int32_t* q_lens, int dhp, int esz, hipStream_t stream) {
+    if (!key_lens || (p.flags & GTA_FLAG_FP32_PRODUCTS)) return GTA_E_UNSUPPORTED;
+#define GTA_CASEB(D) case D: return esz == 2 ? run_bwd_varlen<D, 2>(p, key_lens, q_lens, stream) : run_bwd_varlen<D, 4>(p, key_lens, q_lens, stream);
+    switch (dhp) {
+        GTA_CASEB(32)
+        GTA_CASEB(64)
+        GTA_CASEB(96)
+        GTA_CASEB(128)
+    }
+#undef GTA_CASEB
+    return GTA_E_UNSUPPORTED;
+}
 
 int gta_bwd_dispatch(const GtaBwdParams& p, int dhp, int esz, hipStream_t stream) {
     if (p.flags & GTA_FLAG_FP32_PRODUCTS) {             // the fp32-faithful backward on the matrix cores (gta_fwd_params.h)

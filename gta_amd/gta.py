@@ -477,16 +477,21 @@ def _generic_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scal
 
 
 def generic_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree: int, Nq: int, Nk: int, *, v_transform: bool = True,
-                  euclid: bool = False, precise: bool = False, needs_grad: bool = False, key_views: bool = False) -> str:
+                  euclid: bool = False, precise: bool = False, needs_grad: bool = False, key_views: bool = False,
+                  key_views_backward: bool = False) -> str:
     """How ``gta_attention`` runs a call that ``attention_route`` hands to the generic path (it answered None):
     'staged' = the staged generic forward (``gta_attn_fwd_staged``: K/V pre-pass + one attention kernel, honours ``kv_cache``) when the
                library serves the descriptor, no gradient is needed and the arithmetic is the default one;
     'apply'  = ``_GenericAttn``: the rho-apply kernels around the plain attention kernel, with their adjoints for the backward.
     Sizes alone decide, as in ``attention_route`` (the descriptor is probed at contiguous strides); needs no GPU.
     key_views=True (the call comes with per-scene view counts): 'staged' means its varlen entry (``gta_attn_fwd_staged_varlen``), and a
-    call that would be 'apply' raises ``GtaError`` instead -- ``_GenericAttn`` has no key mask."""
+    call that would be 'apply' raises ``GtaError`` instead -- ``_GenericAttn`` has no key mask; that holds under ``key_views_backward`` too (the
+    backward with per-scene prefixes serves the fused layouts alone)."""
     if key_views:
-        _key_views_refusals(needs_grad=needs_grad, precise=precise)
+        _key_views_refusals(needs_grad=needs_grad, precise=precise, key_views_backward=key_views_backward)
+        if needs_grad:
+            raise native.GtaError("key_views_backward: the staged generic layouts (t2, euclid, so3 of degree 1, unaligned slabs) have no backward "
+                                  "with a key mask")
     if needs_grad or precise or dtype not in (torch.float32, torch.bfloat16):
         if key_views:
             raise native.GtaError(f"key_views: unsupported dtype {dtype} (use float32 or bfloat16)")
@@ -504,9 +509,10 @@ def generic_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree: i
     return "staged" if native.attn_fwd_staged_supported(probe) == 0 else "apply"
 
 
-def _key_views_refusals(*, needs_grad=False, precise=False, pretransformed=False, kv_mode="auto"):
-    """what a call with ``key_views`` cannot be combined with: said here, before anything is launched, instead of running a route without the mask"""
-    if needs_grad:
+def _key_views_refusals(*, needs_grad=False, precise=False, pretransformed=False, kv_mode="auto", key_views_backward=False):
+    """what a call with ``key_views`` cannot be combined with: said here, before anything is launched, instead of running a route without the mask.
+    ``key_views_backward`` opts in to the backward (``gta_attn_bwd_varlen``); without it a call under grad is refused as before."""
+    if needs_grad and not key_views_backward:
         raise native.GtaError("key_views is forward-only (no backward with per-scene key prefixes yet): call under torch.no_grad()")
     if precise:
         raise native.GtaError("key_views has no precise=True (fp32-faithful) instances")
@@ -516,9 +522,14 @@ def _key_views_refusals(*, needs_grad=False, precise=False, pretransformed=False
         raise native.GtaError("key_views runs the two-stage plan: kv_mode='fused' has no per-scene key mask")
 
 
-def check_key_views(key_views, B: int, Nk: Optional[int]) -> Tuple[int, ...]:
+def check_key_views(key_views, B: int, Nk: Optional[int], name: str = "key_views") -> Tuple[int, ...]:
     """Host-side validation of per-scene view counts (a sequence or a CPU integer tensor of length B, each in 1..Nk) -> a tuple of ints.
-    Nothing here touches the device, so there is no sync."""
+    Nothing here touches the device, so there is no sync.  ``name``: what the messages call the argument (``query_views`` against Nq)."""
+    if name != "key_views":
+        try:
+            return check_key_views(key_views, B, Nk)
+        except native.GtaError as e:
+            raise native.GtaError(str(e).replace("key_views", name).replace("Nk", "Nq").replace("vrep_k", "vrep_q").replace("key views", "query views")) from None
     if torch.is_tensor(key_views):
         if key_views.is_cuda:
             raise native.GtaError("key_views must be a host sequence or a CPU tensor (validating a device tensor would sync)")
@@ -607,6 +618,50 @@ def _varlen_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale
     return out
 
 
+class _VarlenAttn(torch.autograd.Function):
+    """The fused layouts with per-scene key prefixes under grad (``key_views_backward=True``): ``gta_attn_fwd_varlen`` forward, whose workspace
+    (the masked K'/V' tile images) and LSE serve ``gta_attn_bwd_varlen``.  ``q_lens`` (or None) masks padded query rows in the backward only.
+    Gradients: q, k, v, trans_coeff, tau -- as ``_GtaAttn``; none for the tables."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, trans_coeff, tau, cfg, key_lens, q_lens, vrep_q, vrep_k, cs_q, cs_k):
+        f_dims, so3_degree, Nq, Nk, scale, flags = cfg
+        dt = q.dtype
+        if dt not in (torch.float32, torch.bfloat16):
+            raise native.GtaError(f"unsupported dtype {dt}: use float32 or bfloat16")
+        k = k.to(dt) if k.dtype != dt else k
+        v = v.to(dt) if v.dtype != dt else v
+        q, k, v = _as_kernel_layout(q), _as_kernel_layout(k), _as_kernel_layout(v)
+        B, H, Tq, dh = q.shape
+        out = torch.empty(B, Tq, H, dh, device=q.device, dtype=dt).permute(0, 2, 1, 3)
+        lse = torch.empty(B, H, Tq, device=q.device, dtype=torch.float32)
+        tc = trans_coeff.detach().to(torch.float32).reshape(-1) if trans_coeff is not None else None
+        ta = tau.detach().to(torch.float32).reshape(-1) if tau is not None else None
+        desc = native.make_desc(q, k, v, out, f_dims, so3_degree, Nq, Nk, scale, flags)
+        _check_tables(q, k, f_dims, Nq, Nk, vrep_q, vrep_k, cs_q, cs_k, None, None, tc, ta)
+        native._require_cuda(q, k, v)
+        ws = torch.empty(native.attn_fwd_workspace_bytes(desc), device=q.device, dtype=torch.uint8)
+        native.attn_fwd_varlen(desc, q, k, v, vrep_q, vrep_k, cs_q, cs_k, tc, ta, key_lens, out, lse, ws)
+        ctx.cfg = cfg
+        ctx.kv_images = ws
+        ctx.save_for_backward(q, k, v, out, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k, key_lens, q_lens)
+        ctx.tc_meta = None if trans_coeff is None else (trans_coeff.shape, trans_coeff.dtype)
+        ctx.tau_meta = None if tau is None else (tau.shape, tau.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from . import backward as _bw
+        q, k, v, out, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k, key_lens, q_lens = ctx.saved_tensors
+        want_dtau = ta is not None and ctx.needs_input_grad[4]
+        dq, dk, dv, dtc, dta = _bw.attn_bwd(ctx.cfg, q, k, v, out, dout, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k,
+                                            kv_images=ctx.kv_images, want_dtau=want_dtau, key_lens=key_lens, q_lens=q_lens)
+        dtc = dtc.reshape(ctx.tc_meta[0]).to(ctx.tc_meta[1]) if (ctx.tc_meta is not None and dtc is not None) else None
+        if dta is not None:
+            dta = dta.reshape(ctx.tau_meta[0]).to(ctx.tau_meta[1])
+        return (dq, dk, dv, dtc, dta) + (None,) * 7
+
+
 def _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, kv_cache=None, key_views=None,
                     key_lens=None):
     """The generic path without a gradient: one pre-pass launch + one attention launch (``gta_attn_fwd_staged``), and the attention
@@ -660,7 +715,8 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
                   trans_coeff=None, tau=None, scale: Optional[float] = None, v_transform: bool = True,
                   euclid: bool = False, pretransformed: bool = False, use_dma: bool = True,
                   kv_mode: str = "auto", kv_cache: Optional[dict] = None, precise: Optional[bool] = None,
-                  key_views=None, key_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  key_views=None, key_lens: Optional[torch.Tensor] = None, key_views_backward: bool = False,
+                  query_views=None) -> torch.Tensor:
     """Fused GTA attention on packed reps.  q [B,H,Tq,dh], k/v [B,H,Tk,dh] -> out [B,H,Tq,dh].
 
     kv_mode: 'prepass' = K/V rep pre-pass + lean attention kernel (two launches; at dh = 96 in the MSN layout the attention kernel is
@@ -684,7 +740,18 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
              default arithmetic, two-stage plan (fused layouts) or staged route (generic layouts); anything else raises ``GtaError``.
              In self-attention the output rows of padded views are unspecified.  ``key_lens``: the ready-made device tensor of
              ``key_lens_tensor`` for these view counts (``ForwardPlan`` keeps one); built per call when None.
+    key_views_backward: False (default): a call with ``key_views`` under grad raises "forward-only", as it always did.  True: the call is
+             differentiable in q, k, v, trans_coeff and tau on the fused layouts (``gta_attn_fwd_varlen`` + ``gta_attn_bwd_varlen``): dk / dv rows
+             of padded views are exactly zero and nothing of a padded view is read.  Still refused, by name: the staged generic layouts under
+             grad, precise=True, pretransformed, kv_mode='fused', and any rep table or pose that requires grad.
+    query_views: only with ``key_views_backward=True``; validated like ``key_views``, against Nq.  Backward only: the query rows of scene b's
+             views past ``query_views[b]`` (self-attention over padded views, where they hold anything) send no gradient -- their ``dout`` is
+             never read, their dq rows are zero.  The forward still computes (unspecified) output rows for them.
     """
+    if query_views is not None and not key_views_backward:
+        raise native.GtaError("query_views masks padded query rows in the backward: it needs key_views_backward=True")
+    if key_views_backward and key_views is None:
+        raise native.GtaError("key_views_backward=True comes with key_views")
     if key_lens is not None and key_views is None:
         raise native.GtaError("key_lens comes with the key_views it was built from")
     if scale is None:
@@ -705,15 +772,29 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
         key_views = check_key_views(key_views, q.shape[0], Nk if "vrep_k" in packed else None)
         if k.shape[2] % Nk:
             raise native.GtaError(f"key_views: {k.shape[2]} key tokens do not split evenly into {Nk} views")
+        if query_views is not None:
+            query_views = check_key_views(query_views, q.shape[0], Nq if "vrep_q" in packed else None, name="query_views")
+            if q.shape[2] % Nq:
+                raise native.GtaError(f"query_views: {q.shape[2]} query tokens do not split evenly into {Nq} views")
+        if key_views_backward and carriers:
+            raise native.GtaError("key_views_backward: no gradient for rep tables or poses under key_views (gta_rep_grad_sums has no key mask): "
+                                  "detach the tables")
     flags = attention_route(tuple(q.shape), k.shape[2], q.dtype, f_dims, so3_degree, Nq, Nk, v_transform=v_transform, euclid=euclid,
                             pretransformed=pretransformed, use_dma=use_dma, kv_mode=kv_mode, kv_cache=kv_cache is not None,
-                            precise=bool(precise), needs_grad=needs_grad, key_views=key_views is not None)
+                            precise=bool(precise), needs_grad=needs_grad, key_views=key_views is not None,
+                            key_views_backward=bool(key_views_backward))
     if key_views is not None:
         if flags is None:
             generic_route(tuple(q.shape), k.shape[2], q.dtype, f_dims, so3_degree, Nq, Nk, v_transform=v_transform, euclid=euclid,
-                          precise=bool(precise), needs_grad=needs_grad, key_views=True)          # ('staged', or it raises)
+                          precise=bool(precise), needs_grad=needs_grad, key_views=True,
+                          key_views_backward=bool(key_views_backward))                          # ('staged', or it raises)
         if key_lens is None:
             key_lens = key_lens_tensor(key_views, k.shape[2] // Nk, q.device)
+        if flags is not None and needs_grad:          # (key_views_backward: anything else was refused above)
+            q_lens = None if query_views is None else key_lens_tensor(query_views, q.shape[2] // Nq, q.device)
+            cfg = ({k_: int(v_) for k_, v_ in f_dims.items()}, int(so3_degree), Nq, Nk, float(scale), flags)
+            return _VarlenAttn.apply(q, k, v, trans_coeff, tau, cfg, key_lens, q_lens, packed.get("vrep_q"), packed.get("vrep_k"),
+                                     packed.get("cs_q"), packed.get("cs_k"))
         if flags is not None:
             return _varlen_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, flags, key_views, key_lens, kv_cache)
         return _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, kv_cache,
@@ -747,7 +828,8 @@ KV_MODES = {
 
 def attention_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree: int, Nq: int, Nk: int, *, v_transform: bool = True,
                     euclid: bool = False, pretransformed: bool = False, use_dma: bool = True, kv_mode: str = "auto",
-                    kv_cache: bool = False, precise: bool = False, needs_grad: bool = False, key_views: bool = False) -> Optional[int]:
+                    kv_cache: bool = False, precise: bool = False, needs_grad: bool = False, key_views: bool = False,
+                    key_views_backward: bool = False) -> Optional[int]:
     """How ``gta_attention`` runs a call: the descriptor flags of the fused path, or None for the generic one (rho-apply kernels around the
     plain attention kernel).  q_shape = (B, H, Tq, dh); Tk keys; dtype of q.
 
@@ -756,11 +838,13 @@ def attention_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree:
 
     key_views=True (the call comes with per-scene view counts): the flags are those of ``gta_attn_fwd_varlen`` -- always the two-stage plan,
     whatever ``kv_mode`` 'auto' would pick for the shape -- or None for the generic layouts (``generic_route`` then answers for its varlen
-    entry); the combinations that have no masked kernel raise ``GtaError``."""
+    entry); the combinations that have no masked kernel raise ``GtaError``.  key_views_backward=True lets needs_grad through: the same flags
+    serve ``gta_attn_bwd_varlen``."""
     if kv_mode not in KV_MODES:
         raise ValueError(f"kv_mode {kv_mode!r}")
     if key_views:
-        _key_views_refusals(needs_grad=needs_grad, precise=precise, pretransformed=pretransformed, kv_mode=kv_mode)
+        _key_views_refusals(needs_grad=needs_grad, precise=precise, pretransformed=pretransformed, kv_mode=kv_mode,
+                            key_views_backward=key_views_backward)
         flags = (KV_MODES[kv_mode] | (native.FLAG_V_TRANSFORM if v_transform else 0) | (native.FLAG_EUCLID if euclid else 0)
                  | (0 if use_dma else native.FLAG_NO_DMA))
         B, H, Tq, dh = q_shape
@@ -824,7 +908,8 @@ def _closure_has_tau(attn_fn) -> bool:
 
 
 def multihead_geometric_transform_attention(q, k, v, attn_fn=None, f_dims=None, reps=None,
-                                            trans_coeff=1.0, v_transform=True, euclid=False, key_views=None, **kwargs):
+                                            trans_coeff=1.0, v_transform=True, euclid=False, key_views=None, key_views_backward=False,
+                                            query_views=None, **kwargs):
     """Drop-in for gta.py:92-279.  Returns ``(out_t, None)``.
 
     Args mirror the reference: q [B,H,Nq*Tq,C]; k, v [B,H,Nk*Tk,C]; ``f_dims`` the slab sizes;
@@ -840,7 +925,8 @@ def multihead_geometric_transform_attention(q, k, v, attn_fn=None, f_dims=None, 
     Arithmetic: products run on the bf16 MFMA with fp32 accumulation for fp32 inputs too (rho and the softmax are
     fp32); see DESIGN.md section 7 for the measured gap to the fp32 reference.
 
-    ``key_views``: per-scene numbers of valid input views (``gta_attention``); inference only.
+    ``key_views``: per-scene numbers of valid input views (``gta_attention``); inference only unless ``key_views_backward=True``, with which
+    ``query_views`` masks padded query rows in the backward (``gta_attention``).
     """
     if f_dims is None or reps is None:
         raise TypeError("f_dims and reps are required")
@@ -856,7 +942,9 @@ def multihead_geometric_transform_attention(q, k, v, attn_fn=None, f_dims=None, 
     out = gta_attention(q, k, v, f_dims, packed, so3_degree=_so3_degree(f_dims, packed, reps),
                         trans_coeff=trans_coeff, tau=tau, scale=scale, v_transform=v_transform, euclid=euclid,
                         use_dma=kwargs.get("use_dma", True), kv_mode=kwargs.get("kv_mode", "auto"),
-                        precise=kwargs.get("precise"), **({"key_views": key_views} if key_views is not None else {}))
+                        precise=kwargs.get("precise"), **({"key_views": key_views} if key_views is not None else {}),
+                        **({"key_views_backward": True} if key_views_backward else {}),
+                        **({"query_views": query_views} if query_views is not None else {}))
     return out, None
 
 

@@ -48,6 +48,7 @@ ABI_SYMBOLS = (
     "gta_rep_grad_workspace_bytes", "gta_rep_grad_sums",
     "gta_attn_fwd_staged", "gta_attn_fwd_staged_supported", "gta_attn_fwd_staged_workspace_bytes",
     "gta_attn_fwd_varlen", "gta_attn_fwd_varlen_supported", "gta_attn_fwd_staged_varlen", "gta_attn_fwd_staged_varlen_supported",
+    "gta_attn_bwd_varlen", "gta_attn_bwd_varlen_supported",
 )
 
 
@@ -135,6 +136,10 @@ def lib():
         L.gta_attn_fwd_varlen_supported.argtypes = [ctypes.POINTER(GtaAttnDesc)]
         L.gta_attn_fwd_staged_varlen.argtypes = [ctypes.POINTER(GtaAttnDesc)] + [c_void_p] * 15 + [c_int64, c_void_p]
         L.gta_attn_fwd_staged_varlen_supported.argtypes = [ctypes.POINTER(GtaAttnDesc)]
+        # gta_attn_bwd with key_lens, q_lens ([B] int32, device; q_lens may be NULL) in front of kv_images
+        L.gta_attn_bwd_varlen.argtypes = ([ctypes.POINTER(GtaAttnDesc)] + [c_void_p] * 18
+                                          + [ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_int64, c_void_p])
+        L.gta_attn_bwd_varlen_supported.argtypes = [ctypes.POINTER(GtaAttnDesc)]
         _lib = L
     return _lib
 
@@ -389,6 +394,27 @@ def attn_bwd(desc: GtaAttnDesc, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, c
                              _ptr(vrep_q), _ptr(vrep_k), _ptr(cs_q), _ptr(cs_k), _ptr(trans_coeff), _ptr(tau),
                              _ptr(kv_images), _ptr(dq), _ptr(dk), _ptr(dv), gs, ds, _ptr(dtrans_coeff), _ptr(dtau),
                              _ptr(workspace), workspace.numel(), _stream()), "gta_attn_bwd")
+
+
+def attn_bwd_varlen_supported(desc: GtaAttnDesc) -> int:
+    """0 when gta_attn_bwd_varlen (the backward with per-scene prefixes) serves desc, else a GTA_E_* code; needs no GPU"""
+    return lib().gta_attn_bwd_varlen_supported(ctypes.byref(desc))
+
+
+def attn_bwd_varlen(desc: GtaAttnDesc, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, key_lens, q_lens, kv_images,
+                    dq, dk, dv, dtrans_coeff, workspace, dtau=None):
+    """``attn_bwd`` with scene b's keys cut to key_lens[b] tokens and (q_lens, or None) its query rows to q_lens[b]: [B] int32 on the device.
+    kv_images: the workspace of ``attn_fwd_varlen`` under the same key_lens, or None."""
+    _require_cuda(q, k, v, out, dout, dq, dk, dv, workspace, key_lens, q_lens)
+    _check_key_lens(key_lens, desc.B, workspace.device)
+    if q_lens is not None:
+        _check_key_lens(q_lens, desc.B, workspace.device)
+    gs = (c_int64 * 9)(*(list(dq.stride()[:3]) + list(dk.stride()[:3]) + list(dv.stride()[:3])))
+    ds = (c_int64 * 3)(*dout.stride()[:3])
+    check(lib().gta_attn_bwd_varlen(ctypes.byref(desc), _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(dout), _ptr(lse),
+                                    _ptr(vrep_q), _ptr(vrep_k), _ptr(cs_q), _ptr(cs_k), _ptr(trans_coeff), _ptr(tau),
+                                    _ptr(key_lens), _ptr(q_lens), _ptr(kv_images), _ptr(dq), _ptr(dk), _ptr(dv), gs, ds,
+                                    _ptr(dtrans_coeff), _ptr(dtau), _ptr(workspace), workspace.numel(), _stream()), "gta_attn_bwd_varlen")
 
 
 def attn_bwd_plain_f32(desc: GtaAttnDesc, q, k, v, out, dout, lse, tau, dq, dk, dv):

@@ -171,16 +171,24 @@ class TransformingSRT(nn.Module):
             x, rays = x.flatten(1, 2), rays.flatten(1, 2)
         return self.decoder(z, x, rays, extras)
 
-    def forward(self, input_images, input_camera_pos, input_rays, target_camera_pos, target_rays, extras=None, input_views=None):
+    def forward(self, input_images, input_camera_pos, input_rays, target_camera_pos, target_rays, extras=None, input_views=None,
+                input_views_backward=False):
         """``input_views``: per-scene numbers of valid input views (a host sequence of length B, each in 1..N) for batches that mix
         view counts: scene b's first ``input_views[b]`` views are its input, the rest of its [N, ...] slots is padding that no valid
         token ever attends to -- in the encoder's self-attention and in the decoder's cross-attention (``gta_attention``'s
-        ``key_views``).  Inference only: call under ``torch.no_grad()``."""
+        ``key_views``).  Inference only (call under ``torch.no_grad()``) unless ``input_views_backward=True``: every layer then runs the
+        differentiable route (``key_views_backward``; fused layouts, tables without grad), and the encoder's self-attention layers also get
+        ``query_views = input_views``, so the tokens of padded views send no gradient into the valid ones."""
         extras = {} if extras is None else extras
         if input_views is not None:
             extras = dict(extras)                      # the caller's dict never carries these counts into a later call (as render_image)
             extras["key_views"] = input_views
+            if input_views_backward:
+                extras["key_views_backward"] = True
+                extras["query_views"] = input_views    # (the encoder's layers: Tq = Tk, the same views on both sides)
         z, extras = self.encoder(input_images, input_camera_pos, input_rays, extras)
+        if input_views is not None and input_views_backward:
+            extras = {k_: v_ for k_, v_ in extras.items() if k_ != "query_views"}      # the decoder's queries are the target rays: all live
         return self.decode(z, target_camera_pos, target_rays, extras=extras)
 
 

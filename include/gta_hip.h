@@ -188,6 +188,32 @@ int gta_attn_bwd(const GtaAttnDesc* desc,
                  float* dtrans_coeff, float* dtau,
                  void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Backward with per-scene prefixes (gta_attention's key_views_backward): the backward of gta_attn_fwd_varlen.
+ *   key_lens: [B] int32 on the device, valid key TOKENS per scene, as in the forward (clamped to 1..Tk).  dk / dv rows at or past the prefix
+ *       are written as zeros; k, v, cs_k rows there are never loaded; the padded key tiles are neither built nor walked.
+ *   q_lens:   [B] int32 on the device or NULL (every query row is live), clamped to 1..Tq.  Query rows at or past the prefix take no part:
+ *       their q, out, dout, lse and cs_q are never loaded, they add nothing to dk, dv, dtrans_coeff or dtau, and their dq rows are zeros
+ *       (self-attention over padded views, where those rows hold anything).
+ *   kv_images: the workspace of a gta_attn_fwd_varlen call under the same key_lens, or NULL -> rebuilt here by the VARLEN pre-pass.
+ *   Kernels: VARLEN instances of the compiled pre-pass / dQ / dK,dV kernels as three launches, for bf16 and fp32 inputs at every head size; the
+ *       generated 64-row streams are never selected (GTA_FLAG_BWD_KEYS64 is ignored).  dq, dk, dv of scene b are bit for bit those of
+ *       gta_attn_bwd (GTA_FLAG_BWD_KEYS32) on that scene alone with its keys (and, with q_lens, its queries) cut to the prefixes.
+ *   gta_attn_bwd_varlen_supported: what gta_attn_fwd_varlen_supported answers -- GTA_E_UNSUPPORTED with the reason in gta_strerror() for
+ *       GTA_FLAG_FP32_PRODUCTS, GTA_FLAG_FUSED_KV, GTA_FLAG_PRETRANSFORMED and for layouts without a fused kernel.
+ *   workspace: >= gta_attn_bwd_workspace_bytes(desc).  Every other argument, check and error code: as in gta_attn_bwd.  No gradient for the
+ *       reps / poses (gta_rep_grad_sums has no key mask). */
+int gta_attn_bwd_varlen_supported(const GtaAttnDesc* desc);
+int gta_attn_bwd_varlen(const GtaAttnDesc* desc,
+                        const void* q, const void* k, const void* v, const void* out, const void* dout,
+                        const float* lse,
+                        const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
+                        const float* trans_coeff, const float* tau,
+                        const int32_t* key_lens, const int32_t* q_lens,
+                        const void* kv_images,
+                        void* dq, void* dk, void* dv, const int64_t* dqkv_stride, const int64_t* dout_stride,
+                        float* dtrans_coeff, float* dtau,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+
 /* -------------------------------------------------------------------------------------------
  * Generic path for the reference's ablations (any f_dims layout): t2 slab (gta.py:221-238,272-274),
  * euclid similarity (GTA_FLAG_EUCLID; gta.py:146-156,251-253 + EuclidAttnFn layers.py:213-224),

@@ -93,12 +93,28 @@ def audit_others():
         if int(dhp) <= 96 and int(esz) == 2 and vgpr > 96:
             problems.append(f"perf: {row['kernel']}: {vgpr} VGPRs (five 4-wave workgroups per CU need <= 96; six would need <= 80)")
     text = _asm("gta_bwd.hip", ("-fno-slp-vectorize",))
+    bwd_scratch = {}
     for kern in ("gta_bwd_prep_kernel", "gta_bwd_dq_kernel", "gta_bwd_dkv_kernel"):
         for name, (dhp, esz), body, vgpr in _kernels(text, kern + r"ILi(\d+)ELi(\d+)E"):
             row = {"kernel": f"{kern}<{dhp},{esz}>", "vgpr": vgpr, "scratch": body.count("scratch_")}
             report.append(row)
+            if kern == "gta_bwd_prep_kernel" and "ELb0ELb1E" in name:      # its VARLEN instances <dhp, esz, false, true, q_lens>: below
+                report.pop()
+                continue
+            if "ELb1E" not in name:                     # (not the prep kernel's X3 instances, which share <dhp, 4>)
+                bwd_scratch[(kern, dhp, esz)] = row["scratch"]
             if row["scratch"]:
                 problems.append(f"perf: {row['kernel']}: {row['scratch']} scratch accesses")
+    # the VARLEN instances (gta_attn_bwd_varlen) are held to the rule of the forward's: never more scratch accesses than the twin without
+    # the prefixes (a comparison inside one compiler run: a hard criterion)
+    for kern in ("gta_bwd_prep", "gta_bwd_dq", "gta_bwd_dkv"):
+        pattern = r"_kernelILi(\d+)ELi(\d+)ELb0ELb1E" if kern == "gta_bwd_prep" else r"_varlen_kernelILi(\d+)ELi(\d+)E"
+        for name, (dhp, esz), body, vgpr in _kernels(text, kern + pattern):
+            row = {"kernel": f"{kern}_varlen_kernel<{dhp},{esz}>", "vgpr": vgpr, "scratch": body.count("scratch_")}
+            report.append(row)
+            twin = bwd_scratch.get((kern + "_kernel", dhp, esz))
+            if twin is None or row["scratch"] > twin:
+                problems.append(f"{row['kernel']} has {row['scratch']} scratch accesses, its twin without VARLEN {twin}")
     text = _asm("gta_wgrad.hip")
     for name, _, body, vgpr in _kernels(text, r"wgrad_kernelILb(\d)E"):
         lines = body.split("\n")
