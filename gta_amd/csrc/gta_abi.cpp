@@ -34,13 +34,38 @@ int fail(int code, const char* why) { g_detail = why; return code; }
 
 int padded_dh(int dh) { return dh <= 32 ? 32 : dh <= 64 ? 64 : dh <= 96 ? 96 : dh <= 128 ? 128 : -1; }
 
+int esz_of(const GtaAttnDesc* d) { return d->dtype == GTA_DTYPE_BF16 ? 2 : 4; }
+
+// what a dispatcher returned: GTA_E_LAUNCH carries HIP's text, anything else `what`
+int launch_status(int rc, const char* what) {
+    return rc ? fail(rc, rc == GTA_E_LAUNCH ? hipGetErrorString(hipGetLastError()) : what) : GTA_OK;
+}
+
+int check_header(const GtaAttnDesc* d) {
+    if (!d) return fail(GTA_E_BADARG, "null descriptor");
+    if (d->abi_version != GTA_ABI_VERSION) return fail(GTA_E_BADARG, "abi_version mismatch");
+    return GTA_OK;
+}
+
+// the (batch, head, token) strides of q, k, v, out into an argument block (GtaFwdParams, GtaGenParams, GtaBwdParams)
+template <class P> void copy_strides(P& p, const GtaAttnDesc* d) {
+    p.q_sb = d->q_stride[0]; p.q_sh = d->q_stride[1]; p.q_st = d->q_stride[2];
+    p.k_sb = d->k_stride[0]; p.k_sh = d->k_stride[1]; p.k_st = d->k_stride[2];
+    p.v_sb = d->v_stride[0]; p.v_sh = d->v_stride[1]; p.v_st = d->v_stride[2];
+    p.o_sb = d->o_stride[0]; p.o_sh = d->o_stride[1]; p.o_st = d->o_stride[2];
+}
+
+// the two slab rules every entry words alike: sizes >= 0 that sum to dh (the group-size rules differ between the entries and stay with them)
+int check_slabs(const GtaAttnDesc* d) {
+    if (d->d_triv < 0 || d->d_se3 < 0 || d->d_so3 < 0 || d->d_so2 < 0 || d->d_t2 < 0) return fail(GTA_E_LAYOUT, "negative slab size");
+    if (d->d_triv + d->d_se3 + d->d_so3 + d->d_so2 + d->d_t2 != d->dh) return fail(GTA_E_LAYOUT, "f_dims do not sum to dh");
+    return GTA_OK;
+}
+
 // Build the per-chunk descriptors for the fused kernels, or say why this layout needs the
 // generic (unfused) path.
 int build_ctab(const GtaAttnDesc* d, uint32_t* ctab) {
-    if (d->d_triv < 0 || d->d_se3 < 0 || d->d_so3 < 0 || d->d_so2 < 0 || d->d_t2 < 0)
-        return fail(GTA_E_LAYOUT, "negative slab size");
-    if (d->d_triv + d->d_se3 + d->d_so3 + d->d_so2 + d->d_t2 != d->dh)
-        return fail(GTA_E_LAYOUT, "f_dims do not sum to dh");
+    if (int rc = check_slabs(d)) return rc;
     if (d->flags & GTA_FLAG_EUCLID) {
         if (d->d_se3 % 3) return fail(GTA_E_LAYOUT, "under euclid_sim the se3 slab holds 3-vectors (gta.py:147)");
         return fail(GTA_E_UNSUPPORTED, "euclid similarity has no fused kernel (gta_rep_apply + gta_attn_fwd_plain)");
@@ -55,7 +80,6 @@ int build_ctab(const GtaAttnDesc* d, uint32_t* ctab) {
     }
     if (d->dh % 8 || d->dh > 128) return fail(GTA_E_UNSUPPORTED, "fused kernel needs dh % 8 == 0 and dh <= 128");
     if (d->d_t2 > 0) return fail(GTA_E_UNSUPPORTED, "t2 slab has no fused kernel (ablation; use the unfused path)");
-    if (d->flags & GTA_FLAG_EUCLID) return fail(GTA_E_UNSUPPORTED, "euclid similarity has no fused kernel");
     if (d->d_so3 > 0 && (d->so3_degree != 2 || d->d_so3 % 8))
         return fail(GTA_E_UNSUPPORTED, "fused so3 needs degree 2 ([3|5] groups of 8 channels)");
     const int s_se3 = d->d_triv, s_so3 = s_se3 + d->d_se3, s_so2 = s_so3 + d->d_so3;
@@ -80,15 +104,14 @@ int build_ctab(const GtaAttnDesc* d, uint32_t* ctab) {
 }
 
 int check_common(const GtaAttnDesc* d) {
-    if (!d) return fail(GTA_E_BADARG, "null descriptor");
-    if (d->abi_version != GTA_ABI_VERSION) return fail(GTA_E_BADARG, "abi_version mismatch");
+    if (int rc = check_header(d)) return rc;
     if (d->dtype != GTA_DTYPE_F32 && d->dtype != GTA_DTYPE_BF16) return fail(GTA_E_BADARG, "bad dtype");
     if (d->B <= 0 || d->H <= 0 || d->Tq <= 0 || d->Tk <= 0 || d->dh <= 0) return fail(GTA_E_BADARG, "non-positive size");
     if (d->Nq <= 0 || d->Nk <= 0 || d->Tq % d->Nq || d->Tk % d->Nk)
         return fail(GTA_E_BADARG, "tokens must split evenly into views (gta.py:160-162)");
     if (d->Nq > GTA_MAX_VIEWS || d->Nk > GTA_MAX_VIEWS) return fail(GTA_E_UNSUPPORTED, "more than GTA_MAX_VIEWS views per side");
     if (d->Tq >= (1 << 22) || d->Tk >= (1 << 22)) return fail(GTA_E_UNSUPPORTED, "more than 2^22 tokens per side");
-    const int esz = d->dtype == GTA_DTYPE_BF16 ? 2 : 4;
+    const int esz = esz_of(d);
     const int64_t* st[4] = {d->q_stride, d->k_stride, d->v_stride, d->o_stride};
     for (int i = 0; i < 4; ++i)
         for (int j = 0; j < 3; ++j)
@@ -107,10 +130,7 @@ int fwd_params(GtaFwdParams& p, const GtaAttnDesc* d, const void* q, const void*
     p.vrep_q = need_view ? vrep_q : nullptr; p.vrep_k = need_view ? vrep_k : nullptr;
     p.cs_q = need_cs ? cs_q : nullptr; p.cs_k = need_cs ? cs_k : nullptr;
     p.trans_coeff = trans_coeff; p.tau = tau;
-    p.q_sb = d->q_stride[0]; p.q_sh = d->q_stride[1]; p.q_st = d->q_stride[2];
-    p.k_sb = d->k_stride[0]; p.k_sh = d->k_stride[1]; p.k_st = d->k_stride[2];
-    p.v_sb = d->v_stride[0]; p.v_sh = d->v_stride[1]; p.v_st = d->v_stride[2];
-    p.o_sb = d->o_stride[0]; p.o_sh = d->o_stride[1]; p.o_st = d->o_stride[2];
+    copy_strides(p, d);
     p.B = d->B; p.H = d->H; p.Tq = d->Tq; p.Tk = d->Tk; p.Nq = d->Nq; p.Nk = d->Nk;
     p.Pq = d->Tq / d->Nq; p.Pk = d->Tk / d->Nk;
     p.invPq = 1.0f / (float)p.Pq; p.invPk = 1.0f / (float)p.Pk;
@@ -132,7 +152,7 @@ GtaFwdSel full_call_selection(const GtaAttnDesc* d) {
     float* const x = (float*)256;
     GtaFwdParams p;
     fwd_params(p, d, x, x, x, x, x, x, x, x, x, x, x, x);
-    return gta_fwd_select(p, padded_dh(d->dh), d->dtype == GTA_DTYPE_BF16 ? 2 : 4);
+    return gta_fwd_select(p, padded_dh(d->dh), esz_of(d));
 }
 
 }  // namespace
@@ -165,11 +185,9 @@ extern "C" const char* gta_strerror(int code) {
 }
 
 extern "C" int gta_attn_fwd_supported(const GtaAttnDesc* desc) {
-    if (!desc) return fail(GTA_E_BADARG, "null descriptor");
-    if (desc->abi_version != GTA_ABI_VERSION) return fail(GTA_E_BADARG, "abi_version mismatch");
+    if (int rc = check_header(desc)) return rc;
     uint32_t ctab[16];
-    int rc = build_ctab(desc, ctab);      // layout first: "no fused kernel" must not be masked by a stride complaint
-    if (rc) return rc;
+    if (int rc = build_ctab(desc, ctab)) return rc;      // layout first: "no fused kernel" must not be masked by a stride complaint
     return check_common(desc);
 }
 
@@ -177,15 +195,14 @@ extern "C" int64_t gta_attn_fwd_workspace_bytes(const GtaAttnDesc* desc) {
     if (gta_attn_fwd_supported(desc)) return 0;
     const bool x3 = (desc->flags & GTA_FLAG_FP32_PRODUCTS) != 0;
     if (x3 && full_call_selection(desc).kind == GTA_FWD_SINGLE) return 0;       // (that mode runs the single-kernel plan here)
-    return gta_fwd2_workspace_bytes(desc->B, desc->H, desc->Tk, padded_dh(desc->dh), desc->Nq, desc->dtype == GTA_DTYPE_BF16 ? 2 : 4, x3);
+    return gta_fwd2_workspace_bytes(desc->B, desc->H, desc->Tk, padded_dh(desc->dh), desc->Nq, esz_of(desc), x3);
 }
 
 extern "C" int gta_attn_fwd_launch_info(const GtaAttnDesc* desc, int32_t* lds_bytes, int32_t* n_workgroups,
                                         int32_t* threads_per_wg) {
     int rc = gta_attn_fwd_supported(desc);
     if (rc) return rc;
-    const int esz = desc->dtype == GTA_DTYPE_BF16 ? 2 : 4;
-    if (lds_bytes) *lds_bytes = gta_fwd_lds_bytes(padded_dh(desc->dh), esz);
+    if (lds_bytes) *lds_bytes = gta_fwd_lds_bytes(padded_dh(desc->dh), esz_of(desc));
     if (n_workgroups) *n_workgroups = desc->B * desc->H * ((desc->Tq + 127) / 128);
     if (threads_per_wg) *threads_per_wg = 256;
     return GTA_OK;
@@ -200,56 +217,69 @@ extern "C" const char* gta_debug_attention_kernel(const GtaAttnDesc* d, int32_t*
     return s.name;
 }
 
-extern "C" int gta_attn_fwd(const GtaAttnDesc* d, const void* q, const void* k, const void* v,
-                            const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
-                            const float* trans_coeff, const float* tau, void* out, float* lse,
-                            void* workspace, int64_t workspace_bytes, void* stream) {
-    int rc = check_common(d);
-    if (rc) return rc;
-    if (!k || !v || ((!q || !out) && !(d->flags & GTA_FLAG_PREP_ONLY))) return fail(GTA_E_BADARG, "null q/k/v/out");
-    GtaFwdParams p;
-    rc = fwd_params(p, d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, out, lse, workspace);
-    if (rc) return rc;
-    const bool pre = (d->flags & GTA_FLAG_PRETRANSFORMED) != 0;
-    if ((d->d_se3 > 0 || d->d_so3 > 0) && (!vrep_q || (!pre && !vrep_k))) return fail(GTA_E_BADARG, "se3/so3 slabs need vrep_q and vrep_k");
-    if (d->d_so2 > 0 && (!cs_q || (!pre && !cs_k))) return fail(GTA_E_BADARG, "so2 slab needs cs_q and cs_k");
-    const int dhp = padded_dh(d->dh), esz = d->dtype == GTA_DTYPE_BF16 ? 2 : 4;
-#ifdef GTA_ABLATE
-    { const char* e = getenv("GTA_DBG"); p.dbg = e ? (uint32_t)atoi(e) : 0u; }
-#endif
-    const GtaFwdSel s = gta_fwd_select(p, dhp, esz);
-    const long n_wg = (long)d->B * d->H * p.n_qtiles;
-    if (t_prof && !(d->flags & GTA_FLAG_PREP_ONLY)) {      // (start / end stamps of every work item: gta_debug_profile_next_attention_kernel)
-        if ((int64_t)d->B * d->H * ((d->Tq + s.rows - 1) / s.rows) <= t_prof_items) p.prof = t_prof;
-        t_prof = nullptr;
-        t_prof_items = 0;
-    }
-    if (n_wg > 0x7fffffffL) return fail(GTA_E_UNSUPPORTED, "grid too large");
-    if ((d->flags & GTA_FLAG_FP32_PRODUCTS) && d->dtype != GTA_DTYPE_F32)
-        return fail(GTA_E_BADARG, "GTA_FLAG_FP32_PRODUCTS is for fp32 inputs (bf16 inputs ask for bf16 arithmetic)");
-    if (s.kind != GTA_FWD_SINGLE) {
-        if (workspace_bytes < gta_fwd2_workspace_bytes(d->B, d->H, d->Tk, dhp, d->Nq, esz, (d->flags & GTA_FLAG_FP32_PRODUCTS) != 0))
-            return fail(GTA_E_BADARG, "workspace smaller than gta_attn_fwd_workspace_bytes()");
-        if (d->H > 65535 || d->B > 65535) return fail(GTA_E_UNSUPPORTED, "B or H above 65535");
-        rc = gta_fwd2_dispatch(p, s, dhp, esz, !(d->flags & GTA_FLAG_KV_READY), !(d->flags & GTA_FLAG_PREP_ONLY), (hipStream_t)stream);
-        if (rc) return fail(rc, rc == GTA_E_LAUNCH ? hipGetErrorString(hipGetLastError()) : "no kernel instance");
-        return GTA_OK;
-    }
-    rc = gta_fwd_dispatch(p, dhp, esz, !(d->flags & GTA_FLAG_NO_DMA), (int)n_wg, (hipStream_t)stream);
-    if (rc) return fail(rc, rc == GTA_E_LAUNCH ? hipGetErrorString(hipGetLastError()) : "no kernel instance");
-    return GTA_OK;
-}
-
-// Per-scene key prefixes on the two-stage plan: the VARLEN instances of the pre-pass and of gta_fwd2_kernel (GtaFwdSel::varlen selects them in
-// gta_fwd2_dispatch), whatever attention kernel gta_fwd_select would give the shape.
 namespace {
+// what per-scene key prefixes (gta_attn_fwd_varlen, gta_attn_bwd_varlen) cannot be combined with
 int varlen_flags(const GtaAttnDesc* d) {
     if (d->flags & GTA_FLAG_FUSED_KV) return fail(GTA_E_UNSUPPORTED, "per-scene key prefixes run the two-stage plan: no GTA_FLAG_FUSED_KV");
     if (d->flags & GTA_FLAG_FP32_PRODUCTS) return fail(GTA_E_UNSUPPORTED, "per-scene key prefixes have no GTA_FLAG_FP32_PRODUCTS instances");
     if (d->flags & GTA_FLAG_PRETRANSFORMED) return fail(GTA_E_UNSUPPORTED, "per-scene key prefixes apply rho_k in the pre-pass: no GTA_FLAG_PRETRANSFORMED");
     return GTA_OK;
 }
+
+// both fused forward entries.  varlen (gta_attn_fwd_varlen) is the explicit selector of per-scene key prefixes -- never "key_lens is non-null":
+// always the two-stage plan, with the VARLEN instances of the pre-pass and of gta_fwd2_kernel (GtaFwdSel::varlen selects them in
+// gta_fwd2_dispatch), whatever attention kernel gta_fwd_select would give the shape.
+int fwd_call(const GtaAttnDesc* d, const void* q, const void* k, const void* v,
+             const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
+             const float* trans_coeff, const float* tau, bool varlen, const int32_t* key_lens, void* out, float* lse,
+             void* workspace, int64_t workspace_bytes, void* stream) {
+    int rc = check_common(d);
+    if (rc) return rc;
+    if (!k || !v || ((!q || !out) && !(d->flags & GTA_FLAG_PREP_ONLY))) return fail(GTA_E_BADARG, "null q/k/v/out");
+    if (varlen) {
+        if (!key_lens) return fail(GTA_E_BADARG, "null key_lens");
+        if (!workspace) return fail(GTA_E_BADARG, "per-scene key prefixes need the workspace of gta_attn_fwd_workspace_bytes()");
+    }
+    GtaFwdParams p;
+    rc = fwd_params(p, d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, out, lse, workspace);
+    if (rc) return rc;
+    if (varlen && (rc = varlen_flags(d))) return rc;
+    const bool pre = (d->flags & GTA_FLAG_PRETRANSFORMED) != 0;
+    if ((d->d_se3 > 0 || d->d_so3 > 0) && (!vrep_q || (!pre && !vrep_k))) return fail(GTA_E_BADARG, "se3/so3 slabs need vrep_q and vrep_k");
+    if (d->d_so2 > 0 && (!cs_q || (!pre && !cs_k))) return fail(GTA_E_BADARG, "so2 slab needs cs_q and cs_k");
+    const int dhp = padded_dh(d->dh), esz = esz_of(d);
+#ifdef GTA_ABLATE
+    if (!varlen) { const char* e = getenv("GTA_DBG"); p.dbg = e ? (uint32_t)atoi(e) : 0u; }
+#endif
+    GtaFwdSel s = gta_fwd_select(p, dhp, esz);
+    if (varlen) {       // (the selection gave the layout of the chunk table; the kernel is fixed)
+        s.kind = GTA_FWD_FWD2; s.coal = false; s.qtiles = false; s.rows = 128; s.name = "gta_fwd2_kernel"; s.varlen = true;
+        p.key_lens = key_lens;
+    } else if (t_prof && !(d->flags & GTA_FLAG_PREP_ONLY)) {      // (start / end stamps of every work item: gta_debug_profile_next_attention_kernel)
+        if ((int64_t)d->B * d->H * ((d->Tq + s.rows - 1) / s.rows) <= t_prof_items) p.prof = t_prof;
+        t_prof = nullptr;
+        t_prof_items = 0;
+    }
+    const long n_wg = (long)d->B * d->H * p.n_qtiles;
+    if (n_wg > 0x7fffffffL) return fail(GTA_E_UNSUPPORTED, "grid too large");
+    if ((d->flags & GTA_FLAG_FP32_PRODUCTS) && d->dtype != GTA_DTYPE_F32)
+        return fail(GTA_E_BADARG, "GTA_FLAG_FP32_PRODUCTS is for fp32 inputs (bf16 inputs ask for bf16 arithmetic)");
+    if (s.kind == GTA_FWD_SINGLE)
+        return launch_status(gta_fwd_dispatch(p, dhp, esz, !(d->flags & GTA_FLAG_NO_DMA), (int)n_wg, (hipStream_t)stream), "no kernel instance");
+    if (workspace_bytes < gta_fwd2_workspace_bytes(d->B, d->H, d->Tk, dhp, d->Nq, esz, (d->flags & GTA_FLAG_FP32_PRODUCTS) != 0))
+        return fail(GTA_E_BADARG, "workspace smaller than gta_attn_fwd_workspace_bytes()");
+    if (d->H > 65535 || d->B > 65535) return fail(GTA_E_UNSUPPORTED, "B or H above 65535");
+    return launch_status(gta_fwd2_dispatch(p, s, dhp, esz, !(d->flags & GTA_FLAG_KV_READY), !(d->flags & GTA_FLAG_PREP_ONLY), (hipStream_t)stream),
+                         "no kernel instance");
+}
 }  // namespace
+
+extern "C" int gta_attn_fwd(const GtaAttnDesc* d, const void* q, const void* k, const void* v,
+                            const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
+                            const float* trans_coeff, const float* tau, void* out, float* lse,
+                            void* workspace, int64_t workspace_bytes, void* stream) {
+    return fwd_call(d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, false, nullptr, out, lse, workspace, workspace_bytes, stream);
+}
 
 extern "C" int gta_attn_fwd_varlen_supported(const GtaAttnDesc* desc) {
     if (int rc = gta_attn_fwd_supported(desc)) return rc;
@@ -260,28 +290,7 @@ extern "C" int gta_attn_fwd_varlen(const GtaAttnDesc* d, const void* q, const vo
                                    const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
                                    const float* trans_coeff, const float* tau, const int32_t* key_lens, void* out, float* lse,
                                    void* workspace, int64_t workspace_bytes, void* stream) {
-    int rc = check_common(d);
-    if (rc) return rc;
-    if (!k || !v || ((!q || !out) && !(d->flags & GTA_FLAG_PREP_ONLY))) return fail(GTA_E_BADARG, "null q/k/v/out");
-    if (!key_lens) return fail(GTA_E_BADARG, "null key_lens");
-    if (!workspace) return fail(GTA_E_BADARG, "per-scene key prefixes need the workspace of gta_attn_fwd_workspace_bytes()");
-    GtaFwdParams p;
-    rc = fwd_params(p, d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, out, lse, workspace);
-    if (rc) return rc;
-    if ((rc = varlen_flags(d))) return rc;
-    if ((d->d_se3 > 0 || d->d_so3 > 0) && (!vrep_q || !vrep_k)) return fail(GTA_E_BADARG, "se3/so3 slabs need vrep_q and vrep_k");
-    if (d->d_so2 > 0 && (!cs_q || !cs_k)) return fail(GTA_E_BADARG, "so2 slab needs cs_q and cs_k");
-    const int dhp = padded_dh(d->dh), esz = d->dtype == GTA_DTYPE_BF16 ? 2 : 4;
-    GtaFwdSel s = gta_fwd_select(p, dhp, esz);          // (for the layout of the chunk table; the kernel is fixed)
-    s.kind = GTA_FWD_FWD2; s.coal = false; s.qtiles = false; s.rows = 128; s.name = "gta_fwd2_kernel"; s.varlen = true;
-    p.key_lens = key_lens;
-    if ((long)d->B * d->H * p.n_qtiles > 0x7fffffffL) return fail(GTA_E_UNSUPPORTED, "grid too large");
-    if (workspace_bytes < gta_fwd2_workspace_bytes(d->B, d->H, d->Tk, dhp, d->Nq, esz, false))
-        return fail(GTA_E_BADARG, "workspace smaller than gta_attn_fwd_workspace_bytes()");
-    if (d->H > 65535 || d->B > 65535) return fail(GTA_E_UNSUPPORTED, "B or H above 65535");
-    rc = gta_fwd2_dispatch(p, s, dhp, esz, !(d->flags & GTA_FLAG_KV_READY), !(d->flags & GTA_FLAG_PREP_ONLY), (hipStream_t)stream);
-    if (rc) return fail(rc, rc == GTA_E_LAUNCH ? hipGetErrorString(hipGetLastError()) : "no kernel instance");
-    return GTA_OK;
+    return fwd_call(d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, true, key_lens, out, lse, workspace, workspace_bytes, stream);
 }
 
 
@@ -291,8 +300,7 @@ extern "C" int gta_attn_fwd_varlen(const GtaAttnDesc* d, const void* q, const vo
 namespace {
 // the layout rules of the generic path (gta_rep_apply), then what the staged kernels add
 int staged_layout(const GtaAttnDesc* d) {
-    if (d->d_triv < 0 || d->d_se3 < 0 || d->d_so3 < 0 || d->d_so2 < 0 || d->d_t2 < 0) return fail(GTA_E_LAYOUT, "negative slab size");
-    if (d->d_triv + d->d_se3 + d->d_so3 + d->d_so2 + d->d_t2 != d->dh) return fail(GTA_E_LAYOUT, "f_dims do not sum to dh");
+    if (int rc = check_slabs(d)) return rc;
     const bool euclid = (d->flags & GTA_FLAG_EUCLID) != 0;
     if (euclid && d->d_se3 % 3) return fail(GTA_E_LAYOUT, "under euclid_sim the se3 slab holds 3-vectors (gta.py:147)");
     if (!euclid && d->d_se3 % 4) return fail(GTA_E_LAYOUT, "se3 slab must be a multiple of 4 channels (gta.py:161)");
@@ -309,8 +317,7 @@ int staged_layout(const GtaAttnDesc* d) {
 }  // namespace
 
 extern "C" int gta_attn_fwd_staged_supported(const GtaAttnDesc* desc) {
-    if (!desc) return fail(GTA_E_BADARG, "null descriptor");
-    if (desc->abi_version != GTA_ABI_VERSION) return fail(GTA_E_BADARG, "abi_version mismatch");
+    if (int rc = check_header(desc)) return rc;
     if (int rc = staged_layout(desc)) return rc;      // layout first, as gta_attn_fwd_supported
     return check_common(desc);
 }
@@ -344,15 +351,12 @@ int staged_call(const GtaAttnDesc* d, const void* q, const void* k, const void* 
     if (d->flags & GTA_FLAG_EUCLID) p.kbias = (float*)((char*)workspace + ((gta_gen_image_bytes(d->B, d->H, d->Tk, dhp) + 255) & ~255L));
     p.vrep_q = vrep_q; p.vrep_k = vrep_k; p.cs_q = cs_q; p.cs_k = cs_k; p.coord_q = coord_q; p.coord_k = coord_k;
     p.trans_coeff = trans_coeff; p.tau = tau;
-    p.q_sb = d->q_stride[0]; p.q_sh = d->q_stride[1]; p.q_st = d->q_stride[2];
-    p.k_sb = d->k_stride[0]; p.k_sh = d->k_stride[1]; p.k_st = d->k_stride[2];
-    p.v_sb = d->v_stride[0]; p.v_sh = d->v_stride[1]; p.v_st = d->v_stride[2];
-    p.o_sb = d->o_stride[0]; p.o_sh = d->o_stride[1]; p.o_st = d->o_stride[2];
+    copy_strides(p, d);
     p.B = d->B; p.H = d->H; p.Tq = d->Tq; p.Tk = d->Tk; p.Nq = d->Nq; p.Nk = d->Nk;
     p.dh = d->dh; p.d_triv = d->d_triv; p.d_se3 = d->d_se3; p.d_so3 = d->d_so3; p.d_so2 = d->d_so2; p.d_t2 = d->d_t2; p.L = d->so3_degree;
     p.euclid = (d->flags & GTA_FLAG_EUCLID) ? 1 : 0;
     p.xv = (d->flags & GTA_FLAG_V_TRANSFORM) ? 1 : 0;
-    p.esz = d->dtype == GTA_DTYPE_BF16 ? 2 : 4;
+    p.esz = esz_of(d);
     p.n_qtiles = (d->Tq + 127) / 128;
     p.n_tiles = (d->Tk + 63) / 64;
     const long n_items = (long)d->B * d->H * p.n_qtiles;
@@ -432,7 +436,7 @@ int bwd_call(const GtaAttnDesc* d, const void* q, const void* k, const void* v, 
     if (!q || !k || !v || !out || !dout || !lse || !dq || !dk || !dv || !dqkv_stride || !dout_stride || !workspace)
         return fail(GTA_E_BADARG, "null argument");
     if (d->flags & GTA_FLAG_PRETRANSFORMED) return fail(GTA_E_UNSUPPORTED, "backward of the pretransformed mode");
-    const int dhp = padded_dh(d->dh), esz = d->dtype == GTA_DTYPE_BF16 ? 2 : 4;
+    const int dhp = padded_dh(d->dh), esz = esz_of(d);
     if ((d->flags & GTA_FLAG_FP32_PRODUCTS) && !gta_x3_takes(dhp, esz))
         return fail(GTA_E_UNSUPPORTED, "GTA_FLAG_FP32_PRODUCTS backward: fp32 inputs at dh <= 64 (other sizes: gta_rep_apply + gta_attn_bwd_plain_f32)");
     GtaBwdParams p;
@@ -467,10 +471,7 @@ int bwd_call(const GtaAttnDesc* d, const void* q, const void* k, const void* v, 
     p.kvimg = kv_images; p.qimg = ws + L.off_qimg; p.stats = (float*)(ws + L.off_stats);
     p.dc_partial = (float*)(ws + L.off_dc); p.dtrans_coeff = (d->d_se3 > 0) ? dtrans_coeff : nullptr;
     p.dt_partial = (tau && dtau) ? (float*)(ws + L.off_dt) : nullptr; p.dtau = (tau && dtau) ? dtau : nullptr;
-    p.q_sb = d->q_stride[0]; p.q_sh = d->q_stride[1]; p.q_st = d->q_stride[2];
-    p.k_sb = d->k_stride[0]; p.k_sh = d->k_stride[1]; p.k_st = d->k_stride[2];
-    p.v_sb = d->v_stride[0]; p.v_sh = d->v_stride[1]; p.v_st = d->v_stride[2];
-    p.o_sb = d->o_stride[0]; p.o_sh = d->o_stride[1]; p.o_st = d->o_stride[2];
+    copy_strides(p, d);
     p.do_sb = dout_stride[0]; p.do_sh = dout_stride[1]; p.do_st = dout_stride[2];
     p.dq_sb = dqkv_stride[0]; p.dq_sh = dqkv_stride[1]; p.dq_st = dqkv_stride[2];
     p.dk_sb = dqkv_stride[3]; p.dk_sh = dqkv_stride[4]; p.dk_st = dqkv_stride[5];
@@ -480,9 +481,8 @@ int bwd_call(const GtaAttnDesc* d, const void* q, const void* k, const void* v, 
     p.Pq = d->Tq / d->Nq; p.Pk = d->Tk / d->Nk; p.invPq = 1.0f / (float)p.Pq; p.invPk = 1.0f / (float)p.Pk;
     p.dh = d->dh; p.nso2 = d->d_so2 / 2; p.flags = d->flags; p.scale = d->scale;
     if (d->H > 65535 || d->B > 65535) return fail(GTA_E_UNSUPPORTED, "B or H above 65535");
-    rc = varlen ? gta_bwd_varlen_dispatch(p, key_lens, q_lens, dhp, esz, (hipStream_t)stream) : gta_bwd_dispatch(p, dhp, esz, (hipStream_t)stream);
-    if (rc) return fail(rc, rc == GTA_E_LAUNCH ? hipGetErrorString(hipGetLastError()) : "no kernel instance");
-    return GTA_OK;
+    return launch_status(varlen ? gta_bwd_varlen_dispatch(p, key_lens, q_lens, dhp, esz, (hipStream_t)stream)
+                                : gta_bwd_dispatch(p, dhp, esz, (hipStream_t)stream), "no kernel instance");
 }
 }  // namespace
 
@@ -525,24 +525,18 @@ extern "C" int gta_attn_fwd_plain(const GtaAttnDesc* d, const void* q, const voi
     const int dhp = (d->dh + 7) / 8 * 8;
     if (dhp != d->dh || d->dh > 128) return fail(GTA_E_UNSUPPORTED, "plain attention needs dh % 8 == 0 and dh <= 128 (pad the channels)");
     if (key_bias && (bias_pitch % 64 || bias_pitch < d->Tk)) return fail(GTA_E_BADARG, "bias_pitch must be a multiple of 64 >= Tk");
-    const int esz = d->dtype == GTA_DTYPE_BF16 ? 2 : 4;
     GtaFwdParams p;
     memset(&p, 0, sizeof p);
     p.q = q; p.k = k; p.v = v; p.o = out; p.lse = lse; p.tau = tau;
     p.kbias = key_bias; p.kbias_pitch = bias_pitch;
-    p.q_sb = d->q_stride[0]; p.q_sh = d->q_stride[1]; p.q_st = d->q_stride[2];
-    p.k_sb = d->k_stride[0]; p.k_sh = d->k_stride[1]; p.k_st = d->k_stride[2];
-    p.v_sb = d->v_stride[0]; p.v_sh = d->v_stride[1]; p.v_st = d->v_stride[2];
-    p.o_sb = d->o_stride[0]; p.o_sh = d->o_stride[1]; p.o_st = d->o_stride[2];
+    copy_strides(p, d);
     p.B = d->B; p.H = d->H; p.Tq = d->Tq; p.Tk = d->Tk; p.Nq = 1; p.Nk = 1; p.Pq = d->Tq; p.Pk = d->Tk;
     p.invPq = 1.0f / p.Pq; p.invPk = 1.0f / p.Pk;
     p.dh = d->dh; p.nso2 = 0; p.n_qtiles = (d->Tq + 127) / 128; p.scale = d->scale;
     p.flags = d->flags & GTA_FLAG_FP32_PRODUCTS;
     if (p.flags && d->dtype != GTA_DTYPE_F32) return fail(GTA_E_BADARG, "GTA_FLAG_FP32_PRODUCTS is for fp32 inputs");
     const long n_wg = (long)d->B * d->H * p.n_qtiles;
-    int rc = gta_fwd_dispatch(p, padded_dh(d->dh), esz, true, (int)n_wg, (hipStream_t)stream);
-    if (rc) return fail(rc, rc == GTA_E_LAUNCH ? hipGetErrorString(hipGetLastError()) : "no kernel instance");
-    return GTA_OK;
+    return launch_status(gta_fwd_dispatch(p, padded_dh(d->dh), esz_of(d), true, (int)n_wg, (hipStream_t)stream), "no kernel instance");
 }
 
 // -------------------------------------------------------------------------------------------------------------------------------
@@ -552,8 +546,7 @@ namespace {
 
 // the side's (T, N, tokens per workgroup, workgroups per view), or an error
 int repgrad_geometry(const GtaAttnDesc* d, int32_t side, int& T, int& N, int& tpb, long& chunks) {
-    if (!d) return fail(GTA_E_BADARG, "null descriptor");
-    if (d->abi_version != GTA_ABI_VERSION) return fail(GTA_E_BADARG, "abi_version mismatch");
+    if (int rc = check_header(d)) return rc;
     if (side != 0 && side != 1) return fail(GTA_E_BADARG, "side must be 0 (query) or 1 (key)");
     T = side ? d->Tk : d->Tq;
     N = side ? d->Nk : d->Nq;
@@ -589,12 +582,11 @@ extern "C" int gta_rep_grad_sums(const GtaAttnDesc* d, int32_t side, int32_t n_p
     if (d->dtype != GTA_DTYPE_F32 && d->dtype != GTA_DTYPE_BF16) return fail(GTA_E_BADARG, "dtype must be GTA_DTYPE_F32 or GTA_DTYPE_BF16");
     if (n_pairs != 1 && n_pairs != 2) return fail(GTA_E_BADARG, "n_pairs must be 1 or 2");
     if (!view_sums && !so2_sums && !t2_sums) return fail(GTA_E_BADARG, "no output requested");
-    const int esz = d->dtype == GTA_DTYPE_BF16 ? 2 : 4;
+    const int esz = esz_of(d);
     if (bad_operand(a0, a0_stride, esz) || bad_operand(b0, b0_stride, esz) ||
         (n_pairs == 2 && (bad_operand(a1, a1_stride, esz) || bad_operand(b1, b1_stride, esz))))
         return fail(GTA_E_BADARG, "null, misaligned or negatively strided operand");
-    if (d->d_triv < 0 || d->d_se3 < 0 || d->d_so3 < 0 || d->d_so2 < 0 || d->d_t2 < 0) return fail(GTA_E_LAYOUT, "negative slab size");
-    if (d->d_triv + d->d_se3 + d->d_so3 + d->d_so2 + d->d_t2 != d->dh) return fail(GTA_E_LAYOUT, "f_dims do not sum to dh");
+    if (int rc = check_slabs(d)) return rc;
     const bool euclid = (d->flags & GTA_FLAG_EUCLID) != 0;
     if (d->d_se3 % (euclid ? 3 : 4) || d->d_so2 % 2 || d->d_t2 % 3) return fail(GTA_E_LAYOUT, "se3 / so2 / t2 slab not a whole number of groups");
     if ((view_sums && d->d_se3 == 0) || (so2_sums && d->d_so2 == 0) || (t2_sums && d->d_t2 == 0))
@@ -621,7 +613,5 @@ extern "C" int gta_rep_grad_sums(const GtaAttnDesc* d, int32_t side, int32_t n_p
     p.off_t2 = p.off_so2 + d->d_so2;
     p.n_t2 = t2_sums ? d->d_t2 / 3 : 0;
     p.part = (float*)workspace; p.view_out = view_sums; p.so2_out = so2_sums; p.t2_out = t2_sums;
-    int rc = gta_repgrad_dispatch(p, esz, euclid, (hipStream_t)stream);
-    if (rc) return fail(rc, rc == GTA_E_LAUNCH ? hipGetErrorString(hipGetLastError()) : "grid too large");
-    return GTA_OK;
+    return launch_status(gta_repgrad_dispatch(p, esz, euclid, (hipStream_t)stream), "grid too large");
 }

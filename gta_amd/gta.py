@@ -10,14 +10,11 @@ What differs, deliberately:
 """
 from __future__ import annotations
 
-import math
+import weakref
+from collections import namedtuple
 from typing import Dict, Optional, Tuple
 
 import numpy as np
-import weakref
-
-import os
-
 import torch
 
 from . import native
@@ -208,6 +205,46 @@ def _check_tables(q, k, f_dims, Nq, Nk, vrep_q, vrep_k, cs_q, cs_k, coord_q, coo
     native.check_scalar("tau", ta, dev)
 
 
+# what a forward entry is called with: q, k, v as the kernels read them, out ([B,H,Tq,dh] view of [B,Tq,H,dh] memory, so the caller's
+# 'b h n d -> b n (h d)' is a free view), the LSE, trans_coeff / tau as detached flat fp32 tensors (or None) and the descriptor
+_Call = namedtuple("_Call", "q k v out lse tc ta desc")
+
+
+def _setup_call(q, k, v, f_dims, so3_degree, Nq, Nk, scale, flags, tables, trans_coeff, tau, *, k_side=True, kernel_layout=True) -> _Call:
+    """The host work in front of every forward entry: dtype check and coercion, kernel layout (skipped by ``_GenericAttn``, whose rho-apply
+    kernels take any strides with unit channel stride), output buffers, descriptor, and the validation of everything that reaches the kernels
+    as a raw pointer.  ``tables``: dict of the packed rep tables; ``k_side=False`` lets the key-side ones be absent (pretransformed)."""
+    dt = q.dtype
+    if dt not in (torch.float32, torch.bfloat16):
+        raise native.GtaError(f"unsupported dtype {dt}: use float32 or bfloat16")
+    k, v = k.to(dt), v.to(dt)
+    if kernel_layout:
+        q, k, v = _as_kernel_layout(q), _as_kernel_layout(k), _as_kernel_layout(v)
+    B, H, Tq, dh = q.shape
+    out = torch.empty(B, Tq, H, dh, device=q.device, dtype=dt).permute(0, 2, 1, 3)
+    lse = torch.empty(B, H, Tq, device=q.device, dtype=torch.float32)
+    tc = trans_coeff.detach().to(torch.float32).reshape(-1) if torch.is_tensor(trans_coeff) else None
+    ta = tau.detach().to(torch.float32).reshape(-1) if torch.is_tensor(tau) else None
+    desc = native.make_desc(q, k, v, out, f_dims, so3_degree, Nq, Nk, scale, flags)
+    _check_tables(q, k, f_dims, Nq, Nk, tables.get("vrep_q"), tables.get("vrep_k"), tables.get("cs_q"), tables.get("cs_k"),
+                  tables.get("coord_q"), tables.get("coord_k"), tc, ta, k_side=k_side)
+    return _Call(q, k, v, out, lse, tc, ta, desc)
+
+
+def _scalar_meta(t):
+    """(shape, dtype) of the trans_coeff / tau parameter a Function was given, None without one"""
+    return (t.shape, t.dtype) if torch.is_tensor(t) else None
+
+
+def _restore_scalar(grad, meta):
+    """the kernels' flat fp32 d trans_coeff / d tau in the parameter's own shape and dtype"""
+    return None if grad is None or meta is None else grad.reshape(meta[0]).to(meta[1])
+
+
+def _layout_flags(v_transform: bool, euclid: bool) -> int:
+    return (native.FLAG_V_TRANSFORM if v_transform else 0) | (native.FLAG_EUCLID if euclid else 0)
+
+
 class _SplitPacked(torch.autograd.Function):
     """[B,T,n,H,dh] packed projection -> n strided [B,H,T,dh] views (layers.py:389,394-395), whose backward hands the
     attention backward's packed gradient buffer straight through (``backward._grad_buffers``) instead of letting autograd
@@ -242,54 +279,23 @@ def split_packed(packed: torch.Tensor):
 
 
 class _GtaAttn(torch.autograd.Function):
-    flash_events = None     # (start, end) torch.cuda.Event pair set by bench.py, else None
-
     @staticmethod
     def forward(ctx, q, k, v, trans_coeff, tau, kv_cache, cfg, vrep_q, vrep_k, cs_q, cs_k, *carriers):
         # carriers: () or six tensors / None (gta_amd.repgrad.split_tables) whose gradients the backward returns
-        f_dims, so3_degree, Nq, Nk, scale, flags = cfg
-        dt = q.dtype
-        if dt not in (torch.float32, torch.bfloat16):
-            raise native.GtaError(f"unsupported dtype {dt}: use float32 or bfloat16")
-        k = k.to(dt) if k.dtype != dt else k
-        v = v.to(dt) if v.dtype != dt else v
-        q, k, v = _as_kernel_layout(q), _as_kernel_layout(k), _as_kernel_layout(v)
-        B, H, Tq, dh = q.shape
-        # out is allocated [B,Tq,H,dh] so the caller's 'b h n d -> b n (h d)' is a free view
-        out = torch.empty(B, Tq, H, dh, device=q.device, dtype=dt).permute(0, 2, 1, 3)
-        lse = torch.empty(B, H, Tq, device=q.device, dtype=torch.float32)
-        tc = trans_coeff.detach().to(torch.float32).reshape(-1) if trans_coeff is not None else None
-        ta = tau.detach().to(torch.float32).reshape(-1) if tau is not None else None
-        desc = native.make_desc(q, k, v, out, f_dims, so3_degree, Nq, Nk, scale, flags)
-        _check_tables(q, k, f_dims, Nq, Nk, vrep_q, vrep_k, cs_q, cs_k, None, None, tc, ta,
-                      k_side=not (flags & native.FLAG_PRETRANSFORMED))
+        flags = cfg[5]
+        c = _setup_call(q, k, v, *cfg, dict(vrep_q=vrep_q, vrep_k=vrep_k, cs_q=cs_q, cs_k=cs_k), trans_coeff, tau,
+                        k_side=not (flags & native.FLAG_PRETRANSFORMED))
         ws = None
         if not (flags & (native.FLAG_FUSED_KV | native.FLAG_PRETRANSFORMED)):
-            plan_key = _plan_key_fused(flags, dt, B, H, k.shape[2], dh, f_dims, so3_degree, Nk)
-            ws = _two_stage_workspace(desc, flags, plan_key, kv_cache, q.device)
-        if ws is not None and _GtaAttn.flash_events is not None and not (desc.flags & native.FLAG_KV_READY):
-            # instrumentation (bench.py): bracket the attention kernel alone with stream events
-            desc.flags = flags | native.FLAG_PREP_ONLY
-            native.attn_fwd(desc, q, k, v, vrep_q, vrep_k, cs_q, cs_k, tc, ta, out, lse, ws)
-            desc.flags = flags | native.FLAG_KV_READY
-            _GtaAttn.flash_events[0].record()
-            native.attn_fwd(desc, q, k, v, vrep_q, vrep_k, cs_q, cs_k, tc, ta, out, lse, ws)
-            _GtaAttn.flash_events[1].record()
-        else:
-            if _GtaAttn.flash_events is not None:
-                _GtaAttn.flash_events[0].record()
-            native.attn_fwd(desc, q, k, v, vrep_q, vrep_k, cs_q, cs_k, tc, ta, out, lse, ws)
-            if _GtaAttn.flash_events is not None:
-                _GtaAttn.flash_events[1].record()
+            ws = _fused_workspace(c, cfg, kv_cache)
+        native.attn_fwd(c.desc, c.q, c.k, c.v, vrep_q, vrep_k, cs_q, cs_k, c.tc, c.ta, c.out, c.lse, ws)
         ctx.cfg = cfg
         # K'/V' tile images of the two-stage plan: reused by the backward (fp32-faithful plan: its hi / lo images by the X3 walks, r06)
         ctx.kv_images = ws
-        ctx.save_for_backward(q, k, v, out, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k)
-        ctx.tc_shape = None if trans_coeff is None else trans_coeff.shape
-        ctx.tc_dtype = None if trans_coeff is None else trans_coeff.dtype
-        ctx.tau_meta = None if tau is None else (tau.shape, tau.dtype)
+        ctx.save_for_backward(c.q, c.k, c.v, c.out, c.lse, c.tc, c.ta, vrep_q, vrep_k, cs_q, cs_k)
+        ctx.tc_meta, ctx.tau_meta = _scalar_meta(trans_coeff), _scalar_meta(tau)
         ctx.carriers = _repgrad.carrier_meta(carriers)
-        return out
+        return c.out
 
     @staticmethod
     def backward(ctx, dout):
@@ -298,12 +304,7 @@ class _GtaAttn(torch.autograd.Function):
         want_dtau = ta is not None and ctx.needs_input_grad[4]
         dq, dk, dv, dtc, dta = _bw.attn_bwd(ctx.cfg, q, k, v, out, dout, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k,
                                             kv_images=ctx.kv_images, want_dtau=want_dtau)
-        if ctx.tc_shape is not None and dtc is not None:
-            dtc = dtc.reshape(ctx.tc_shape).to(ctx.tc_dtype)
-        else:
-            dtc = None
-        if dta is not None:
-            dta = dta.reshape(ctx.tau_meta[0]).to(ctx.tau_meta[1])
+        dtc, dta = _restore_scalar(dtc, ctx.tc_meta), _restore_scalar(dta, ctx.tau_meta)
         grads = ()
         if ctx.carriers:
             # gradients of the tables: a pass after the backward over (q, dq), (dout, out) and (dk, k), (dv, v) (gta_amd/repgrad.py)
@@ -326,28 +327,22 @@ class _GenericAttn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, trans_coeff, tau, cfg, packed, *carriers):
         f_dims, so3_degree, scale, v_transform, euclid, precise = cfg
+        flags = _layout_flags(v_transform, euclid)
+        if q.dtype not in (torch.float32, torch.bfloat16):
+            raise native.GtaError(f"unsupported dtype {q.dtype}")
+        c = _setup_call(q, k, v, f_dims, so3_degree, *_views(f_dims, packed, q, k), scale, flags, packed, trans_coeff, tau, kernel_layout=False)
+        k, v, out, lse, tc, ta, desc = c.k, c.v, c.out, c.lse, c.tc, c.ta, c.desc
         dt = q.dtype
-        if dt not in (torch.float32, torch.bfloat16):
-            raise native.GtaError(f"unsupported dtype {dt}")
-        k, v = k.to(dt), v.to(dt)
         B, H, Tq, dh = q.shape
         Tk = k.shape[2]
-        Nq, Nk = _views(f_dims, packed, q, k)
-        flags = (native.FLAG_V_TRANSFORM if v_transform else 0) | (native.FLAG_EUCLID if euclid else 0)
         dhp = (dh + 7) // 8 * 8                                    # the attention kernel works on 8-channel chunks
         # (every kernel below writes all dh channels of every row: only PADDING channels need the zero fill -- 6 us + a launch boundary per buffer)
         alloc = torch.zeros if dhp != dh else torch.empty
         mk = lambda T: alloc(B, T, H, dhp, device=q.device, dtype=dt).permute(0, 2, 1, 3)
         qp, kp, vp, op = mk(Tq), mk(Tk), mk(Tk), mk(Tq)
-        out = torch.empty(B, Tq, H, dh, device=q.device, dtype=dt).permute(0, 2, 1, 3)
-        desc = native.make_desc(q, k, v, out, f_dims, so3_degree, Nq, Nk, scale, flags)
-        tc = trans_coeff.detach().float().reshape(-1) if torch.is_tensor(trans_coeff) else None
-        ta = tau.detach().float().reshape(-1) if torch.is_tensor(tau) else None
         pitch = (Tk + 63) // 64 * 64
         kbias = torch.zeros(B, H, pitch, device=q.device, dtype=torch.float32) if euclid else None
         vq, vk = packed.get("vrep_q"), packed.get("vrep_k")
-        _check_tables(q, k, f_dims, Nq, Nk, vq, vk, packed.get("cs_q"), packed.get("cs_k"), packed.get("coord_q"),
-                      packed.get("coord_k"), tc, ta)
         native.rep_apply(desc, 0, q, vq, packed.get("cs_q"), packed.get("coord_q"), tc, qp[..., :dh])
         native.rep_apply(desc, 1, k, vk, packed.get("cs_k"), packed.get("coord_k"), tc, kp[..., :dh], kbias, scale)
         if v_transform:
@@ -355,15 +350,13 @@ class _GenericAttn(torch.autograd.Function):
         else:
             vp[..., :dh] = v
         pdesc = native.make_desc(qp, kp, vp, op, {"triv": dhp}, 0, 1, 1, scale, native.FLAG_FP32_PRODUCTS if precise else 0)
-        lse = torch.empty(B, H, Tq, device=q.device, dtype=torch.float32)
         native.attn_fwd_plain(pdesc, qp, kp, vp, kbias, ta, op, lse)
         if v_transform:
             native.rep_apply(desc, 2, op[..., :dh], vq, packed.get("cs_q"), packed.get("coord_q"), tc, out)
         else:
             out.copy_(op[..., :dh])
         ctx.cfg, ctx.packed, ctx.flags = cfg, packed, flags
-        ctx.tc_meta = None if not torch.is_tensor(trans_coeff) else (trans_coeff.shape, trans_coeff.dtype)
-        ctx.tau_meta = None if not torch.is_tensor(tau) else (tau.shape, tau.dtype)
+        ctx.tc_meta, ctx.tau_meta = _scalar_meta(trans_coeff), _scalar_meta(tau)
         ctx.carriers = _repgrad.carrier_meta(carriers)
         ctx.save_for_backward(q, k, v, qp, kp, vp, op, lse, tc, ta)
         return out
@@ -433,8 +426,7 @@ class _GenericAttn(torch.autograd.Function):
         else:
             dqp, dkp, dvp, _, dta = _bw.attn_bwd(pcfg, qp, kp, vp, op, dop, lse, None, ta, None, None, None, None,
                                                  want_dtau=want_dtau)
-        if dta is not None:
-            dta = dta.reshape(ctx.tau_meta[0]).to(ctx.tau_meta[1])
+        dta = _restore_scalar(dta, ctx.tau_meta)
         if euclid:
             pitch = (Tk + 63) // 64 * 64
             dbias = torch.zeros(B, H, pitch, device=q.device, dtype=torch.float32)
@@ -453,7 +445,7 @@ class _GenericAttn(torch.autograd.Function):
         dtc = None
         if need_tc:
             assert row_at[0] == n_rows
-            dtc = row_buf.sum(dtype=torch.float64).to(ctx.tc_meta[1]).reshape(ctx.tc_meta[0])
+            dtc = _restore_scalar(row_buf.sum(dtype=torch.float64), ctx.tc_meta)
         grads = ()
         if ctx.carriers:
             # gradients of the tables, in the transformed space: (q, dq'), (dout, o~) and (dk', k), (dv', v) (gta_amd/repgrad.py); under
@@ -476,6 +468,13 @@ def _generic_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scal
     return _GenericAttn.apply(q, k, v, tc, ta, (f_dims, so3_degree, scale, v_transform, euclid, precise), packed, *carriers)
 
 
+def _probe(dtype, q_shape, Tk: int, f_dims, so3_degree: int, Nq: int, Nk: int, flags: int):
+    """the descriptor the routes ask the library about: the call's sizes at contiguous strides"""
+    B, H, Tq, dh = q_shape
+    qs, ks = (H * Tq * dh, Tq * dh, dh), (H * Tk * dh, Tk * dh, dh)
+    return native.make_desc_from(dtype, q_shape, Tk, (qs, ks, ks, qs), f_dims, so3_degree, Nq, Nk, 1.0, flags)
+
+
 def generic_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree: int, Nq: int, Nk: int, *, v_transform: bool = True,
                   euclid: bool = False, precise: bool = False, needs_grad: bool = False, key_views: bool = False,
                   key_views_backward: bool = False) -> str:
@@ -496,10 +495,7 @@ def generic_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree: i
         if key_views:
             raise native.GtaError(f"key_views: unsupported dtype {dtype} (use float32 or bfloat16)")
         return "apply"
-    B, H, Tq, dh = q_shape
-    qs, ks = (H * Tq * dh, Tq * dh, dh), (H * Tk * dh, Tk * dh, dh)
-    flags = (native.FLAG_V_TRANSFORM if v_transform else 0) | (native.FLAG_EUCLID if euclid else 0)
-    probe = native.make_desc_from(dtype, q_shape, Tk, (qs, ks, ks, qs), f_dims, so3_degree, Nq, Nk, 1.0, flags)
+    probe = _probe(dtype, q_shape, Tk, f_dims, so3_degree, Nq, Nk, _layout_flags(v_transform, euclid))
     if key_views:
         rc = native.attn_fwd_staged_varlen_supported(probe)
         if rc != 0:
@@ -525,32 +521,27 @@ def _key_views_refusals(*, needs_grad=False, precise=False, pretransformed=False
 def check_key_views(key_views, B: int, Nk: Optional[int], name: str = "key_views") -> Tuple[int, ...]:
     """Host-side validation of per-scene view counts (a sequence or a CPU integer tensor of length B, each in 1..Nk) -> a tuple of ints.
     Nothing here touches the device, so there is no sync.  ``name``: what the messages call the argument (``query_views`` against Nq)."""
-    if name != "key_views":
-        try:
-            return check_key_views(key_views, B, Nk)
-        except native.GtaError as e:
-            raise native.GtaError(str(e).replace("key_views", name).replace("Nk", "Nq").replace("vrep_k", "vrep_q").replace("key views", "query views")) from None
+    bound, table, views = ("Nk", "vrep_k", "key views") if name == "key_views" else ("Nq", "vrep_q", "query views")
     if torch.is_tensor(key_views):
         if key_views.is_cuda:
-            raise native.GtaError("key_views must be a host sequence or a CPU tensor (validating a device tensor would sync)")
+            raise native.GtaError(f"{name} must be a host sequence or a CPU tensor (validating a device tensor would sync)")
         if key_views.is_floating_point() or key_views.is_complex() or key_views.dtype == torch.bool or key_views.dim() != 1:
-            raise native.GtaError("key_views must be a 1-D integer tensor")
+            raise native.GtaError(f"{name} must be a 1-D integer tensor")
         key_views = key_views.tolist()
     try:
         vals = tuple(key_views)
     except TypeError:
-        raise native.GtaError("key_views must be a sequence of B view counts") from None
+        raise native.GtaError(f"{name} must be a sequence of B view counts") from None
     if any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) for x in vals):
-        raise native.GtaError(f"key_views must hold integers, got {vals}")
+        raise native.GtaError(f"{name} must hold integers, got {vals}")
     vals = tuple(int(x) for x in vals)
     if len(vals) != B:
-        raise native.GtaError(f"key_views has {len(vals)} entries for a batch of {B} scenes")
+        raise native.GtaError(f"{name} has {len(vals)} entries for a batch of {B} scenes")
     if Nk is None:
-        raise native.GtaError("key_views needs the number of key views Nk, which the view tables give (vrep_k): this layout has no "
+        raise native.GtaError(f"{name} needs the number of {views} {bound}, which the view tables give ({table}): this layout has no "
                               "se3 / so3 slab and so no view structure")
-    bad = [x for x in vals if x < 1 or x > Nk]
-    if bad:
-        raise native.GtaError(f"key_views entries must lie in 1..Nk = 1..{Nk}, got {vals}")
+    if any(x < 1 or x > Nk for x in vals):
+        raise native.GtaError(f"{name} entries must lie in 1..{bound} = 1..{Nk}, got {vals}")
     return vals
 
 
@@ -559,95 +550,81 @@ def key_lens_tensor(key_views: Tuple[int, ...], Pk: int, device) -> torch.Tensor
     return torch.tensor([n * Pk for n in key_views], dtype=torch.int32).to(device, non_blocking=True)
 
 
-def _plan_key_fused(flags, dt, B, H, Tk, dh, f_dims, so3_degree, Nk):
-    """what the images of a cache depend on: the key side's shape and layout, the dtype (bf16 / fp32 inputs pick different instances) and the
-    arithmetic mode -- the fp32-faithful plan stores FOUR images per tile [K'hi | V'hi | K'lo | V'lo], the default plan two: a cache
-    written under one plan must never be streamed under the other (the byte-size check alone let that through).  A call with
-    key_views appends the view counts."""
-    return (bool(flags & native.FLAG_FP32_PRODUCTS), bool(flags & native.FLAG_V_TRANSFORM), str(dt), B, H, int(Tk), dh,
-            tuple(sorted((g, int(n)) for g, n in f_dims.items() if n)), int(so3_degree), int(Nk))
+def _plan_key(family: str, flags, dt, B, H, Tk, dh, f_dims, so3_degree, Nk, scale, key_views):
+    """what the images of a cache depend on besides the keys, reps and trans_coeff (the caller's contract, see gta_attention): the family
+    ('fused' / 'staged': different tile images), the key side's shape and layout, the dtype (bf16 / fp32 inputs pick different instances), the
+    arithmetic mode -- the fp32-faithful plan stores FOUR images per tile [K'hi | V'hi | K'lo | V'lo], the default plan two: a cache written
+    under one plan must never be streamed under the other (the byte-size check alone let that through) --, under euclid the scale,
+    which the cached key bias -0.5 scale |k'|^2 carries, and last the view counts of a call with key_views (else None)."""
+    euclid = bool(flags & native.FLAG_EUCLID)
+    return (family, bool(flags & native.FLAG_FP32_PRODUCTS), bool(flags & native.FLAG_V_TRANSFORM), euclid, str(dt), B, H, int(Tk), dh,
+            tuple(sorted((g, int(n)) for g, n in f_dims.items() if n)), int(so3_degree), int(Nk), float(scale) if euclid else None,
+            None if key_views is None else tuple(key_views))
 
 
-def _two_stage_workspace(desc, flags, plan_key, kv_cache, device):
-    """The K'/V' workspace of a two-stage call (``_GtaAttn`` and ``_varlen_forward`` alike): a fresh one -- stored in ``kv_cache`` with its
-    plan key when there is a cache --, or the cache's images, with GTA_FLAG_KV_READY set in ``desc``; images written under another plan or
-    for another key set raise ``GtaError``."""
-    if kv_cache is not None and kv_cache.get("images") is not None:
-        # K'/V' tile images of an earlier call against the same keys (chunked decode): skip the pre-pass
-        ws = kv_cache["images"]
-        if kv_cache.get("plan") != plan_key:
-            raise native.GtaError(f"kv_cache holds images written under another plan {kv_cache.get('plan')} (this call: {plan_key}): "
-                                  "use one cache dict per (key set, dtype, precise mode)")
-        if ws.numel() < native.attn_fwd_workspace_bytes(desc) or ws.device != device:
-            raise native.GtaError("kv_cache holds images of a different key set")
-        desc.flags = flags | native.FLAG_KV_READY
-        return ws
-    need = native.attn_fwd_workspace_bytes(desc)
-    if kv_cache is not None:
-        # the workspace's tail (query-side operand tiles) grows with the number of QUERY views: a cache serves later query
-        # sets against the same keys, so it is sized by asking the library for the most views a call can have (the size
-        # rule -- which instances carry a tail, how large a tile is -- stays the library's)
-        widest = type(desc).from_buffer_copy(desc)
-        widest.Nq = widest.Tq = native.MAX_VIEWS
-        need = max(need, native.attn_fwd_workspace_bytes(widest))
-    ws = torch.empty(need, device=device, dtype=torch.uint8)
-    if kv_cache is not None:
+def _two_stage_workspace(desc, flags, plan_key, kv_cache, device, need, cache_bytes=0):
+    """The K'/V' workspace of a two-stage call, ``need`` bytes, in both families: a fresh one -- stored in ``kv_cache`` with its plan key
+    when there is a cache, and then of at least ``cache_bytes`` --, or the cache's images, with GTA_FLAG_KV_READY set in ``desc``; images
+    written under another plan or for another key set raise ``GtaError``."""
+    if kv_cache is None:
+        return torch.empty(need, device=device, dtype=torch.uint8)
+    ws = kv_cache.get("images")
+    if ws is None:
+        ws = torch.empty(max(need, cache_bytes), device=device, dtype=torch.uint8)
         kv_cache["images"], kv_cache["plan"] = ws, plan_key
+        return ws
+    # K'/V' tile images of an earlier call against the same keys (chunked decode): skip the pre-pass
+    if kv_cache.get("plan") != plan_key:
+        raise native.GtaError(f"kv_cache holds images written under another plan {kv_cache.get('plan')} (this call: {plan_key}): "
+                              "use one cache dict per (key set, dtype, precise mode)")
+    if ws.numel() < need or ws.device != device:
+        raise native.GtaError("kv_cache holds images of a different key set")
+    desc.flags = flags | native.FLAG_KV_READY
     return ws
 
 
-def _varlen_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, flags, key_views, key_lens, kv_cache=None):
-    """The fused layouts with per-scene key prefixes, no gradient: ``gta_attn_fwd_varlen`` -- the two-stage plan's pre-pass and
-    gta_fwd2_kernel in their VARLEN instances.  ``kv_cache`` as in ``_GtaAttn``; its plan key carries the view counts."""
-    dt = q.dtype
-    k, v = k.to(dt), v.to(dt)
-    q, k, v = _as_kernel_layout(q), _as_kernel_layout(k), _as_kernel_layout(v)
-    B, H, Tq, dh = q.shape
-    Tk = k.shape[2]
-    Nq, Nk = _views(f_dims, packed, q, k)
-    out = torch.empty(B, Tq, H, dh, device=q.device, dtype=dt).permute(0, 2, 1, 3)
-    lse = torch.empty(B, H, Tq, device=q.device, dtype=torch.float32)
-    tc = trans_coeff.detach().float().reshape(-1) if torch.is_tensor(trans_coeff) else None
-    ta = tau.detach().float().reshape(-1) if torch.is_tensor(tau) else None
-    desc = native.make_desc(q, k, v, out, f_dims, so3_degree, Nq, Nk, scale, flags)
-    _check_tables(q, k, f_dims, Nq, Nk, packed.get("vrep_q"), packed.get("vrep_k"), packed.get("cs_q"), packed.get("cs_k"), None, None, tc, ta)
-    plan_key = _plan_key_fused(flags, dt, B, H, Tk, dh, f_dims, so3_degree, Nk) + (tuple(key_views),)
-    ws = _two_stage_workspace(desc, flags, plan_key, kv_cache, q.device)
-    native.attn_fwd_varlen(desc, q, k, v, packed.get("vrep_q"), packed.get("vrep_k"), packed.get("cs_q"), packed.get("cs_k"), tc, ta,
-                           key_lens, out, lse, ws)
-    return out
+def _fused_workspace(c: _Call, cfg, kv_cache, key_views=None):
+    """``_two_stage_workspace`` for the fused family (``_GtaAttn`` and the varlen forward alike)"""
+    f_dims, so3_degree, _, Nk, scale, flags = cfg
+    need = native.attn_fwd_workspace_bytes(c.desc)
+    if kv_cache is None:
+        return _two_stage_workspace(c.desc, flags, None, None, c.q.device, need)
+    # the workspace's tail (query-side operand tiles) grows with the number of QUERY views: a cache serves later query sets against the
+    # same keys, so it is sized by asking the library for the most views a call can have (the size rule -- which instances carry a
+    # tail, how large a tile is -- stays the library's)
+    cache_bytes = 0
+    if kv_cache.get("images") is None:
+        widest = type(c.desc).from_buffer_copy(c.desc)
+        widest.Nq = widest.Tq = native.MAX_VIEWS
+        cache_bytes = native.attn_fwd_workspace_bytes(widest)
+    B, H, Tk, dh = c.k.shape
+    plan_key = _plan_key("fused", flags, c.q.dtype, B, H, Tk, dh, f_dims, so3_degree, Nk, scale, key_views)
+    return _two_stage_workspace(c.desc, flags, plan_key, kv_cache, c.q.device, need, cache_bytes)
+
+
+def _varlen_forward(q, k, v, cfg, tables, trans_coeff, tau, key_lens, key_views=None, kv_cache=None):
+    """The fused layouts with per-scene key prefixes: ``gta_attn_fwd_varlen`` -- the two-stage plan's pre-pass and gta_fwd2_kernel in their
+    VARLEN instances.  ``kv_cache`` as in ``_GtaAttn``; its plan key carries the view counts.  -> (the call, its workspace)"""
+    c = _setup_call(q, k, v, *cfg, tables, trans_coeff, tau)
+    ws = _fused_workspace(c, cfg, kv_cache, key_views)
+    native.attn_fwd_varlen(c.desc, c.q, c.k, c.v, tables.get("vrep_q"), tables.get("vrep_k"), tables.get("cs_q"), tables.get("cs_k"),
+                           c.tc, c.ta, key_lens, c.out, c.lse, ws)
+    return c, ws
 
 
 class _VarlenAttn(torch.autograd.Function):
-    """The fused layouts with per-scene key prefixes under grad (``key_views_backward=True``): ``gta_attn_fwd_varlen`` forward, whose workspace
+    """The fused layouts with per-scene key prefixes under grad (``key_views_backward=True``): the forward of ``_varlen_forward``, whose workspace
     (the masked K'/V' tile images) and LSE serve ``gta_attn_bwd_varlen``.  ``q_lens`` (or None) masks padded query rows in the backward only.
     Gradients: q, k, v, trans_coeff, tau -- as ``_GtaAttn``; none for the tables."""
 
     @staticmethod
     def forward(ctx, q, k, v, trans_coeff, tau, cfg, key_lens, q_lens, vrep_q, vrep_k, cs_q, cs_k):
-        f_dims, so3_degree, Nq, Nk, scale, flags = cfg
-        dt = q.dtype
-        if dt not in (torch.float32, torch.bfloat16):
-            raise native.GtaError(f"unsupported dtype {dt}: use float32 or bfloat16")
-        k = k.to(dt) if k.dtype != dt else k
-        v = v.to(dt) if v.dtype != dt else v
-        q, k, v = _as_kernel_layout(q), _as_kernel_layout(k), _as_kernel_layout(v)
-        B, H, Tq, dh = q.shape
-        out = torch.empty(B, Tq, H, dh, device=q.device, dtype=dt).permute(0, 2, 1, 3)
-        lse = torch.empty(B, H, Tq, device=q.device, dtype=torch.float32)
-        tc = trans_coeff.detach().to(torch.float32).reshape(-1) if trans_coeff is not None else None
-        ta = tau.detach().to(torch.float32).reshape(-1) if tau is not None else None
-        desc = native.make_desc(q, k, v, out, f_dims, so3_degree, Nq, Nk, scale, flags)
-        _check_tables(q, k, f_dims, Nq, Nk, vrep_q, vrep_k, cs_q, cs_k, None, None, tc, ta)
-        native._require_cuda(q, k, v)
-        ws = torch.empty(native.attn_fwd_workspace_bytes(desc), device=q.device, dtype=torch.uint8)
-        native.attn_fwd_varlen(desc, q, k, v, vrep_q, vrep_k, cs_q, cs_k, tc, ta, key_lens, out, lse, ws)
+        c, ws = _varlen_forward(q, k, v, cfg, dict(vrep_q=vrep_q, vrep_k=vrep_k, cs_q=cs_q, cs_k=cs_k), trans_coeff, tau, key_lens)
         ctx.cfg = cfg
         ctx.kv_images = ws
-        ctx.save_for_backward(q, k, v, out, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k, key_lens, q_lens)
-        ctx.tc_meta = None if trans_coeff is None else (trans_coeff.shape, trans_coeff.dtype)
-        ctx.tau_meta = None if tau is None else (tau.shape, tau.dtype)
-        return out
+        ctx.save_for_backward(c.q, c.k, c.v, c.out, c.lse, c.tc, c.ta, vrep_q, vrep_k, cs_q, cs_k, key_lens, q_lens)
+        ctx.tc_meta, ctx.tau_meta = _scalar_meta(trans_coeff), _scalar_meta(tau)
+        return c.out
 
     @staticmethod
     def backward(ctx, dout):
@@ -656,10 +633,7 @@ class _VarlenAttn(torch.autograd.Function):
         want_dtau = ta is not None and ctx.needs_input_grad[4]
         dq, dk, dv, dtc, dta = _bw.attn_bwd(ctx.cfg, q, k, v, out, dout, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k,
                                             kv_images=ctx.kv_images, want_dtau=want_dtau, key_lens=key_lens, q_lens=q_lens)
-        dtc = dtc.reshape(ctx.tc_meta[0]).to(ctx.tc_meta[1]) if (ctx.tc_meta is not None and dtc is not None) else None
-        if dta is not None:
-            dta = dta.reshape(ctx.tau_meta[0]).to(ctx.tau_meta[1])
-        return (dq, dk, dv, dtc, dta) + (None,) * 7
+        return (dq, dk, dv, _restore_scalar(dtc, ctx.tc_meta), _restore_scalar(dta, ctx.tau_meta)) + (None,) * 7
 
 
 def _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, kv_cache=None, key_views=None,
@@ -668,47 +642,19 @@ def _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale
     launch alone on a call that finds its K'/V' images in ``kv_cache`` -- the contract of ``_GtaAttn``: images and plan key are stored by
     the first call, later calls against another key set / plan raise ``GtaError``.  ``key_views`` (validated) with ``key_lens`` (device):
     the varlen entry, and the view counts join the plan key."""
-    dt = q.dtype
-    k, v = k.to(dt), v.to(dt)
-    q, k, v = _as_kernel_layout(q), _as_kernel_layout(k), _as_kernel_layout(v)
-    B, H, Tq, dh = q.shape
-    Tk = k.shape[2]
+    flags = _layout_flags(v_transform, euclid)
     Nq, Nk = _views(f_dims, packed, q, k)
-    flags = (native.FLAG_V_TRANSFORM if v_transform else 0) | (native.FLAG_EUCLID if euclid else 0)
-    out = torch.empty(B, Tq, H, dh, device=q.device, dtype=dt).permute(0, 2, 1, 3)
-    lse = torch.empty(B, H, Tq, device=q.device, dtype=torch.float32)
-    tc = trans_coeff.detach().float().reshape(-1) if torch.is_tensor(trans_coeff) else None
-    ta = tau.detach().float().reshape(-1) if torch.is_tensor(tau) else None
-    desc = native.make_desc(q, k, v, out, f_dims, so3_degree, Nq, Nk, scale, flags)
-    _check_tables(q, k, f_dims, Nq, Nk, packed.get("vrep_q"), packed.get("vrep_k"), packed.get("cs_q"), packed.get("cs_k"),
-                  packed.get("coord_q"), packed.get("coord_k"), tc, ta)
-    need = native.attn_fwd_staged_workspace_bytes(desc)
-    # what the images depend on besides the keys, reps and trans_coeff (the caller's contract, see gta_attention): layout, dtype, key-side
-    # shape -- and under euclid the scale, which the cached key bias -0.5 scale |k'|^2 carries (the workspace's size does not depend on
-    # the query side)
-    plan_key = ("staged", bool(v_transform), bool(euclid), str(dt), B, H, Tk, dh,
-                tuple(sorted((g, int(n)) for g, n in f_dims.items() if n)), int(so3_degree), int(Nk), float(scale) if euclid else None)
+    c = _setup_call(q, k, v, f_dims, so3_degree, Nq, Nk, scale, flags, packed, trans_coeff, tau)
+    B, H, Tk, dh = c.k.shape
+    # (the workspace's size does not depend on the query side)
+    plan_key = None if kv_cache is None else _plan_key("staged", flags, c.q.dtype, B, H, Tk, dh, f_dims, so3_degree, Nk, scale, key_views)
+    ws = _two_stage_workspace(c.desc, flags, plan_key, kv_cache, c.q.device, native.attn_fwd_staged_workspace_bytes(c.desc))
+    tables = [packed.get(t) for t in ("vrep_q", "vrep_k", "cs_q", "cs_k", "coord_q", "coord_k")]
     if key_views is not None:
-        plan_key = plan_key + (tuple(key_views),)
-    if kv_cache is not None and kv_cache.get("images") is not None:
-        ws = kv_cache["images"]
-        if kv_cache.get("plan") != plan_key:
-            raise native.GtaError(f"kv_cache holds images written under another plan {kv_cache.get('plan')} (this call: {plan_key}): "
-                                  "use one cache dict per (key set, dtype, precise mode)")
-        if ws.numel() < need or ws.device != q.device:
-            raise native.GtaError("kv_cache holds images of a different key set")
-        desc.flags = flags | native.FLAG_KV_READY
+        native.attn_fwd_staged_varlen(c.desc, c.q, c.k, c.v, *tables, c.tc, c.ta, key_lens, c.out, c.lse, ws)
     else:
-        ws = torch.empty(need, device=q.device, dtype=torch.uint8)
-        if kv_cache is not None:
-            kv_cache["images"], kv_cache["plan"] = ws, plan_key
-    if key_views is not None:
-        native.attn_fwd_staged_varlen(desc, q, k, v, packed.get("vrep_q"), packed.get("vrep_k"), packed.get("cs_q"), packed.get("cs_k"),
-                                      packed.get("coord_q"), packed.get("coord_k"), tc, ta, key_lens, out, lse, ws)
-        return out
-    native.attn_fwd_staged(desc, q, k, v, packed.get("vrep_q"), packed.get("vrep_k"), packed.get("cs_q"), packed.get("cs_k"),
-                           packed.get("coord_q"), packed.get("coord_k"), tc, ta, out, lse, ws)
-    return out
+        native.attn_fwd_staged(c.desc, c.q, c.k, c.v, *tables, c.tc, c.ta, c.out, c.lse, ws)
+    return c.out
 
 
 def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: int = 0,
@@ -779,35 +725,28 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
         if key_views_backward and carriers:
             raise native.GtaError("key_views_backward: no gradient for rep tables or poses under key_views (gta_rep_grad_sums has no key mask): "
                                   "detach the tables")
-    flags = attention_route(tuple(q.shape), k.shape[2], q.dtype, f_dims, so3_degree, Nq, Nk, v_transform=v_transform, euclid=euclid,
-                            pretransformed=pretransformed, use_dma=use_dma, kv_mode=kv_mode, kv_cache=kv_cache is not None,
-                            precise=bool(precise), needs_grad=needs_grad, key_views=key_views is not None,
-                            key_views_backward=bool(key_views_backward))
-    if key_views is not None:
-        if flags is None:
-            generic_route(tuple(q.shape), k.shape[2], q.dtype, f_dims, so3_degree, Nq, Nk, v_transform=v_transform, euclid=euclid,
-                          precise=bool(precise), needs_grad=needs_grad, key_views=True,
-                          key_views_backward=bool(key_views_backward))                          # ('staged', or it raises)
-        if key_lens is None:
-            key_lens = key_lens_tensor(key_views, k.shape[2] // Nk, q.device)
-        if flags is not None and needs_grad:          # (key_views_backward: anything else was refused above)
-            q_lens = None if query_views is None else key_lens_tensor(query_views, q.shape[2] // Nq, q.device)
-            cfg = ({k_: int(v_) for k_, v_ in f_dims.items()}, int(so3_degree), Nq, Nk, float(scale), flags)
-            return _VarlenAttn.apply(q, k, v, trans_coeff, tau, cfg, key_lens, q_lens, packed.get("vrep_q"), packed.get("vrep_k"),
-                                     packed.get("cs_q"), packed.get("cs_k"))
-        if flags is not None:
-            return _varlen_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, flags, key_views, key_lens, kv_cache)
+    how = dict(v_transform=v_transform, euclid=euclid, precise=bool(precise), needs_grad=needs_grad, key_views=key_views is not None,
+               key_views_backward=bool(key_views_backward))
+    flags = attention_route(tuple(q.shape), k.shape[2], q.dtype, f_dims, so3_degree, Nq, Nk, pretransformed=pretransformed, use_dma=use_dma,
+                            kv_mode=kv_mode, kv_cache=kv_cache is not None, **how)
+    # no fused kernel: 'staged' or 'apply' (under key_views: 'staged', or it raises)
+    route = generic_route(tuple(q.shape), k.shape[2], q.dtype, f_dims, so3_degree, Nq, Nk, **how) if flags is None else "fused"
+    if key_views is not None and key_lens is None:
+        key_lens = key_lens_tensor(key_views, k.shape[2] // Nk, q.device)
+    if route == "staged":
         return _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, kv_cache,
                                key_views=key_views, key_lens=key_lens)
-    if flags is None:
-        if generic_route(tuple(q.shape), k.shape[2], q.dtype, f_dims, so3_degree, Nq, Nk, v_transform=v_transform, euclid=euclid,
-                         precise=bool(precise), needs_grad=needs_grad) == "staged":
-            return _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, kv_cache)
+    if route == "apply":
         return _generic_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, precise=bool(precise),
                                 carriers=carriers)
     cfg = ({k_: int(v_) for k_, v_ in f_dims.items()}, int(so3_degree), Nq, Nk, float(scale), flags)
-    return _GtaAttn.apply(q, k, v, trans_coeff, tau, kv_cache, cfg, packed.get("vrep_q"), packed.get("vrep_k"),
-                          packed.get("cs_q"), packed.get("cs_k"), *carriers)
+    tables = [packed.get(t) for t in ("vrep_q", "vrep_k", "cs_q", "cs_k")]
+    if key_views is None:
+        return _GtaAttn.apply(q, k, v, trans_coeff, tau, kv_cache, cfg, *tables, *carriers)
+    if needs_grad:          # (key_views_backward: anything else was refused above)
+        q_lens = None if query_views is None else key_lens_tensor(query_views, q.shape[2] // Nq, q.device)
+        return _VarlenAttn.apply(q, k, v, trans_coeff, tau, cfg, key_lens, q_lens, *tables)
+    return _varlen_forward(q, k, v, cfg, packed, trans_coeff, tau, key_lens, key_views, kv_cache)[0].out
 
 
 # kv_mode name -> flags of its tuning knob; every name but 'auto' and 'fused' asks for the two-stage plan ('prepass')
@@ -842,28 +781,23 @@ def attention_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree:
     serve ``gta_attn_bwd_varlen``."""
     if kv_mode not in KV_MODES:
         raise ValueError(f"kv_mode {kv_mode!r}")
+    flags = KV_MODES[kv_mode] | _layout_flags(v_transform, euclid) | (0 if use_dma else native.FLAG_NO_DMA)
+    probe = lambda fl: _probe(dtype, q_shape, Tk, f_dims, so3_degree, Nq, Nk, fl)
     if key_views:
         _key_views_refusals(needs_grad=needs_grad, precise=precise, pretransformed=pretransformed, kv_mode=kv_mode,
                             key_views_backward=key_views_backward)
-        flags = (KV_MODES[kv_mode] | (native.FLAG_V_TRANSFORM if v_transform else 0) | (native.FLAG_EUCLID if euclid else 0)
-                 | (0 if use_dma else native.FLAG_NO_DMA))
-        B, H, Tq, dh = q_shape
-        qs, ks = (H * Tq * dh, Tq * dh, dh), (H * Tk * dh, Tk * dh, dh)
-        probe = native.make_desc_from(dtype, q_shape, Tk, (qs, ks, ks, qs), f_dims, so3_degree, Nq, Nk, 1.0, flags)
-        if native.attn_fwd_supported(probe) == -3:         # GTA_E_UNSUPPORTED: a generic layout
+        if native.attn_fwd_supported(probe(flags)) == native.E_UNSUPPORTED:         # a generic layout
             return None
         # a fused layout: what the varlen entry refuses now is a flag (GTA_FLAG_FUSED_KV, ...), and that is said, not routed elsewhere
-        native.check(native.attn_fwd_varlen_supported(probe), "gta_attn_fwd_varlen_supported")
+        native.check(native.attn_fwd_varlen_supported(probe(flags)), "gta_attn_fwd_varlen_supported")
         return flags
-    flags = (KV_MODES[kv_mode] | (native.FLAG_V_TRANSFORM if v_transform else 0) | (native.FLAG_EUCLID if euclid else 0)
-             | (native.FLAG_PRETRANSFORMED if pretransformed else 0) | (0 if use_dma else native.FLAG_NO_DMA))
+    if pretransformed:
+        flags |= native.FLAG_PRETRANSFORMED
     if precise:
         if dtype != torch.float32:
             raise native.GtaError("precise=True is for float32 inputs (bf16 inputs ask for bf16 arithmetic)")
         flags |= native.FLAG_FP32_PRODUCTS
-    B, H, Tq, dh = q_shape
-    qs, ks = (H * Tq * dh, Tq * dh, dh), (H * Tk * dh, Tk * dh, dh)
-    probe = lambda fl: native.make_desc_from(dtype, q_shape, Tk, (qs, ks, ks, qs), f_dims, so3_degree, Nq, Nk, 1.0, fl)
+    Tq = q_shape[2]
     route = "prepass" if kv_cache or kv_mode.startswith("prepass") else kv_mode
     if route == "auto":
         route = "prepass" if Tq > 256 else "fused"
@@ -883,7 +817,7 @@ def attention_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree:
         # backward (gta_plain32.hip) and the adjoint rho kernels -- the generic path serves every layout that way.
         flags &= ~native.FLAG_FUSED_KV        # (use_dma=False too ends on the two-stage plan here: kept as it was, changing it is a change of behaviour)
         return flags if kv_mode != "fused" and native.attn_fwd_workspace_bytes(probe(flags)) > 0 else None
-    if not pretransformed and native.attn_fwd_supported(probe(flags)) == -3:       # GTA_E_UNSUPPORTED: valid request, no fused kernel
+    if not pretransformed and native.attn_fwd_supported(probe(flags)) == native.E_UNSUPPORTED:       # GTA_E_UNSUPPORTED: valid request, no fused kernel
         return None
     return flags
 

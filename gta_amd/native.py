@@ -36,6 +36,7 @@ FLAG_BWD_SPLIT = 1 << 15
 VREP_STRIDE = 72
 VREP_INV, VREP_REP, VREP_D1, VREP_D2 = 0, 16, 32, 41
 MAX_VIEWS = 16
+E_UNSUPPORTED = -3      # GTA_E_UNSUPPORTED: a valid request this build has no kernel for
 
 # every symbol include/gta_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = (
@@ -163,6 +164,12 @@ def _ptr(t: Optional[torch.Tensor]):
 
 def _stream():
     return c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _strides(*ts):
+    """the (batch, head, token) element strides of the [B,H,T,dh] views ``ts``, one after the other, as the ABI reads them"""
+    flat = [s for t in ts for s in t.stride()[:3]]
+    return (c_int64 * len(flat))(*flat)
 
 
 def _require_cuda(*ts):
@@ -299,19 +306,57 @@ def make_desc_from(dtype, q_shape, Tk: int, strides, f_dims: dict, so3_degree: i
     return d
 
 
+def _check_key_lens(key_lens, B: int, device):
+    if (not torch.is_tensor(key_lens) or key_lens.dtype != torch.int32 or key_lens.device != device or key_lens.dim() != 1
+            or key_lens.numel() != B or not key_lens.is_contiguous()):
+        raise GtaError(f"key_lens must be a contiguous int32 tensor of shape ({B},) on {device}")
+
+
+def _fwd_call(entry: str, desc: GtaAttnDesc, qkv, tables, out, lse, workspace, key_lens=None):
+    """The four forward entries: ``tables`` are the float operands between v and out in the entry's order; the *_varlen entries take
+    ``key_lens`` ([B] int32 on the device) in front of out."""
+    _require_cuda(*qkv, out, workspace, key_lens)
+    lens = ()
+    if entry.endswith("_varlen"):
+        _check_key_lens(key_lens, desc.B, workspace.device)
+        lens = (_ptr(key_lens),)
+    check(getattr(lib(), entry)(ctypes.byref(desc), *map(_ptr, qkv), *map(_ptr, tables), *lens, _ptr(out), _ptr(lse), _ptr(workspace),
+                                0 if workspace is None else workspace.numel(), _stream()), entry)
+
+
 def attn_fwd(desc: GtaAttnDesc, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, out, lse,
              workspace: Optional[torch.Tensor] = None):
     """workspace: uint8 CUDA tensor of >= attn_fwd_workspace_bytes(desc) bytes selects the two-stage
     plan (K/V pre-pass + lean attention kernel); None selects the single fused kernel."""
-    _require_cuda(q, k, v, out, workspace)
-    check(lib().gta_attn_fwd(ctypes.byref(desc), _ptr(q), _ptr(k), _ptr(v), _ptr(vrep_q), _ptr(vrep_k),
-                             _ptr(cs_q), _ptr(cs_k), _ptr(trans_coeff), _ptr(tau), _ptr(out), _ptr(lse),
-                             _ptr(workspace), 0 if workspace is None else workspace.numel(), _stream()),
-          "gta_attn_fwd")
+    _fwd_call("gta_attn_fwd", desc, (q, k, v), (vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau), out, lse, workspace)
+
+
+def attn_fwd_varlen(desc: GtaAttnDesc, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, key_lens, out, lse, workspace: torch.Tensor):
+    """``attn_fwd`` on the two-stage plan with scene b attending over its first key_lens[b] key tokens ([B] int32 on the device);
+    workspace: uint8 CUDA tensor of >= attn_fwd_workspace_bytes(desc) bytes (sized by Tk, not by the prefixes)."""
+    _fwd_call("gta_attn_fwd_varlen", desc, (q, k, v), (vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau), out, lse, workspace, key_lens)
+
+
+def attn_fwd_staged(desc: GtaAttnDesc, q, k, v, vrep_q, vrep_k, cs_q, cs_k, coord_q, coord_k, trans_coeff, tau, out, lse,
+                    workspace: torch.Tensor):
+    """K/V pre-pass (skipped under FLAG_KV_READY) + attention kernel of the staged generic forward; workspace: uint8 CUDA tensor of
+    >= attn_fwd_staged_workspace_bytes(desc) bytes holding the K'/V' tile images (+ the euclid key bias)."""
+    _fwd_call("gta_attn_fwd_staged", desc, (q, k, v), (vrep_q, vrep_k, cs_q, cs_k, coord_q, coord_k, trans_coeff, tau), out, lse, workspace)
+
+
+def attn_fwd_staged_varlen(desc: GtaAttnDesc, q, k, v, vrep_q, vrep_k, cs_q, cs_k, coord_q, coord_k, trans_coeff, tau, key_lens, out, lse,
+                           workspace: torch.Tensor):
+    """``attn_fwd_staged`` with per-scene key prefixes (see ``attn_fwd_varlen``)."""
+    _fwd_call("gta_attn_fwd_staged_varlen", desc, (q, k, v), (vrep_q, vrep_k, cs_q, cs_k, coord_q, coord_k, trans_coeff, tau), out, lse,
+              workspace, key_lens)
 
 
 def attn_fwd_workspace_bytes(desc: GtaAttnDesc) -> int:
     return int(lib().gta_attn_fwd_workspace_bytes(ctypes.byref(desc)))
+
+
+def attn_fwd_staged_workspace_bytes(desc: GtaAttnDesc) -> int:
+    return int(lib().gta_attn_fwd_staged_workspace_bytes(ctypes.byref(desc)))
 
 
 def attn_fwd_supported(desc: GtaAttnDesc) -> int:
@@ -323,26 +368,6 @@ def attn_fwd_staged_supported(desc: GtaAttnDesc) -> int:
     return lib().gta_attn_fwd_staged_supported(ctypes.byref(desc))
 
 
-def attn_fwd_staged_workspace_bytes(desc: GtaAttnDesc) -> int:
-    return int(lib().gta_attn_fwd_staged_workspace_bytes(ctypes.byref(desc)))
-
-
-def attn_fwd_staged(desc: GtaAttnDesc, q, k, v, vrep_q, vrep_k, cs_q, cs_k, coord_q, coord_k, trans_coeff, tau, out, lse,
-                    workspace: torch.Tensor):
-    """K/V pre-pass (skipped under FLAG_KV_READY) + attention kernel of the staged generic forward; workspace: uint8 CUDA tensor of
-    >= attn_fwd_staged_workspace_bytes(desc) bytes holding the K'/V' tile images (+ the euclid key bias)."""
-    _require_cuda(q, k, v, out, workspace)
-    check(lib().gta_attn_fwd_staged(ctypes.byref(desc), _ptr(q), _ptr(k), _ptr(v), _ptr(vrep_q), _ptr(vrep_k), _ptr(cs_q), _ptr(cs_k),
-                                    _ptr(coord_q), _ptr(coord_k), _ptr(trans_coeff), _ptr(tau), _ptr(out), _ptr(lse),
-                                    _ptr(workspace), workspace.numel(), _stream()), "gta_attn_fwd_staged")
-
-
-def _check_key_lens(key_lens, B: int, device):
-    if (not torch.is_tensor(key_lens) or key_lens.dtype != torch.int32 or key_lens.device != device or key_lens.dim() != 1
-            or key_lens.numel() != B or not key_lens.is_contiguous()):
-        raise GtaError(f"key_lens must be a contiguous int32 tensor of shape ({B},) on {device}")
-
-
 def attn_fwd_varlen_supported(desc: GtaAttnDesc) -> int:
     """0 when gta_attn_fwd_varlen (per-scene key prefixes on the two-stage plan) serves desc, else a GTA_E_* code; needs no GPU"""
     return lib().gta_attn_fwd_varlen_supported(ctypes.byref(desc))
@@ -352,25 +377,18 @@ def attn_fwd_staged_varlen_supported(desc: GtaAttnDesc) -> int:
     return lib().gta_attn_fwd_staged_varlen_supported(ctypes.byref(desc))
 
 
-def attn_fwd_varlen(desc: GtaAttnDesc, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, key_lens, out, lse, workspace: torch.Tensor):
-    """``attn_fwd`` on the two-stage plan with scene b attending over its first key_lens[b] key tokens ([B] int32 on the device);
-    workspace: uint8 CUDA tensor of >= attn_fwd_workspace_bytes(desc) bytes (sized by Tk, not by the prefixes)."""
-    _require_cuda(q, k, v, out, workspace, key_lens)
-    _check_key_lens(key_lens, desc.B, workspace.device)
-    check(lib().gta_attn_fwd_varlen(ctypes.byref(desc), _ptr(q), _ptr(k), _ptr(v), _ptr(vrep_q), _ptr(vrep_k), _ptr(cs_q), _ptr(cs_k),
-                                    _ptr(trans_coeff), _ptr(tau), _ptr(key_lens), _ptr(out), _ptr(lse),
-                                    _ptr(workspace), workspace.numel(), _stream()), "gta_attn_fwd_varlen")
-
-
-def attn_fwd_staged_varlen(desc: GtaAttnDesc, q, k, v, vrep_q, vrep_k, cs_q, cs_k, coord_q, coord_k, trans_coeff, tau, key_lens, out, lse,
-                           workspace: torch.Tensor):
-    """``attn_fwd_staged`` with per-scene key prefixes (see ``attn_fwd_varlen``)."""
-    _require_cuda(q, k, v, out, workspace, key_lens)
-    _check_key_lens(key_lens, desc.B, workspace.device)
-    check(lib().gta_attn_fwd_staged_varlen(ctypes.byref(desc), _ptr(q), _ptr(k), _ptr(v), _ptr(vrep_q), _ptr(vrep_k), _ptr(cs_q),
-                                           _ptr(cs_k), _ptr(coord_q), _ptr(coord_k), _ptr(trans_coeff), _ptr(tau), _ptr(key_lens),
-                                           _ptr(out), _ptr(lse), _ptr(workspace), workspace.numel(), _stream()),
-          "gta_attn_fwd_staged_varlen")
+def forward_family(desc: GtaAttnDesc, varlen: bool = False):
+    """Which forward entry a ``ForwardPlan`` calls for desc (with per-scene key prefixes under ``varlen``) -> (family, rc, name): 'fused'
+    (gta_attn_fwd*) or, for the layouts without a fused kernel (t2 slab, euclid, so3 of degree 1, unaligned slabs), 'staged'
+    (gta_attn_fwd_staged*); rc is 0 or that family's refusal, name the *_supported entry that spoke last.  Needs no GPU."""
+    rc, name = attn_fwd_supported(desc), "gta_attn_fwd_supported"
+    if rc == E_UNSUPPORTED:
+        name = "gta_attn_fwd_staged_varlen_supported" if varlen else "gta_attn_fwd_staged_supported"
+        return "staged", getattr(lib(), name)(ctypes.byref(desc)), name
+    if rc == 0 and varlen:
+        # a fused layout: what the varlen entry refuses is a flag (GTA_FLAG_FUSED_KV, GTA_FLAG_FP32_PRODUCTS, GTA_FLAG_PRETRANSFORMED)
+        rc, name = attn_fwd_varlen_supported(desc), "gta_attn_fwd_varlen_supported"
+    return "fused", rc, name
 
 
 def launch_info(desc: GtaAttnDesc):
@@ -384,16 +402,21 @@ def attn_bwd_workspace_bytes(desc: GtaAttnDesc) -> int:
     return int(lib().gta_attn_bwd_workspace_bytes(ctypes.byref(desc)))
 
 
+def _bwd_call(entry: str, desc: GtaAttnDesc, q, k, v, out, dout, lse, tables, lens, kv_images, dq, dk, dv, dtrans_coeff, workspace, dtau):
+    """Both backward entries: ``lens`` is () or (key_lens, q_lens) -- [B] int32 on the device, q_lens may be None."""
+    _require_cuda(q, k, v, out, dout, dq, dk, dv, workspace, *lens)
+    for t in lens[:1] + tuple(t for t in lens[1:] if t is not None):
+        _check_key_lens(t, desc.B, workspace.device)
+    check(getattr(lib(), entry)(ctypes.byref(desc), *map(_ptr, (q, k, v, out, dout, lse)), *map(_ptr, tables), *map(_ptr, lens),
+                                _ptr(kv_images), _ptr(dq), _ptr(dk), _ptr(dv), _strides(dq, dk, dv), _strides(dout),
+                                _ptr(dtrans_coeff), _ptr(dtau), _ptr(workspace), workspace.numel(), _stream()), entry)
+
+
 def attn_bwd(desc: GtaAttnDesc, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, kv_images,
              dq, dk, dv, dtrans_coeff, workspace, dtau=None):
     """All tensors [B,H,T,dh] views (unit channel stride); dq/dk/dv/dout strides are passed explicitly."""
-    _require_cuda(q, k, v, out, dout, dq, dk, dv, workspace)
-    gs = (c_int64 * 9)(*(list(dq.stride()[:3]) + list(dk.stride()[:3]) + list(dv.stride()[:3])))
-    ds = (c_int64 * 3)(*dout.stride()[:3])
-    check(lib().gta_attn_bwd(ctypes.byref(desc), _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(dout), _ptr(lse),
-                             _ptr(vrep_q), _ptr(vrep_k), _ptr(cs_q), _ptr(cs_k), _ptr(trans_coeff), _ptr(tau),
-                             _ptr(kv_images), _ptr(dq), _ptr(dk), _ptr(dv), gs, ds, _ptr(dtrans_coeff), _ptr(dtau),
-                             _ptr(workspace), workspace.numel(), _stream()), "gta_attn_bwd")
+    _bwd_call("gta_attn_bwd", desc, q, k, v, out, dout, lse, (vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau), (), kv_images,
+              dq, dk, dv, dtrans_coeff, workspace, dtau)
 
 
 def attn_bwd_varlen_supported(desc: GtaAttnDesc) -> int:
@@ -405,35 +428,23 @@ def attn_bwd_varlen(desc: GtaAttnDesc, q, k, v, out, dout, lse, vrep_q, vrep_k, 
                     dq, dk, dv, dtrans_coeff, workspace, dtau=None):
     """``attn_bwd`` with scene b's keys cut to key_lens[b] tokens and (q_lens, or None) its query rows to q_lens[b]: [B] int32 on the device.
     kv_images: the workspace of ``attn_fwd_varlen`` under the same key_lens, or None."""
-    _require_cuda(q, k, v, out, dout, dq, dk, dv, workspace, key_lens, q_lens)
-    _check_key_lens(key_lens, desc.B, workspace.device)
-    if q_lens is not None:
-        _check_key_lens(q_lens, desc.B, workspace.device)
-    gs = (c_int64 * 9)(*(list(dq.stride()[:3]) + list(dk.stride()[:3]) + list(dv.stride()[:3])))
-    ds = (c_int64 * 3)(*dout.stride()[:3])
-    check(lib().gta_attn_bwd_varlen(ctypes.byref(desc), _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(dout), _ptr(lse),
-                                    _ptr(vrep_q), _ptr(vrep_k), _ptr(cs_q), _ptr(cs_k), _ptr(trans_coeff), _ptr(tau),
-                                    _ptr(key_lens), _ptr(q_lens), _ptr(kv_images), _ptr(dq), _ptr(dk), _ptr(dv), gs, ds,
-                                    _ptr(dtrans_coeff), _ptr(dtau), _ptr(workspace), workspace.numel(), _stream()), "gta_attn_bwd_varlen")
+    _bwd_call("gta_attn_bwd_varlen", desc, q, k, v, out, dout, lse, (vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau), (key_lens, q_lens),
+              kv_images, dq, dk, dv, dtrans_coeff, workspace, dtau)
 
 
 def attn_bwd_plain_f32(desc: GtaAttnDesc, q, k, v, out, dout, lse, tau, dq, dk, dv):
     """exact-fp32 backward of plain attention on pre-transformed float32 tensors (include/gta_hip.h: gta_attn_bwd_plain_f32)"""
     _require_cuda(q, k, v, out, dout, dq, dk, dv)
-    gs = (c_int64 * 9)(*(list(dq.stride()[:3]) + list(dk.stride()[:3]) + list(dv.stride()[:3])))
-    ds = (c_int64 * 3)(*dout.stride()[:3])
     ws = torch.empty(int(lib().gta_attn_bwd_plain_f32_workspace_bytes(ctypes.byref(desc))), device=q.device, dtype=torch.uint8)
-    check(lib().gta_attn_bwd_plain_f32(ctypes.byref(desc), _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(dout), ds, _ptr(lse), _ptr(tau),
-                                       _ptr(dq), _ptr(dk), _ptr(dv), gs, _ptr(ws), ws.numel(), _stream()), "gta_attn_bwd_plain_f32")
+    check(lib().gta_attn_bwd_plain_f32(ctypes.byref(desc), _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(dout), _strides(dout), _ptr(lse),
+                                       _ptr(tau), _ptr(dq), _ptr(dk), _ptr(dv), _strides(dq, dk, dv), _ptr(ws), ws.numel(), _stream()), "gta_attn_bwd_plain_f32")
 
 
 def rep_apply(desc: GtaAttnDesc, mode: int, x, vrep, cs, coord, trans_coeff, y, key_bias=None, bias_scale=0.0):
     """Generic rho application (any layout / t2 / euclid): x, y are [B,H,T,dh] views."""
     _require_cuda(x, y)
-    xs = (c_int64 * 3)(*x.stride()[:3])
-    ys = (c_int64 * 3)(*y.stride()[:3])
-    check(lib().gta_rep_apply(ctypes.byref(desc), int(mode), _ptr(x), xs, _ptr(vrep), _ptr(cs), _ptr(coord),
-                              _ptr(trans_coeff), _ptr(y), ys, _ptr(key_bias), float(bias_scale),
+    check(lib().gta_rep_apply(ctypes.byref(desc), int(mode), _ptr(x), _strides(x), _ptr(vrep), _ptr(cs), _ptr(coord),
+                              _ptr(trans_coeff), _ptr(y), _strides(y), _ptr(key_bias), float(bias_scale),
                               0 if key_bias is None else key_bias.shape[-1], _stream()), "gta_rep_apply")
 
 
@@ -441,12 +452,9 @@ def rep_apply_bwd(desc: GtaAttnDesc, mode: int, x, dy, vrep, cs, coord, trans_co
                   bias_scale=0.0):
     """Adjoint of rep_apply(mode): dx = M^T dy; dtc_rows [B,H,T] receives per-row d trans_coeff terms."""
     _require_cuda(x, dy, dx)
-    xs = (c_int64 * 3)(*x.stride()[:3])
-    ys = (c_int64 * 3)(*dy.stride()[:3])
-    ds = (c_int64 * 3)(*dx.stride()[:3])
-    check(lib().gta_rep_apply_bwd(ctypes.byref(desc), int(mode), _ptr(x), xs, _ptr(dy), ys, _ptr(vrep), _ptr(cs),
+    check(lib().gta_rep_apply_bwd(ctypes.byref(desc), int(mode), _ptr(x), _strides(x), _ptr(dy), _strides(dy), _ptr(vrep), _ptr(cs),
                                   _ptr(coord), _ptr(trans_coeff), _ptr(dkey_bias), float(bias_scale),
-                                  0 if dkey_bias is None else dkey_bias.shape[-1], _ptr(dx), ds, _ptr(dtc_rows),
+                                  0 if dkey_bias is None else dkey_bias.shape[-1], _ptr(dx), _strides(dx), _ptr(dtc_rows),
                                   _stream()), "gta_rep_apply_bwd")
 
 
@@ -482,7 +490,7 @@ def rep_grad_sums(desc: GtaAttnDesc, side: int, pairs, view: bool = False, so2: 
     args = []
     for i in range(2):
         for t in (pairs[i] if i < len(pairs) else (None, None)):
-            args += [_ptr(t), None if t is None else (c_int64 * 3)(*t.stride()[:3])]
+            args += [_ptr(t), None if t is None else _strides(t)]
     check(lib().gta_rep_grad_sums(ctypes.byref(desc), int(side), len(pairs), *args, _ptr(vo), _ptr(so), _ptr(to), _ptr(ws),
                                   0 if ws is None else ws.numel(), _stream()), "gta_rep_grad_sums")
     return vo, so, to

@@ -70,25 +70,20 @@ class ForwardPlan:
         fl = flags | (native.FLAG_V_TRANSFORM if v_transform else 0) | (native.FLAG_EUCLID if euclid else 0)
         self.desc = native.make_desc(q, k, v, self.out, f_dims, so3_degree, Nq, Nk,
                                      float(scale if scale is not None else dh ** -0.5), fl)
-        rc = native.attn_fwd_supported(self.desc)
-        if rc == 0 and self.key_views is not None:
-            # a fused layout: what the varlen entry refuses is a flag (GTA_FLAG_FUSED_KV, GTA_FLAG_FP32_PRODUCTS, GTA_FLAG_PRETRANSFORMED) -- that
-            # raises with its reason; only a layout without a fused kernel goes on to the staged entry
-            native.check(native.attn_fwd_varlen_supported(self.desc), "gta_attn_fwd_varlen_supported")
-        # layouts without a fused kernel (t2 slab, euclid, so3 of degree 1, unaligned slabs): the staged generic forward, where it serves them
-        staged_supported = native.attn_fwd_staged_supported if self.key_views is None else native.attn_fwd_staged_varlen_supported
-        rc_staged = staged_supported(self.desc) if rc == -3 else rc
-        self._staged = rc == -3 and rc_staged == 0
-        if rc == -3 and rc_staged:                    # both entries refuse: the staged one spoke last, its reason is the library's message
-            native.check(rc_staged, "gta_attn_fwd_staged_supported" if self.key_views is None else "gta_attn_fwd_staged_varlen_supported")
-        elif rc and not self._staged:
-            native.check(rc, "gta_attn_fwd_supported")
+        family, rc, name = native.forward_family(self.desc, varlen=self.key_views is not None)
+        native.check(rc, name)                # (a layout without a fused kernel that the staged entry refuses too: the staged one spoke last)
+        self._staged = family == "staged"
         if self.key_views is not None:
             self.key_lens = key_lens_tensor(self.key_views, k.shape[2] // Nk, q.device)
         self.ws = torch.empty(native.attn_fwd_staged_workspace_bytes(self.desc) if self._staged else native.attn_fwd_workspace_bytes(self.desc),
                               device=q.device, dtype=torch.uint8)
+        # the entry every call goes through, resolved once: its name (gta_attn_fwd[_staged][_varlen]), the bound function, whether the coordinate
+        # tables are among its arguments, and the arguments that never change (key_lens where it takes them; the plan's own buffers)
+        self._entry = "gta_attn_fwd" + ("_staged" if self._staged else "") + ("_varlen" if self.key_lens is not None else "")
+        self._fn = getattr(native.lib(), self._entry)
+        p = native._ptr
+        self._tail = (() if self.key_lens is None else (p(self.key_lens),)) + (p(self.out), p(self.lse), p(self.ws), self.ws.numel())
         self._sig = (tuple(q.shape), tuple(q.stride()), tuple(k.shape), tuple(k.stride()), tuple(v.stride()), q.dtype)
-        self._lib = native.lib()
         self._need_view = f_dims.get("se3", 0) > 0 or f_dims.get("so3", 0) > 0
         self._need_cs = f_dims.get("so2", 0) > 0
         self._need_coord = f_dims.get("t2", 0) > 0
@@ -120,24 +115,10 @@ class ForwardPlan:
         base = d.flags
         if flags_extra:
             d.flags = base | flags_extra
+        coords = (p(coord_q), p(coord_k)) if self._staged else ()
         try:
-            if self.key_lens is not None and self._staged:
-                native.check(self._lib.gta_attn_fwd_staged_varlen(ctypes.byref(d), p(q), p(k), p(v), p(vrep_q), p(vrep_k), p(cs_q), p(cs_k),
-                                                                  p(coord_q), p(coord_k), p(trans_coeff), p(tau), p(self.key_lens),
-                                                                  p(self.out), p(self.lse), p(self.ws), self.ws.numel(), native._stream()),
-                             "gta_attn_fwd_staged_varlen")
-            elif self.key_lens is not None:
-                native.check(self._lib.gta_attn_fwd_varlen(ctypes.byref(d), p(q), p(k), p(v), p(vrep_q), p(vrep_k), p(cs_q), p(cs_k),
-                                                           p(trans_coeff), p(tau), p(self.key_lens), p(self.out), p(self.lse), p(self.ws),
-                                                           self.ws.numel(), native._stream()), "gta_attn_fwd_varlen")
-            elif self._staged:
-                native.check(self._lib.gta_attn_fwd_staged(ctypes.byref(d), p(q), p(k), p(v), p(vrep_q), p(vrep_k), p(cs_q), p(cs_k),
-                                                           p(coord_q), p(coord_k), p(trans_coeff), p(tau), p(self.out), p(self.lse),
-                                                           p(self.ws), self.ws.numel(), native._stream()), "gta_attn_fwd_staged")
-            else:
-                native.check(self._lib.gta_attn_fwd(ctypes.byref(d), p(q), p(k), p(v), p(vrep_q), p(vrep_k), p(cs_q), p(cs_k),
-                                                    p(trans_coeff), p(tau), p(self.out), p(self.lse), p(self.ws),
-                                                    self.ws.numel(), native._stream()), "gta_attn_fwd")
+            native.check(self._fn(ctypes.byref(d), p(q), p(k), p(v), p(vrep_q), p(vrep_k), p(cs_q), p(cs_k), *coords, p(trans_coeff), p(tau),
+                                  *self._tail, native._stream()), self._entry)
         finally:
             d.flags = base
         return self.out

@@ -4,8 +4,8 @@
 
 Compiles every kernel source of gta_amd/csrc in both trees to gfx950 assembly with the Makefile's flags and compares, function by function,
 the instruction streams (comments, directives and the numbering of local labels dropped; other symbols replaced by a placeholder).  A
-function is matched by its demangled name; a trailing `false` of the templates that gained a defaulted VARLEN argument is ignored, their
-`true` instances are counted as new.  Exit status 1 when a function of OLD_TREE is missing from NEW_TREE or differs.  Needs hipcc and c++filt."""
+function is matched by its demangled name; against an OLD_TREE from before the templates gained their defaulted VARLEN argument, a trailing
+`false` of those is ignored and their `true` instances are counted as new.  Exit status 1 when a function of OLD_TREE is missing from NEW_TREE or differs.  Needs hipcc and c++filt."""
 import os
 import re
 import subprocess
@@ -65,9 +65,10 @@ def main():
         for s in SOURCES:
             old = functions(jobs[("old", s)].result())
             new_all = functions(jobs[("new", s)].result())
-            new_fns = {canonical(k): v for k, v in new_all.items() if canonical(k) is not None}
+            # (the old tree's names are taken as they are; a name of the new tree that the old tree has too -- it has the extra argument as well -- is its own key)
+            new_fns = {(k if k in old else canonical(k)): v for k, v in new_all.items() if k in old or canonical(k) is not None}
             new += len(new_all) - len(new_fns) + sum(1 for k in new_fns if k not in old)
-            for name, body in old.items():              # (the old tree's names are taken as they are: only the new tree has the extra argument)
+            for name, body in old.items():
                 total += 1
                 key = name
                 if key not in new_fns:
