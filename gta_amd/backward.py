@@ -37,9 +37,11 @@ def _grad_buffers(q, k, v):
     return dq, new(Tk, 1)[:, :, 0].permute(0, 2, 1, 3), new(Tk, 1)[:, :, 0].permute(0, 2, 1, 3)
 
 
-def attn_bwd(cfg, q, k, v, out, dout, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k, kv_images=None, want_dtau=False, key_lens=None, q_lens=None):
+def attn_bwd(cfg, q, k, v, out, dout, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k, kv_images=None, want_dtau=False, key_lens=None, q_lens=None,
+             dlse=None):
     """Returns (dq, dk, dv, dtrans_coeff or None, dtau or None); dtau ([1] fp32) only with ``want_dtau``.
-    key_lens (with q_lens or None): ``gta_attn_bwd_varlen`` -- per-scene prefixes, kv_images those of ``attn_fwd_varlen`` under the same key_lens."""
+    key_lens (with q_lens or None): ``gta_attn_bwd_varlen`` -- per-scene prefixes, kv_images those of ``attn_fwd_varlen`` under the same key_lens.
+    dlse ([B,H,Tq], the gradient of the forward's lse; not with key_lens): ``gta_attn_bwd_dlse`` -- the backward of the pair (out, lse)."""
     f_dims, so3_degree, Nq, Nk, scale, flags = cfg
     flags = flags & ~(native.FLAG_FUSED_KV | native.FLAG_KV_READY | native.FLAG_PREP_ONLY | native.FLAG_PERSIST)      # (GTA_FLAG_FP32_PRODUCTS stays: the X3 walks)
     dt = q.dtype
@@ -55,7 +57,12 @@ def attn_bwd(cfg, q, k, v, out, dout, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k, k
     desc = native.make_desc(q, k, v, out, f_dims, so3_degree, Nq, Nk, scale, flags)
     ws = torch.empty(native.attn_bwd_workspace_bytes(desc), device=q.device, dtype=torch.uint8)
     dta = torch.empty(1, device=q.device, dtype=torch.float32) if (want_dtau and ta is not None) else None
-    if key_lens is not None:
+    if dlse is not None:
+        if key_lens is not None:
+            raise native.GtaError("return_lse: gta_attn_bwd_varlen takes no gradient of the log-sum-exp")
+        native.attn_bwd_dlse(desc, q, k, v, out, dout, lse, dlse.to(torch.float32).contiguous(), vrep_q, vrep_k, cs_q, cs_k, tc, ta, kv_images,
+                             dq, dk, dv, dtc, ws, dta)
+    elif key_lens is not None:
         native.attn_bwd_varlen(desc, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, tc, ta, key_lens, q_lens, kv_images, dq, dk, dv, dtc, ws, dta)
     else:
         native.attn_bwd(desc, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, tc, ta, kv_images, dq, dk, dv, dtc, ws, dta)

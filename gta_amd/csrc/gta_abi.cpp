@@ -9,6 +9,7 @@
 #include "gta_bwd_params.h"
 #include "gta_repgrad_params.h"
 #include "gta_gen_params.h"
+#include "gta_merge_params.h"
 
 // chunk-descriptor constants (mirrors gta_common.h, which is device-only)
 #define HALF_ID 0u
@@ -23,7 +24,9 @@ long gta_fwd2_qtiles_offset(int B, int H, int Tk, int dhp, bool x3);
 long gta_fwd2_image_bytes(int B, int H, int Tk, int dhp, bool x3);
 int gta_fwd2_lds_bytes(int dhp, int nq);
 int gta_fwd2_dispatch(GtaFwdParams& p, const GtaFwdSel& s, int dhp, int esz, bool run_prep, bool run_flash, hipStream_t stream);
-int gta_bwd_dispatch(const GtaBwdParams& p, int dhp, int esz, hipStream_t stream);
+int gta_bwd_dispatch(const GtaBwdParams& p, const float* dlse, int dhp, int esz, hipStream_t stream);
+int gta_merge_dispatch(const GtaMergeParams& p, int esz, hipStream_t stream);
+int gta_merge_bwd_dispatch(const GtaMergeBwdParams& p, int esz, hipStream_t stream);
 int gta_bwd_varlen_dispatch(const GtaBwdParams& p, const int32_t* key_lens, const int32_t* q_lens, int dhp, int esz, hipStream_t stream);
 
 namespace {
@@ -419,11 +422,20 @@ extern "C" int64_t gta_attn_bwd_workspace_bytes(const GtaAttnDesc* desc) {
 }
 
 namespace {
-// both backward entries.  varlen (gta_attn_bwd_varlen) is the explicit selector of the VARLEN instances -- never "key_lens is non-null"
+// what no backward entry serves, whatever the layout (gta_attn_bwd_dlse_supported asks before a launch; bwd_call at one)
+int bwd_flags(const GtaAttnDesc* d) {
+    if (d->flags & GTA_FLAG_PRETRANSFORMED) return fail(GTA_E_UNSUPPORTED, "backward of the pretransformed mode");
+    if ((d->flags & GTA_FLAG_FP32_PRODUCTS) && !gta_x3_takes(padded_dh(d->dh), esz_of(d)))
+        return fail(GTA_E_UNSUPPORTED, "GTA_FLAG_FP32_PRODUCTS backward: fp32 inputs at dh <= 64 (other sizes: gta_rep_apply + gta_attn_bwd_plain_f32)");
+    return GTA_OK;
+}
+
+// the three backward entries.  varlen (gta_attn_bwd_varlen) is the explicit selector of the VARLEN instances -- never "key_lens is non-null";
+// with_dlse (gta_attn_bwd_dlse) likewise selects the instances that read dlse
 int bwd_call(const GtaAttnDesc* d, const void* q, const void* k, const void* v, const void* out,
              const void* dout, const float* lse, const float* vrep_q, const float* vrep_k,
              const float* cs_q, const float* cs_k, const float* trans_coeff, const float* tau,
-             bool varlen, const int32_t* key_lens, const int32_t* q_lens,
+             bool varlen, const int32_t* key_lens, const int32_t* q_lens, bool with_dlse, const float* dlse,
              const void* kv_images, void* dq, void* dk, void* dv, const int64_t* dqkv_stride,
              const int64_t* dout_stride, float* dtrans_coeff, float* dtau, void* workspace,
              int64_t workspace_bytes, void* stream) {
@@ -435,10 +447,9 @@ int bwd_call(const GtaAttnDesc* d, const void* q, const void* k, const void* v, 
     }
     if (!q || !k || !v || !out || !dout || !lse || !dq || !dk || !dv || !dqkv_stride || !dout_stride || !workspace)
         return fail(GTA_E_BADARG, "null argument");
-    if (d->flags & GTA_FLAG_PRETRANSFORMED) return fail(GTA_E_UNSUPPORTED, "backward of the pretransformed mode");
+    if (with_dlse && !dlse) return fail(GTA_E_BADARG, "null dlse");
+    if ((rc = bwd_flags(d))) return rc;
     const int dhp = padded_dh(d->dh), esz = esz_of(d);
-    if ((d->flags & GTA_FLAG_FP32_PRODUCTS) && !gta_x3_takes(dhp, esz))
-        return fail(GTA_E_UNSUPPORTED, "GTA_FLAG_FP32_PRODUCTS backward: fp32 inputs at dh <= 64 (other sizes: gta_rep_apply + gta_attn_bwd_plain_f32)");
     GtaBwdParams p;
     memset(&p, 0, sizeof p);
     rc = build_ctab(d, p.ctab);
@@ -482,7 +493,7 @@ int bwd_call(const GtaAttnDesc* d, const void* q, const void* k, const void* v, 
     p.dh = d->dh; p.nso2 = d->d_so2 / 2; p.flags = d->flags; p.scale = d->scale;
     if (d->H > 65535 || d->B > 65535) return fail(GTA_E_UNSUPPORTED, "B or H above 65535");
     return launch_status(varlen ? gta_bwd_varlen_dispatch(p, key_lens, q_lens, dhp, esz, (hipStream_t)stream)
-                                : gta_bwd_dispatch(p, dhp, esz, (hipStream_t)stream), "no kernel instance");
+                                : gta_bwd_dispatch(p, with_dlse ? dlse : nullptr, dhp, esz, (hipStream_t)stream), "no kernel instance");
 }
 }  // namespace
 
@@ -493,7 +504,23 @@ extern "C" int gta_attn_bwd(const GtaAttnDesc* d, const void* q, const void* k, 
                             const int64_t* dout_stride, float* dtrans_coeff, float* dtau, void* workspace,
                             int64_t workspace_bytes,
                             void* stream) {
-    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, false, nullptr, nullptr, kv_images, dq, dk, dv,
+    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, false, nullptr, nullptr, false, nullptr, kv_images, dq, dk, dv,
+                    dqkv_stride, dout_stride, dtrans_coeff, dtau, workspace, workspace_bytes, stream);
+}
+
+// Backward of the pair (out, lse): the DLSE instances of the q-side pre-pass (and of the X3 dQ walk's d tau), every other kernel as in gta_attn_bwd
+extern "C" int gta_attn_bwd_dlse_supported(const GtaAttnDesc* desc) {
+    if (int rc = gta_attn_fwd_supported(desc)) return rc;
+    return bwd_flags(desc);
+}
+
+extern "C" int gta_attn_bwd_dlse(const GtaAttnDesc* d, const void* q, const void* k, const void* v, const void* out,
+                                 const void* dout, const float* lse, const float* dlse, const float* vrep_q, const float* vrep_k,
+                                 const float* cs_q, const float* cs_k, const float* trans_coeff, const float* tau,
+                                 const void* kv_images, void* dq, void* dk, void* dv, const int64_t* dqkv_stride,
+                                 const int64_t* dout_stride, float* dtrans_coeff, float* dtau, void* workspace,
+                                 int64_t workspace_bytes, void* stream) {
+    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, false, nullptr, nullptr, true, dlse, kv_images, dq, dk, dv,
                     dqkv_stride, dout_stride, dtrans_coeff, dtau, workspace, workspace_bytes, stream);
 }
 
@@ -507,8 +534,77 @@ extern "C" int gta_attn_bwd_varlen(const GtaAttnDesc* d, const void* q, const vo
                                    const void* kv_images, void* dq, void* dk, void* dv, const int64_t* dqkv_stride,
                                    const int64_t* dout_stride, float* dtrans_coeff, float* dtau, void* workspace,
                                    int64_t workspace_bytes, void* stream) {
-    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, true, key_lens, q_lens, kv_images, dq, dk, dv,
+    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, true, key_lens, q_lens, false, nullptr, kv_images, dq, dk, dv,
                     dqkv_stride, dout_stride, dtrans_coeff, dtau, workspace, workspace_bytes, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// merge of partial attentions (gta_merge.hip)
+// ---------------------------------------------------------------------------------------------
+namespace {
+int merge_check(int32_t dtype, int32_t n, int32_t B, int32_t H, int32_t Tq, int32_t dh) {
+    if (dtype != GTA_DTYPE_F32 && dtype != GTA_DTYPE_BF16) return fail(GTA_E_BADARG, "bad dtype");
+    if (n < 1 || n > GTA_MERGE_MAX) return fail(GTA_E_BADARG, "a merge takes 1 to 8 partial attentions");
+    if (B <= 0 || H <= 0 || Tq <= 0 || dh <= 0) return fail(GTA_E_BADARG, "non-positive size");
+    if (dh % 8 || dh > 128) return fail(GTA_E_UNSUPPORTED, "the merge needs dh % 8 == 0 and dh <= 128");
+    return GTA_OK;
+}
+// a [B,H,Tq,dh] operand the kernels move in 16-byte units: aligned base and (b, h, t) strides
+int merge_rows_ok(const void* ptr, const int64_t* st, int esz) {
+    if (!ptr) return fail(GTA_E_BADARG, "null argument");
+    if ((uintptr_t)ptr % 16) return fail(GTA_E_BADARG, "merge operands must be 16-byte aligned");
+    for (int i = 0; i < 3; ++i) if ((st[i] * esz) % 16) return fail(GTA_E_BADARG, "merge operand strides must keep rows 16-byte aligned");
+    return GTA_OK;
+}
+}  // namespace
+
+extern "C" int gta_attn_merge(int32_t dtype, int32_t n, int32_t B, int32_t H, int32_t Tq, int32_t dh,
+                              const void* const* outs, const int64_t* outs_stride, const float* const* lses, const int64_t* lses_stride,
+                              void* out, const int64_t* out_stride, float* lse, const int64_t* lse_stride, void* stream) {
+    if (int rc = merge_check(dtype, n, B, H, Tq, dh)) return rc;
+    if (!outs || !outs_stride || !lses || !lses_stride || !out_stride || !lse || !lse_stride) return fail(GTA_E_BADARG, "null argument");
+    const int esz = dtype == GTA_DTYPE_BF16 ? 2 : 4;
+    GtaMergeParams p;
+    memset(&p, 0, sizeof p);
+    for (int i = 0; i < n; ++i) {
+        if (int rc = merge_rows_ok(outs[i], outs_stride + 3 * i, esz)) return rc;
+        if (!lses[i]) return fail(GTA_E_BADARG, "null argument");
+        p.outs[i] = outs[i]; p.lses[i] = lses[i];
+        for (int j = 0; j < 3; ++j) { p.outs_st[i][j] = outs_stride[3 * i + j]; p.lses_st[i][j] = lses_stride[3 * i + j]; }
+    }
+    if (int rc = merge_rows_ok(out, out_stride, esz)) return rc;
+    p.out = out; p.lse = lse;
+    for (int j = 0; j < 3; ++j) { p.out_st[j] = out_stride[j]; p.lse_st[j] = lse_stride[j]; }
+    p.n = n; p.B = B; p.H = H; p.Tq = Tq; p.dh = dh;
+    return launch_status(gta_merge_dispatch(p, esz, (hipStream_t)stream), "no kernel instance");
+}
+
+extern "C" int gta_attn_merge_bwd(int32_t dtype, int32_t n, int32_t B, int32_t H, int32_t Tq, int32_t dh,
+                                  const void* const* outs, const int64_t* outs_stride, const float* const* lses, const int64_t* lses_stride,
+                                  const void* dout, const int64_t* dout_stride, const float* dlse, const int64_t* dlse_stride,
+                                  void* const* douts, const int64_t* douts_stride, float* const* dlses, const int64_t* dlses_stride,
+                                  void* stream) {
+    if (int rc = merge_check(dtype, n, B, H, Tq, dh)) return rc;
+    if (!outs || !outs_stride || !lses || !lses_stride || !dout_stride || !douts || !douts_stride || !dlses || !dlses_stride || (dlse && !dlse_stride))
+        return fail(GTA_E_BADARG, "null argument");
+    const int esz = dtype == GTA_DTYPE_BF16 ? 2 : 4;
+    GtaMergeBwdParams p;
+    memset(&p, 0, sizeof p);
+    for (int i = 0; i < n; ++i) {
+        if (int rc = merge_rows_ok(outs[i], outs_stride + 3 * i, esz)) return rc;
+        if (int rc = merge_rows_ok(douts[i], douts_stride + 3 * i, esz)) return rc;
+        if (!lses[i] || !dlses[i]) return fail(GTA_E_BADARG, "null argument");
+        p.outs[i] = outs[i]; p.lses[i] = lses[i]; p.douts[i] = douts[i]; p.dlses[i] = dlses[i];
+        for (int j = 0; j < 3; ++j) {
+            p.outs_st[i][j] = outs_stride[3 * i + j]; p.lses_st[i][j] = lses_stride[3 * i + j];
+            p.douts_st[i][j] = douts_stride[3 * i + j]; p.dlses_st[i][j] = dlses_stride[3 * i + j];
+        }
+    }
+    if (int rc = merge_rows_ok(dout, dout_stride, esz)) return rc;
+    p.dout = dout; p.dlse = dlse;
+    for (int j = 0; j < 3; ++j) { p.dout_st[j] = dout_stride[j]; p.dlse_st[j] = dlse ? dlse_stride[j] : 0; }
+    p.n = n; p.B = B; p.H = H; p.Tq = Tq; p.dh = dh;
+    return launch_status(gta_merge_bwd_dispatch(p, esz, (hipStream_t)stream), "no kernel instance");
 }
 
 

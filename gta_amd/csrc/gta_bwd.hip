@@ -222,12 +222,22 @@ struct BPrepSmem {
 // Tiles wholly past the prefix are still written (all zero): the dQ walk of a block that straddles the prefix reads its second tile.
 // The VARLEN instances alone take the trailing argument (LENS = const int32_t*: q_lens); without it LENS is empty and the kernel's signature
 // and argument block are what they were.
+// DLSE instances (gta_attn_bwd_dlse: the gradient of the pair (out, lse)): LENS = const float*, the row gradients dlse [B,H,Tq] of the
+// log-sum-exp.  dS_ij = P_ij (dP_ij - D_i + dlse_i), so these instances store -(D - dlse) where the others store -D and every walk stays as it
+// is; never combined with VARLEN.
 GTA_DEV const int32_t* first_len() { return nullptr; }
 GTA_DEV const int32_t* first_len(const int32_t* a) { return a; }
+GTA_DEV const int32_t* first_len(const float*) { return nullptr; }
+GTA_DEV const float* first_dlse() { return nullptr; }
+GTA_DEV const float* first_dlse(const int32_t*) { return nullptr; }
+GTA_DEV const float* first_dlse(const float* a) { return a; }
+template <class... LENS> struct LensIsDlse : std::false_type {};
+template <> struct LensIsDlse<const float*> : std::true_type {};
 template <int DHP, int ESZ, bool X3 = false, bool VARLEN = false, class... LENS>
 __global__ __launch_bounds__(256) void gta_bwd_prep_kernel(const GtaBwdParams p, LENS... lens) {
     static_assert(!(X3 && VARLEN), "no fp32-faithful VARLEN instances");
-    static_assert(sizeof...(LENS) == (VARLEN ? 1 : 0), "q_lens comes with VARLEN");
+    constexpr bool DLSE = LensIsDlse<LENS...>::value;
+    static_assert(sizeof...(LENS) == ((VARLEN || DLSE) ? 1 : 0) && !(VARLEN && DLSE), "q_lens comes with VARLEN, dlse without it");
     using S = BPrepSmem<DHP, ESZ, X3>;
     constexpr int CHP = DHP / 8, U = S::U, IMG = S::IMG;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -385,7 +395,12 @@ __global__ __launch_bounds__(256) void gta_bwd_prep_kernel(const GtaBwdParams p,
     if (tid < 64) {
         const int tt = j * BN + tid;
         st[tid] = tt < GTA_TQB ? -(p.lse[((long)b * p.H + h) * p.Tq + tt] * LOG2E) : -1e30f;
-        st[64 + tid] = tt < GTA_TQB ? -((dsum[tid] + dsum[64 + tid]) + (dsum[128 + tid] + dsum[192 + tid])) : 0.f;
+        if constexpr (DLSE) {
+            const float* dlse = first_dlse(lens...);
+            st[64 + tid] = tt < p.Tq ? -(((dsum[tid] + dsum[64 + tid]) + (dsum[128 + tid] + dsum[192 + tid])) - dlse[((long)b * p.H + h) * p.Tq + tt]) : 0.f;
+        } else {
+            st[64 + tid] = tt < GTA_TQB ? -((dsum[tid] + dsum[64 + tid]) + (dsum[128 + tid] + dsum[192 + tid])) : 0.f;
+        }
     }
     if (tid == 0) p.dc_partial[p.dc_off_prep + tile] = dc_wg;
 #undef GTA_TQB
@@ -1468,8 +1483,10 @@ struct DqX3Smem {
     static constexpr int total(int nviews) { return OFF_REC + nviews * BREC * 4; }
 };
 
-template <int DHP>
-GTA_DEV void bwd_dq_x3_body(const GtaBwdParams& p, char* smem, const int L, const int nwg) {
+// DLSE (gta_attn_bwd_dlse): dlse [B,H,Tq], the row gradients of the log-sum-exp, for the centred d tau of the epilogue alone -- the walk's
+// statistics already carry them (gta_bwd_prep_kernel)
+template <int DHP, bool DLSE = false>
+GTA_DEV void bwd_dq_x3_body(const GtaBwdParams& p, char* smem, const int L, const int nwg, const float* dlse = nullptr) {
     using S = DqX3Smem<DHP>;
     constexpr int CHP = S::CHP, KS = DHP / 16, DB = DHP / 32, BM = 128, ESZ = 4, IMG = S::IMG;
     constexpr int ITEMS = 2 * CHP / 4;
@@ -1645,7 +1662,16 @@ GTA_DEV void bwd_dq_x3_body(const GtaBwdParams& p, char* smem, const int L, cons
     float dcpart = 0.f, dtpart = 0.f;
     if (want_dtau) {
         const float tBf = tB + __shfl_xor(tB, 32), tCf = tC + __shfl_xor(tC, 32), tAf = tA + __shfl_xor(tA, 32);
-        if (lh == 0 && q0 + my_row < p.Tq) dtpart = LN2 * (tAf - tBf * tCf);
+        if constexpr (DLSE) {
+            // with a gradient through lse the row sum of dS is dlse_i, not 0: the common-mode error is tB - dlse_i, and the uncentred sum
+            // sum_j dS_ij S2_ij = tA + lse2_i dlse_i keeps its second term (lse2_i = -lse2n, log2 units)
+            if (lh == 0 && q0 + my_row < p.Tq) {
+                const float g = dlse[((long)b * p.H + h) * p.Tq + q0 + my_row];
+                dtpart = LN2 * (tAf - (tBf - g) * tCf - lse2n * g);
+            }
+        } else {
+            if (lh == 0 && q0 + my_row < p.Tq) dtpart = LN2 * (tAf - tBf * tCf);
+        }
     }
 #pragma unroll
     for (int it = 0; it < ITEMS; ++it) {
@@ -1918,22 +1944,35 @@ __global__ __launch_bounds__(256, 2) void gta_bwd_dqkv_x3_kernel(const GtaBwdPar
     if (L < n_dkv) bwd_dkv_x3_body<DHP>(p, smem, L, n_dkv);
     else bwd_dq_x3_body<DHP>(p, smem, L - n_dkv, n_dq);
 }
+// the same launch for gta_attn_bwd_dlse: the dQ share reads dlse for its d tau
+template <int DHP>
+__global__ __launch_bounds__(256, 2) void gta_bwd_dqkv_x3_dlse_kernel(const GtaBwdParams p, const int n_dq, const float* dlse) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int L = blockIdx.x, n_dkv = (int)gridDim.x - n_dq;
+    if (L < n_dkv) bwd_dkv_x3_body<DHP>(p, smem, L, n_dkv);
+    else bwd_dq_x3_body<DHP, true>(p, smem, L - n_dkv, n_dq, dlse);
+}
 
 __global__ __launch_bounds__(1024) void gta_reduce_kernel(const float* __restrict__ part, int n, float* __restrict__ out, const float* __restrict__ tau);
 
+// dlse (both run_bwd_x3 and run_bwd): null = gta_attn_bwd; else the DLSE instance of the pre-pass (and of the X3 joint launch) in place of the plain one
 template <int DHP>
-int run_bwd_x3(const GtaBwdParams& p, hipStream_t stream) {
+int run_bwd_x3(const GtaBwdParams& p, const float* dlse, hipStream_t stream) {
     const int n_qt = (p.Tq + BN - 1) / BN;
     using PS = BPrepSmem<DHP, 4, true>;
     if (int rc = gta_lds_optin<&gta_bwd_prep_kernel<DHP, 4, true>>(PS::total(GTA_MAX_VIEWS))) return rc;
+    if (int rc = gta_lds_optin<&gta_bwd_prep_kernel<DHP, 4, true, false, const float*>>(PS::total(GTA_MAX_VIEWS))) return rc;
     constexpr int LDS_MAX = DqX3Smem<DHP>::total(GTA_MAX_VIEWS) > DkvX3Smem<DHP>::total(GTA_MAX_VIEWS) ? DqX3Smem<DHP>::total(GTA_MAX_VIEWS) : DkvX3Smem<DHP>::total(GTA_MAX_VIEWS);
     if (int rc = gta_lds_optin<&gta_bwd_dqkv_x3_kernel<DHP>>(LDS_MAX)) return rc;
+    if (int rc = gta_lds_optin<&gta_bwd_dqkv_x3_dlse_kernel<DHP>>(LDS_MAX)) return rc;
     const long prep_grid = ((long)p.B * n_qt + 7) / 8 * 8 * p.H;
     const long n_dq = (long)p.B * p.H * ((p.Tq + 127) / 128), n_dkv = (long)p.B * p.H * ((p.Tk + 127) / 128);
     if (prep_grid > 0x7fffffffL || n_dq + n_dkv > 0x7fffffffL) return GTA_E_UNSUPPORTED;
-    hipLaunchKernelGGL((gta_bwd_prep_kernel<DHP, 4, true>), dim3((unsigned)prep_grid), dim3(256), PS::total(p.vrep_q ? p.Nq : 0), stream, p);
+    if (dlse) hipLaunchKernelGGL((gta_bwd_prep_kernel<DHP, 4, true, false, const float*>), dim3((unsigned)prep_grid), dim3(256), PS::total(p.vrep_q ? p.Nq : 0), stream, p, dlse);
+    else hipLaunchKernelGGL((gta_bwd_prep_kernel<DHP, 4, true>), dim3((unsigned)prep_grid), dim3(256), PS::total(p.vrep_q ? p.Nq : 0), stream, p);
     const int lds_dq = DqX3Smem<DHP>::total(p.vrep_q ? p.Nq : 0), lds_dkv = DkvX3Smem<DHP>::total(p.vrep_k ? p.Nk : 0);
-    hipLaunchKernelGGL((gta_bwd_dqkv_x3_kernel<DHP>), dim3((unsigned)(n_dq + n_dkv)), dim3(256), lds_dq > lds_dkv ? lds_dq : lds_dkv, stream, p, (int)n_dq);
+    if (dlse) hipLaunchKernelGGL((gta_bwd_dqkv_x3_dlse_kernel<DHP>), dim3((unsigned)(n_dq + n_dkv)), dim3(256), lds_dq > lds_dkv ? lds_dq : lds_dkv, stream, p, (int)n_dq, dlse);
+    else hipLaunchKernelGGL((gta_bwd_dqkv_x3_kernel<DHP>), dim3((unsigned)(n_dq + n_dkv)), dim3(256), lds_dq > lds_dkv ? lds_dq : lds_dkv, stream, p, (int)n_dq);
     if (p.dtrans_coeff)
         hipLaunchKernelGGL(gta_reduce_kernel, dim3(1), dim3(1024), 0, stream, p.dc_partial, p.dc_total, p.dtrans_coeff, (const float*)nullptr);
     if (p.dtau)
@@ -1942,15 +1981,17 @@ int run_bwd_x3(const GtaBwdParams& p, hipStream_t stream) {
 }
 
 template <int DHP, int ESZ>
-int run_bwd(const GtaBwdParams& p, hipStream_t stream) {
+int run_bwd(const GtaBwdParams& p, const float* dlse, hipStream_t stream) {
     const int n_qt = (p.Tq + BN - 1) / BN;
     if (int rc = gta_lds_optin<&gta_bwd_prep_kernel<DHP, ESZ>>(BPrepSmem<DHP, ESZ>::total(GTA_MAX_VIEWS))) return rc;
+    if (int rc = gta_lds_optin<&gta_bwd_prep_kernel<DHP, ESZ, false, false, const float*>>(BPrepSmem<DHP, ESZ>::total(GTA_MAX_VIEWS))) return rc;
     if (int rc = gta_lds_optin<&gta_bwd_dq_kernel<DHP, ESZ>>(DqSmem<DHP>::total(GTA_MAX_VIEWS))) return rc;
     if (int rc = gta_lds_optin<&gta_bwd_dkv_kernel<DHP, ESZ>>(DkvSmem<DHP>::total(GTA_MAX_VIEWS))) return rc;
     const int lds_prep = BPrepSmem<DHP, ESZ>::total(p.vrep_q ? p.Nq : 0);
     const long prep_grid = ((long)p.B * n_qt + 7) / 8 * 8 * p.H;
     if (prep_grid > 0x7fffffffL) return GTA_E_UNSUPPORTED;
-    hipLaunchKernelGGL((gta_bwd_prep_kernel<DHP, ESZ>), dim3((unsigned)prep_grid), dim3(256), lds_prep, stream, p);
+    if (dlse) hipLaunchKernelGGL((gta_bwd_prep_kernel<DHP, ESZ, false, false, const float*>), dim3((unsigned)prep_grid), dim3(256), lds_prep, stream, p, dlse);
+    else hipLaunchKernelGGL((gta_bwd_prep_kernel<DHP, ESZ>), dim3((unsigned)prep_grid), dim3(256), lds_prep, stream, p);
     const int n_dq = p.B * p.H * ((p.Tq + 127) / 128);
     const int n_dkv = p.B * p.H * ((p.Tk + 127) / 128);
     // (the generated kernels' epilogues are written for the MSN chunk layout)
@@ -2038,12 +2079,13 @@ int gta_bwd_varlen_dispatch(const GtaBwdParams& p, const int32_t* key_lens, cons
     return GTA_E_UNSUPPORTED;
 }
 
-int gta_bwd_dispatch(const GtaBwdParams& p, int dhp, int esz, hipStream_t stream) {
+// dlse: null (gta_attn_bwd) or the [B,H,Tq] row gradients of the log-sum-exp (gta_attn_bwd_dlse)
+int gta_bwd_dispatch(const GtaBwdParams& p, const float* dlse, int dhp, int esz, hipStream_t stream) {
     if (p.flags & GTA_FLAG_FP32_PRODUCTS) {             // the fp32-faithful backward on the matrix cores (gta_fwd_params.h)
         if (!gta_x3_takes(dhp, esz)) return GTA_E_UNSUPPORTED;
-        return dhp == 32 ? run_bwd_x3<32>(p, stream) : run_bwd_x3<64>(p, stream);
+        return dhp == 32 ? run_bwd_x3<32>(p, dlse, stream) : run_bwd_x3<64>(p, dlse, stream);
     }
-#define GTA_CASEB(D) case D: return esz == 2 ? run_bwd<D, 2>(p, stream) : run_bwd<D, 4>(p, stream);
+#define GTA_CASEB(D) case D: return esz == 2 ? run_bwd<D, 2>(p, dlse, stream) : run_bwd<D, 4>(p, dlse, stream);
     switch (dhp) {
         GTA_CASEB(32)
         GTA_CASEB(64)

@@ -278,9 +278,25 @@ def split_packed(packed: torch.Tensor):
     return _SplitPacked.apply(packed)
 
 
+def _none_to_zero(dout, like):
+    """the gradient of an output the loss did not use (``set_materialize_grads(False)``: None) as zeros of ``like``'s shape, dtype and memory"""
+    return torch.zeros_like(like) if dout is None else dout
+
+
 class _GtaAttn(torch.autograd.Function):
+    """forward -> out.  ``_GtaAttnLse`` below is the same call with the pair (out, lse) as differentiable outputs (``return_lse``); both
+    share ``_run`` and ``_grads``."""
+
     @staticmethod
-    def forward(ctx, q, k, v, trans_coeff, tau, kv_cache, cfg, vrep_q, vrep_k, cs_q, cs_k, *carriers):
+    def forward(ctx, *args):
+        return _GtaAttn._run(ctx, *args).out
+
+    @staticmethod
+    def backward(ctx, dout):
+        return _GtaAttn._grads(ctx, dout)
+
+    @staticmethod
+    def _run(ctx, q, k, v, trans_coeff, tau, kv_cache, cfg, vrep_q, vrep_k, cs_q, cs_k, *carriers):
         # carriers: () or six tensors / None (gta_amd.repgrad.split_tables) whose gradients the backward returns
         flags = cfg[5]
         c = _setup_call(q, k, v, *cfg, dict(vrep_q=vrep_q, vrep_k=vrep_k, cs_q=cs_q, cs_k=cs_k), trans_coeff, tau,
@@ -295,15 +311,15 @@ class _GtaAttn(torch.autograd.Function):
         ctx.save_for_backward(c.q, c.k, c.v, c.out, c.lse, c.tc, c.ta, vrep_q, vrep_k, cs_q, cs_k)
         ctx.tc_meta, ctx.tau_meta = _scalar_meta(trans_coeff), _scalar_meta(tau)
         ctx.carriers = _repgrad.carrier_meta(carriers)
-        return c.out
+        return c
 
     @staticmethod
-    def backward(ctx, dout):
+    def _grads(ctx, dout, dlse=None):
         from . import backward as _bw
         q, k, v, out, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k = ctx.saved_tensors
         want_dtau = ta is not None and ctx.needs_input_grad[4]
         dq, dk, dv, dtc, dta = _bw.attn_bwd(ctx.cfg, q, k, v, out, dout, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k,
-                                            kv_images=ctx.kv_images, want_dtau=want_dtau)
+                                            kv_images=ctx.kv_images, want_dtau=want_dtau, dlse=dlse)
         dtc, dta = _restore_scalar(dtc, ctx.tc_meta), _restore_scalar(dta, ctx.tau_meta)
         grads = ()
         if ctx.carriers:
@@ -319,13 +335,36 @@ class _GtaAttn(torch.autograd.Function):
         return (dq, dk, dv, dtc, dta, None, None, None, None, None, None) + grads
 
 
+class _GtaAttnLse(torch.autograd.Function):
+    """``_GtaAttn`` -> (out, lse), both differentiable: the backward takes (dout, dlse), either of which may be None, through
+    ``gta_attn_bwd_dlse`` (dS = P (dP - D + dlse): the q-side pre-pass stores -(D - dlse), every walk is the one of ``gta_attn_bwd``)."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        ctx.set_materialize_grads(False)
+        c = _GtaAttn._run(ctx, *args)
+        return c.out, c.lse
+
+    @staticmethod
+    def backward(ctx, dout, dlse):
+        return _GtaAttn._grads(ctx, _none_to_zero(dout, ctx.saved_tensors[3]), dlse)
+
+
 class _GenericAttn(torch.autograd.Function):
     """Ablation layouts the fused kernels refuse (t2 slab, so3 degree 1, unaligned slabs, euclid similarity):
     generic rho-apply kernels (gta_rep_apply) around the plain attention kernel, and for the backward their
     adjoints (gta_rep_apply_bwd) around the fused backward on an identity layout."""
 
     @staticmethod
-    def forward(ctx, q, k, v, trans_coeff, tau, cfg, packed, *carriers):
+    def forward(ctx, *args):
+        return _GenericAttn._run(ctx, *args)[0]
+
+    @staticmethod
+    def backward(ctx, dout):
+        return _GenericAttn._grads(ctx, dout)
+
+    @staticmethod
+    def _run(ctx, q, k, v, trans_coeff, tau, cfg, packed, *carriers):
         f_dims, so3_degree, scale, v_transform, euclid, precise = cfg
         flags = _layout_flags(v_transform, euclid)
         if q.dtype not in (torch.float32, torch.bfloat16):
@@ -359,10 +398,12 @@ class _GenericAttn(torch.autograd.Function):
         ctx.tc_meta, ctx.tau_meta = _scalar_meta(trans_coeff), _scalar_meta(tau)
         ctx.carriers = _repgrad.carrier_meta(carriers)
         ctx.save_for_backward(q, k, v, qp, kp, vp, op, lse, tc, ta)
-        return out
+        return out, lse
 
     @staticmethod
-    def backward(ctx, dout):
+    def _grads(ctx, dout, dlse=None):
+        # dlse (``_GenericAttnLse``): the gradient of the plain attention's lse -- rho touches neither the logits nor lse, so it enters the plain
+        # backward alone; under euclid the augmented channels carry the key bias, the logits and so lse are those of the forward
         from . import backward as _bw
         q, k, v, qp, kp, vp, op, lse, tc, ta = ctx.saved_tensors
         f_dims, so3_degree, scale, v_transform, euclid, _precise = ctx.cfg
@@ -416,6 +457,8 @@ class _GenericAttn(torch.autograd.Function):
             dhp = dhp2
         pcfg = ({"triv": dhp}, 0, 1, 1, scale, 0)
         # (with the bias in the augmented channels, <q', dq'> also carries the bias part of d tau)
+        if _precise and dt == torch.float32 and dlse is not None:
+            raise native.GtaError("return_lse: the exact-fp32 backward (gta_attn_bwd_plain_f32) takes no gradient of the log-sum-exp")
         if _precise and dt == torch.float32:
             # fp32-faithful mode: exact-fp32 products and sums (gta_plain32.hip) -- the gradients of the reference's fp32 autograd
             dqp, dkp, dvp = mk(Tq, dhp), mk(Tk, dhp), mk(Tk, dhp)
@@ -425,7 +468,7 @@ class _GenericAttn(torch.autograd.Function):
             dta = (-(qp.double() * dqp.double()).sum() / ta.double()).float().reshape(1) if (want_dtau and ta is not None) else None
         else:
             dqp, dkp, dvp, _, dta = _bw.attn_bwd(pcfg, qp, kp, vp, op, dop, lse, None, ta, None, None, None, None,
-                                                 want_dtau=want_dtau)
+                                                 want_dtau=want_dtau, dlse=dlse)
         dta = _restore_scalar(dta, ctx.tau_meta)
         if euclid:
             pitch = (Tk + 63) // 64 * 64
@@ -461,11 +504,29 @@ class _GenericAttn(torch.autograd.Function):
         return (dq, dk, dv, dtc, dta, None, None) + grads
 
 
-def _generic_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, precise=False, carriers=()):
-    """Generic path entry (forward + backward through _GenericAttn)."""
+class _GenericAttnLse(torch.autograd.Function):
+    """``_GenericAttn`` -> (out, lse), both differentiable (``return_lse``; default arithmetic): see ``_GtaAttnLse``"""
+
+    @staticmethod
+    def forward(ctx, *args):
+        ctx.set_materialize_grads(False)
+        return _GenericAttn._run(ctx, *args)
+
+    @staticmethod
+    def backward(ctx, dout, dlse):
+        q = ctx.saved_tensors[0]
+        if dout is None:
+            dout = torch.zeros(q.shape, device=q.device, dtype=q.dtype)
+        return _GenericAttn._grads(ctx, dout, dlse)
+
+
+def _generic_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, precise=False, carriers=(),
+                     return_lse=False):
+    """Generic path entry (forward + backward through _GenericAttn); ``return_lse``: -> (out, lse) through _GenericAttnLse."""
     tc = trans_coeff if torch.is_tensor(trans_coeff) else None
     ta = tau if torch.is_tensor(tau) else None
-    return _GenericAttn.apply(q, k, v, tc, ta, (f_dims, so3_degree, scale, v_transform, euclid, precise), packed, *carriers)
+    fn = _GenericAttnLse if return_lse else _GenericAttn
+    return fn.apply(q, k, v, tc, ta, (f_dims, so3_degree, scale, v_transform, euclid, precise), packed, *carriers)
 
 
 def _probe(dtype, q_shape, Tk: int, f_dims, so3_degree: int, Nq: int, Nk: int, flags: int):
@@ -637,7 +698,7 @@ class _VarlenAttn(torch.autograd.Function):
 
 
 def _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, kv_cache=None, key_views=None,
-                    key_lens=None):
+                    key_lens=None, return_lse=False):
     """The generic path without a gradient: one pre-pass launch + one attention launch (``gta_attn_fwd_staged``), and the attention
     launch alone on a call that finds its K'/V' images in ``kv_cache`` -- the contract of ``_GtaAttn``: images and plan key are stored by
     the first call, later calls against another key set / plan raise ``GtaError``.  ``key_views`` (validated) with ``key_lens`` (device):
@@ -654,7 +715,7 @@ def _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale
         native.attn_fwd_staged_varlen(c.desc, c.q, c.k, c.v, *tables, c.tc, c.ta, key_lens, c.out, c.lse, ws)
     else:
         native.attn_fwd_staged(c.desc, c.q, c.k, c.v, *tables, c.tc, c.ta, c.out, c.lse, ws)
-    return c.out
+    return (c.out, c.lse) if return_lse else c.out
 
 
 def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: int = 0,
@@ -662,7 +723,7 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
                   euclid: bool = False, pretransformed: bool = False, use_dma: bool = True,
                   kv_mode: str = "auto", kv_cache: Optional[dict] = None, precise: Optional[bool] = None,
                   key_views=None, key_lens: Optional[torch.Tensor] = None, key_views_backward: bool = False,
-                  query_views=None) -> torch.Tensor:
+                  query_views=None, return_lse: bool = False):
     """Fused GTA attention on packed reps.  q [B,H,Tq,dh], k/v [B,H,Tk,dh] -> out [B,H,Tq,dh].
 
     kv_mode: 'prepass' = K/V rep pre-pass + lean attention kernel (two launches; at dh = 96 in the MSN layout the attention kernel is
@@ -693,6 +754,12 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
     query_views: only with ``key_views_backward=True``; validated like ``key_views``, against Nq.  Backward only: the query rows of scene b's
              views past ``query_views[b]`` (self-attention over padded views, where they hold anything) send no gradient -- their ``dout`` is
              never read, their dq rows are zero.  The forward still computes (unspecified) output rows for them.
+    return_lse: False (default): -> out, exactly as without the keyword.  True: -> (out, lse); lse [B,H,Tq] float32 is the natural log of
+             sum_k exp((scale q'.k' + bias_k) / tau) per query row (bias_k: the euclid key bias, else 0) -- what every forward kernel writes
+             beside out and ``gta_attention_merge`` combines partial attentions with.  Without grad on every route (fused, key_views, staged,
+             rho-apply).  Under grad lse is a differentiable output like out -- the backward takes (dout, dlse), either may be missing -- in
+             the default arithmetic (fused layouts and the rho-apply route) and with precise=True where the fused fp32-faithful backward runs
+             (float32, dh <= 64); ``key_views_backward`` and the exact-fp32 route of precise=True (gta_plain32) raise ``GtaError``.
     """
     if query_views is not None and not key_views_backward:
         raise native.GtaError("query_views masks padded query rows in the backward: it needs key_views_backward=True")
@@ -713,6 +780,9 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
     if isinstance(tau, (int, float)):
         tau = None if float(tau) == 1.0 else torch.tensor([float(tau)], device=q.device, dtype=torch.float32)
     needs_grad = torch.is_grad_enabled() and (bool(carriers) or any(torch.is_tensor(t) and t.requires_grad for t in (q, k, v, trans_coeff, tau)))
+    if return_lse and needs_grad and key_views_backward:
+        raise native.GtaError("return_lse under grad with key_views_backward: gta_attn_bwd_varlen takes no gradient of the log-sum-exp "
+                              "(drop return_lse, or call under torch.no_grad())")
     Nq, Nk = _views(f_dims, packed, q, k)
     if key_views is not None:
         key_views = check_key_views(key_views, q.shape[0], Nk if "vrep_k" in packed else None)
@@ -735,18 +805,120 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
         key_lens = key_lens_tensor(key_views, k.shape[2] // Nk, q.device)
     if route == "staged":
         return _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, kv_cache,
-                               key_views=key_views, key_lens=key_lens)
+                               key_views=key_views, key_lens=key_lens, return_lse=return_lse)
     if route == "apply":
+        if return_lse and needs_grad and precise and q.dtype == torch.float32:
+            raise native.GtaError("return_lse under grad with precise=True at this layout: the exact-fp32 backward (gta_plain32) takes no "
+                                  "gradient of the log-sum-exp; the fused fp32-faithful backward (float32, dh <= 64, fused layouts) does")
         return _generic_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, precise=bool(precise),
-                                carriers=carriers)
+                                carriers=carriers, return_lse=return_lse)
     cfg = ({k_: int(v_) for k_, v_ in f_dims.items()}, int(so3_degree), Nq, Nk, float(scale), flags)
     tables = [packed.get(t) for t in ("vrep_q", "vrep_k", "cs_q", "cs_k")]
     if key_views is None:
-        return _GtaAttn.apply(q, k, v, trans_coeff, tau, kv_cache, cfg, *tables, *carriers)
-    if needs_grad:          # (key_views_backward: anything else was refused above)
+        return (_GtaAttnLse if return_lse else _GtaAttn).apply(q, k, v, trans_coeff, tau, kv_cache, cfg, *tables, *carriers)
+    if needs_grad:          # (key_views_backward: anything else was refused above, return_lse included)
         q_lens = None if query_views is None else key_lens_tensor(query_views, q.shape[2] // Nq, q.device)
         return _VarlenAttn.apply(q, k, v, trans_coeff, tau, cfg, key_lens, q_lens, *tables)
-    return _varlen_forward(q, k, v, cfg, packed, trans_coeff, tau, key_lens, key_views, kv_cache)[0].out
+    c = _varlen_forward(q, k, v, cfg, packed, trans_coeff, tau, key_lens, key_views, kv_cache)[0]
+    return (c.out, c.lse) if return_lse else c.out
+
+
+class _MergeAttn(torch.autograd.Function):
+    """``gta_attention_merge``: (out_1..n, lse_1..n) -> (out, lse) through gta_attn_merge, backward through gta_attn_merge_bwd"""
+
+    @staticmethod
+    def forward(ctx, n, *ts):
+        ctx.set_materialize_grads(False)
+        outs, lses = [_as_kernel_layout(t.detach()) for t in ts[:n]], [t.detach() for t in ts[n:]]
+        B, H, Tq, dh = outs[0].shape
+        out = torch.empty(B, Tq, H, dh, device=outs[0].device, dtype=outs[0].dtype).permute(0, 2, 1, 3)
+        lse = torch.empty(B, H, Tq, device=outs[0].device, dtype=torch.float32)
+        native.attn_merge(outs, lses, out, lse)
+        ctx.n = n
+        ctx.save_for_backward(*outs, *lses)
+        return out, lse
+
+    @staticmethod
+    def backward(ctx, dout, dlse):
+        n = ctx.n
+        outs, lses = ctx.saved_tensors[:n], ctx.saved_tensors[n:]
+        B, H, Tq, dh = outs[0].shape
+        dev, dt = outs[0].device, outs[0].dtype
+        dout = torch.zeros(B, Tq, H, dh, device=dev, dtype=dt).permute(0, 2, 1, 3) if dout is None else _as_kernel_layout(dout.to(dt))
+        douts = [torch.empty(B, Tq, H, dh, device=dev, dtype=dt).permute(0, 2, 1, 3) for _ in range(n)]
+        dlses = [torch.empty(B, H, Tq, device=dev, dtype=torch.float32) for _ in range(n)]
+        native.attn_merge_bwd(outs, lses, dout, None if dlse is None else dlse.to(torch.float32), douts, dlses)
+        return (None, *douts, *dlses)
+
+
+def gta_attention_merge(outs, lses):
+    """Combine n (1..8) partial attentions of the SAME queries over DISJOINT key sets -- each an ``(out_i, lse_i)`` of
+    ``gta_attention(..., return_lse=True)`` -- into the attention over the union of the key sets: -> (out [B,H,Tq,dh], lse [B,H,Tq]).
+
+    With a_i = softmax_i(lse_i) per query row: out = sum_i a_i out_i, lse = logsumexp_i(lse_i); differentiable in every out_i and lse_i
+    (dout_i = a_i dout, dlse_i = a_i (dlse + <dout, out_i - out>)).  One HIP kernel each way (gta_merge.hip), fp32 arithmetic and one rounding
+    to the dtype of ``outs``.  A partial whose lse_i is -inf on a row (it saw no key) is selected out, not multiplied: its out_i there may hold
+    NaN; rows that are -inf in every partial give zeros and -inf.  dh % 8 == 0, dh <= 128."""
+    outs, lses = list(outs), list(lses)
+    if not 1 <= len(outs) <= native.MERGE_MAX or len(lses) != len(outs):
+        raise native.GtaError(f"gta_attention_merge takes 1 to {native.MERGE_MAX} partial attentions, each an (out, lse) pair "
+                              f"(got {len(outs)} outs, {len(lses)} lses)")
+    return _MergeAttn.apply(len(outs), *outs, *lses)
+
+
+_KEY_SIDE_TABLES = ("vrep_k", "cs_k", "coord_k", "grad_cs_k", "grad_coord_k")
+
+
+def gta_attention_by_view_groups(q, k, v, f_dims: Dict[str, int], packed: dict, *, views_per_call: int, num_key_views: Optional[int] = None,
+                                 **kw):
+    """``gta_attention`` over a key side of ANY number of views: the key views are cut into groups of at most ``views_per_call``
+    (<= GTA_MAX_VIEWS = 16, what one fused call takes; or a sequence of group sizes that add up to the number of key views), each group is one ``gta_attention(..., return_lse=True)`` call and the partial
+    attentions are merged (``gta_attention_merge``, up to 8 at a time) -> out [B,H,Tq,dh], or (out, lse) with ``return_lse=True``.
+
+    K and V of a group are token slices of k and v (tokens are view-major: no copy where the slice keeps 16-byte rows); the key-side tables'
+    rows are copied per group (vrep_k per view, cs_k / coord_k per token).  The number of key views is that of ``packed['vrep_k']``;
+    a layout without view tables says it with ``num_key_views``.  Differentiable wherever ``gta_attention(..., return_lse=True)`` is.  Every
+    other keyword goes to ``gta_attention``; ``kv_cache``, ``key_views`` (with its companions) and ``return_attmap`` are refused."""
+    for name in ("kv_cache", "key_views", "key_lens", "key_views_backward", "query_views", "return_attmap"):
+        if kw.get(name) is not None and kw.get(name) is not False:
+            raise native.GtaError(f"gta_attention_by_view_groups takes no {name}: every group is a call of its own")
+    return_lse = bool(kw.get("return_lse", False))
+    kw = {n_: v_ for n_, v_ in kw.items() if n_ not in ("kv_cache", "key_views", "key_lens", "key_views_backward", "query_views", "return_attmap",
+                                                         "return_lse")}
+    sizes = None if isinstance(views_per_call, (int, np.integer)) and not isinstance(views_per_call, bool) else views_per_call
+    try:
+        sizes = None if sizes is None else [int(x) for x in sizes if not isinstance(x, bool) and isinstance(x, (int, np.integer))]
+        bad = sizes is not None and (len(sizes) != len(tuple(views_per_call)) or not sizes)
+    except TypeError:
+        bad = True
+    if bad or any(not 1 <= x <= native.MAX_VIEWS for x in (sizes if sizes is not None else [views_per_call])):
+        raise native.GtaError(f"views_per_call must be an integer (or a sequence of group sizes) in 1..GTA_MAX_VIEWS = 1..{native.MAX_VIEWS}, "
+                              f"got {views_per_call!r}")
+    Nk = packed["vrep_k"].shape[1] if "vrep_k" in packed else num_key_views
+    if Nk is None:
+        raise native.GtaError("gta_attention_by_view_groups: this layout has no view tables (vrep_k): pass num_key_views")
+    Tk = k.shape[2]
+    if Nk < 1 or Tk % Nk:
+        raise native.GtaError(f"gta_attention_by_view_groups: {Tk} key tokens do not split evenly into {Nk} views")
+    Pk = Tk // Nk
+    if sizes is None:
+        sizes = [min(int(views_per_call), Nk - g0) for g0 in range(0, Nk, int(views_per_call))]
+    elif sum(sizes) != Nk:
+        raise native.GtaError(f"views_per_call: the group sizes {sizes} do not add up to the {Nk} key views")
+    partials, g1 = [], 0
+    for n_views in sizes:
+        g0, g1 = g1, g1 + n_views
+        t0, t1 = g0 * Pk, g1 * Pk
+        sub = dict(packed)
+        for name in _KEY_SIDE_TABLES:
+            if torch.is_tensor(packed.get(name)):
+                sub[name] = (packed[name][:, g0:g1] if name == "vrep_k" else packed[name][:, t0:t1]).contiguous()
+        partials.append(gta_attention(q, k[:, :, t0:t1], v[:, :, t0:t1], f_dims, sub, return_lse=True, **kw))
+    # (more than 8 groups: merge in rounds of 8 -- a merge of merges is the merge)
+    while len(partials) > 1:
+        partials = [gta_attention_merge([p_[0] for p_ in partials[i:i + native.MERGE_MAX]], [p_[1] for p_ in partials[i:i + native.MERGE_MAX]])
+                    for i in range(0, len(partials), native.MERGE_MAX)]
+    return partials[0] if return_lse else partials[0][0]
 
 
 # kv_mode name -> flags of its tuning knob; every name but 'auto' and 'fused' asks for the two-stage plan ('prepass')

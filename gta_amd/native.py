@@ -50,7 +50,9 @@ ABI_SYMBOLS = (
     "gta_attn_fwd_staged", "gta_attn_fwd_staged_supported", "gta_attn_fwd_staged_workspace_bytes",
     "gta_attn_fwd_varlen", "gta_attn_fwd_varlen_supported", "gta_attn_fwd_staged_varlen", "gta_attn_fwd_staged_varlen_supported",
     "gta_attn_bwd_varlen", "gta_attn_bwd_varlen_supported",
+    "gta_attn_bwd_dlse", "gta_attn_bwd_dlse_supported", "gta_attn_merge", "gta_attn_merge_bwd",
 )
+MERGE_MAX = 8           # partial attentions per gta_attn_merge call
 
 
 class GtaError(RuntimeError):
@@ -141,6 +143,15 @@ def lib():
         L.gta_attn_bwd_varlen.argtypes = ([ctypes.POINTER(GtaAttnDesc)] + [c_void_p] * 18
                                           + [ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_int64, c_void_p])
         L.gta_attn_bwd_varlen_supported.argtypes = [ctypes.POINTER(GtaAttnDesc)]
+        # gta_attn_bwd with dlse ([B,H,Tq] fp32, device) behind lse
+        L.gta_attn_bwd_dlse.argtypes = ([ctypes.POINTER(GtaAttnDesc)] + [c_void_p] * 17
+                                        + [ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_int64, c_void_p])
+        L.gta_attn_bwd_dlse_supported.argtypes = [ctypes.POINTER(GtaAttnDesc)]
+        # merges: sizes, then (host array of device pointers | device pointer, host array of element strides) per operand
+        P64 = ctypes.POINTER(c_int64)
+        L.gta_attn_merge.argtypes = [c_int32] * 6 + [ctypes.POINTER(c_void_p), P64] * 2 + [c_void_p, P64] * 2 + [c_void_p]
+        L.gta_attn_merge_bwd.argtypes = ([c_int32] * 6 + [ctypes.POINTER(c_void_p), P64] * 2 + [c_void_p, P64] * 2
+                                         + [ctypes.POINTER(c_void_p), P64] * 2 + [c_void_p])
         _lib = L
     return _lib
 
@@ -402,12 +413,12 @@ def attn_bwd_workspace_bytes(desc: GtaAttnDesc) -> int:
     return int(lib().gta_attn_bwd_workspace_bytes(ctypes.byref(desc)))
 
 
-def _bwd_call(entry: str, desc: GtaAttnDesc, q, k, v, out, dout, lse, tables, lens, kv_images, dq, dk, dv, dtrans_coeff, workspace, dtau):
-    """Both backward entries: ``lens`` is () or (key_lens, q_lens) -- [B] int32 on the device, q_lens may be None."""
-    _require_cuda(q, k, v, out, dout, dq, dk, dv, workspace, *lens)
+def _bwd_call(entry: str, desc: GtaAttnDesc, q, k, v, out, dout, lse, tables, lens, kv_images, dq, dk, dv, dtrans_coeff, workspace, dtau, dlse=()):
+    """The backward entries: ``lens`` is () or (key_lens, q_lens) -- [B] int32 on the device, q_lens may be None; ``dlse`` is () or (dlse,)."""
+    _require_cuda(q, k, v, out, dout, dq, dk, dv, workspace, *lens, *dlse)
     for t in lens[:1] + tuple(t for t in lens[1:] if t is not None):
         _check_key_lens(t, desc.B, workspace.device)
-    check(getattr(lib(), entry)(ctypes.byref(desc), *map(_ptr, (q, k, v, out, dout, lse)), *map(_ptr, tables), *map(_ptr, lens),
+    check(getattr(lib(), entry)(ctypes.byref(desc), *map(_ptr, (q, k, v, out, dout, lse)), *map(_ptr, dlse), *map(_ptr, tables), *map(_ptr, lens),
                                 _ptr(kv_images), _ptr(dq), _ptr(dk), _ptr(dv), _strides(dq, dk, dv), _strides(dout),
                                 _ptr(dtrans_coeff), _ptr(dtau), _ptr(workspace), workspace.numel(), _stream()), entry)
 
@@ -417,6 +428,61 @@ def attn_bwd(desc: GtaAttnDesc, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, c
     """All tensors [B,H,T,dh] views (unit channel stride); dq/dk/dv/dout strides are passed explicitly."""
     _bwd_call("gta_attn_bwd", desc, q, k, v, out, dout, lse, (vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau), (), kv_images,
               dq, dk, dv, dtrans_coeff, workspace, dtau)
+
+
+def attn_bwd_dlse_supported(desc: GtaAttnDesc) -> int:
+    """0 when gta_attn_bwd_dlse (the backward of the pair (out, lse)) serves desc, else a GTA_E_* code; needs no GPU"""
+    return lib().gta_attn_bwd_dlse_supported(ctypes.byref(desc))
+
+
+def attn_bwd_dlse(desc: GtaAttnDesc, q, k, v, out, dout, lse, dlse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, kv_images,
+                  dq, dk, dv, dtrans_coeff, workspace, dtau=None):
+    """``attn_bwd`` for the pair (dout, dlse): dlse [B,H,Tq] float32, contiguous, the gradient of the forward's lse."""
+    if (not torch.is_tensor(dlse) or dlse.dtype != torch.float32 or tuple(dlse.shape) != (desc.B, desc.H, desc.Tq) or not dlse.is_contiguous()
+            or dlse.device != q.device):
+        raise GtaError(f"dlse must be a contiguous float32 tensor of shape ({desc.B}, {desc.H}, {desc.Tq}) on {q.device}")
+    _bwd_call("gta_attn_bwd_dlse", desc, q, k, v, out, dout, lse, (vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau), (), kv_images,
+              dq, dk, dv, dtrans_coeff, workspace, dtau, dlse=(dlse,))
+
+
+def _ptr_array(ts):
+    return (c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def _check_merge(name: str, n: int, n_lses: int, outs, lses):
+    """n partials; ``outs`` / ``lses``: every out-like ([B,H,Tq,dh], one dtype, unit channel stride) / lse-like ([B,H,Tq] float32) operand of the call,
+    all on the current GPU"""
+    if not 1 <= n <= MERGE_MAX or n_lses != n:
+        raise GtaError(f"{name}: a merge takes 1 to {MERGE_MAX} partial attentions, each an (out, lse) pair (got {n} outs, {n_lses} lses)")
+    if not all(torch.is_tensor(t) for t in list(outs) + list(lses)):
+        raise GtaError(f"{name}: operands are tensors")
+    shape, dt = tuple(outs[0].shape), outs[0].dtype
+    if len(shape) != 4 or dt not in (torch.float32, torch.bfloat16):
+        raise GtaError(f"{name}: outs are [B,H,Tq,dh] tensors of float32 or bfloat16 (got {shape}, {dt})")
+    _require_cuda(*outs, *lses)
+    for o, l in zip(outs, lses):
+        if tuple(o.shape) != shape or o.dtype != dt or o.stride(3) != 1:
+            raise GtaError(f"{name}: every out is a {shape} {dt} tensor with unit channel stride (got {tuple(o.shape)}, {o.dtype}, strides {o.stride()})")
+        if tuple(l.shape) != shape[:3] or l.dtype != torch.float32:
+            raise GtaError(f"{name}: every lse is a {shape[:3]} float32 tensor (got {tuple(l.shape)}, {l.dtype})")
+    return shape, dt
+
+
+def attn_merge(outs, lses, out, lse):
+    """gta_attn_merge: n partial attentions (out_i [B,H,Tq,dh], lse_i [B,H,Tq] fp32) -> out, lse (written)."""
+    (B, H, Tq, dh), dt = _check_merge("gta_attn_merge", len(outs), len(lses), list(outs) + [out], list(lses) + [lse])
+    check(lib().gta_attn_merge(DTYPE_BF16 if dt == torch.bfloat16 else DTYPE_F32, len(outs), B, H, Tq, dh, _ptr_array(outs), _strides(*outs),
+                               _ptr_array(lses), _strides(*lses), _ptr(out), _strides(out), _ptr(lse), _strides(lse), _stream()), "gta_attn_merge")
+
+
+def attn_merge_bwd(outs, lses, dout, dlse, douts, dlses):
+    """gta_attn_merge_bwd: (dout, dlse or None) -> douts, dlses (written) for the partials ``outs``, ``lses`` of ``attn_merge``."""
+    (B, H, Tq, dh), dt = _check_merge("gta_attn_merge_bwd", len(outs), len(lses), list(outs) + list(douts) + [dout],
+                                      list(lses) + list(dlses) + ([dlse] if dlse is not None else []))
+    check(lib().gta_attn_merge_bwd(DTYPE_BF16 if dt == torch.bfloat16 else DTYPE_F32, len(outs), B, H, Tq, dh, _ptr_array(outs), _strides(*outs),
+                                   _ptr_array(lses), _strides(*lses), _ptr(dout), _strides(dout), _ptr(dlse),
+                                   None if dlse is None else _strides(dlse), _ptr_array(douts), _strides(*douts), _ptr_array(dlses),
+                                   _strides(*dlses), _stream()), "gta_attn_merge_bwd")
 
 
 def attn_bwd_varlen_supported(desc: GtaAttnDesc) -> int:

@@ -214,6 +214,50 @@ int gta_attn_bwd_varlen(const GtaAttnDesc* desc,
                         float* dtrans_coeff, float* dtau,
                         void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Backward of the PAIR (out, lse) (gta_attention's return_lse under grad): gta_attn_bwd with the gradient of the log-sum-exp.
+ *   dlse: [B,H,Tq] fp32, contiguous, non-NULL (GTA_E_BADARG) -- d loss / d lse per query row, lse as the forward wrote it (natural log).
+ *   The exact gradient of the logits is dS_ij = P_ij (dP_ij - D_i + dlse_i): the q-side pre-pass runs in instances that store -(D - dlse)
+ *       where gta_attn_bwd's store -D, and every dQ / dK,dV kernel -- compiled pair, generated 64-row streams, X3 walks -- is the one
+ *       gta_attn_bwd launches for the same desc.  An all-zero dlse gives dq, dk, dv, dtrans_coeff and dtau bit for bit those of gta_attn_bwd.
+ *       Under GTA_FLAG_FP32_PRODUCTS the centred dtau of the X3 dQ walk accounts for sum_j dS_ij = dlse_i.
+ *   gta_attn_bwd_dlse_supported: 0 where gta_attn_bwd serves desc, else its error with the reason in gta_strerror() (layouts without a
+ *       fused kernel, GTA_FLAG_PRETRANSFORMED, GTA_FLAG_FP32_PRODUCTS outside fp32 inputs at dh <= 64).  No instance with per-scene prefixes.
+ *   Every other argument, check, workspace size and error code: as in gta_attn_bwd. */
+int gta_attn_bwd_dlse_supported(const GtaAttnDesc* desc);
+int gta_attn_bwd_dlse(const GtaAttnDesc* desc,
+                      const void* q, const void* k, const void* v, const void* out, const void* dout,
+                      const float* lse, const float* dlse,
+                      const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
+                      const float* trans_coeff, const float* tau,
+                      const void* kv_images,
+                      void* dq, void* dk, void* dv, const int64_t* dqkv_stride, const int64_t* dout_stride,
+                      float* dtrans_coeff, float* dtau,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+
+/* -------------------------------------------------------------------------------------------
+ * Merge of partial attentions (gta_attention_merge): n in 1..8 attentions (out_i, lse_i) of the SAME queries over DISJOINT key sets
+ * combine into the attention over the union.  With a_i = softmax_i(lse_i) per query row:
+ *     out = sum_i a_i out_i,   lse = logsumexp_i(lse_i);      dout_i = a_i dout,   dlse_i = a_i (dlse + <dout, out_i - out>).
+ *   dtype: GTA_DTYPE_* of every out / dout operand; B, H, Tq, dh: their [B,H,Tq,dh] shape, dh % 8 == 0 and <= 128 (else GTA_E_UNSUPPORTED).
+ *   outs, lses (and douts, dlses): HOST arrays of n DEVICE pointers; *_stride: host arrays of the (batch, head, token) element strides, three
+ *       per operand ([n][3] for the arrays); the channel stride is 1.  out-like operands: 16-byte aligned base and rows (GTA_E_BADARG);
+ *       lse-like operands are [B,H,Tq] fp32 views with any strides.  The host arrays are read during the call only.
+ *   Arithmetic in fp32, one rounding to dtype.  A partial whose lse_i is -inf on a row (no key) is selected out, not multiplied: its out_i
+ *       row enters no arithmetic (it may hold NaN; it must be readable memory), its dout_i row and dlse_i are exact zeros; a row with every lse_i = -inf gives out = 0, lse = -inf.
+ *       n = 1 returns its input bit for bit.
+ *   gta_attn_merge_bwd: dout like out, dlse [B,H,Tq] fp32 through dlse_stride or NULL (= 0); douts / dlses are written, not accumulated.
+ *   Kernels (gta_merge.hip): HBM-bound streams, one 16-byte unit per lane, rows in the memory order of [B,Tq,H,dh] tensors, no LDS, no
+ *       workspace.  No operand may alias an output.
+ * ------------------------------------------------------------------------------------------- */
+int gta_attn_merge(int32_t dtype, int32_t n, int32_t B, int32_t H, int32_t Tq, int32_t dh,
+                   const void* const* outs, const int64_t* outs_stride, const float* const* lses, const int64_t* lses_stride,
+                   void* out, const int64_t* out_stride, float* lse, const int64_t* lse_stride, void* stream);
+int gta_attn_merge_bwd(int32_t dtype, int32_t n, int32_t B, int32_t H, int32_t Tq, int32_t dh,
+                       const void* const* outs, const int64_t* outs_stride, const float* const* lses, const int64_t* lses_stride,
+                       const void* dout, const int64_t* dout_stride, const float* dlse, const int64_t* dlse_stride,
+                       void* const* douts, const int64_t* douts_stride, float* const* dlses, const int64_t* dlses_stride,
+                       void* stream);
+
 /* -------------------------------------------------------------------------------------------
  * Generic path for the reference's ablations (any f_dims layout): t2 slab (gta.py:221-238,272-274),
  * euclid similarity (GTA_FLAG_EUCLID; gta.py:146-156,251-253 + EuclidAttnFn layers.py:213-224),

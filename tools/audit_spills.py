@@ -101,6 +101,9 @@ def audit_others():
             if kern == "gta_bwd_prep_kernel" and "ELb0ELb1E" in name:      # its VARLEN instances <dhp, esz, false, true, q_lens>: below
                 report.pop()
                 continue
+            if kern == "gta_bwd_prep_kernel" and "JPKfE" in name:         # its DLSE instances <dhp, esz, x3, false, dlse>: below
+                report.pop()
+                continue
             if "ELb1E" not in name:                     # (not the prep kernel's X3 instances, which share <dhp, 4>)
                 bwd_scratch[(kern, dhp, esz)] = row["scratch"]
             if row["scratch"]:
@@ -115,6 +118,30 @@ def audit_others():
             twin = bwd_scratch.get((kern + "_kernel", dhp, esz))
             if twin is None or row["scratch"] > twin:
                 problems.append(f"{row['kernel']} has {row['scratch']} scratch accesses, its twin without VARLEN {twin}")
+    # the DLSE instances of the pre-pass (gta_attn_bwd_dlse) by the same rule against the twin without dlse, X3 ones against the X3 twin
+    prep = {}
+    for name, (dhp, esz, x3), body, vgpr in _kernels(text, r"gta_bwd_prep_kernelILi(\d+)ELi(\d+)ELb(\d)ELb0EJ"):
+        prep[(dhp, esz, x3, "JPKfE" in name)] = (body.count("scratch_"), vgpr)
+    for (dhp, esz, x3, dlse), (n, vgpr) in sorted(prep.items()):
+        if not dlse:
+            continue
+        row = {"kernel": f"gta_bwd_prep_kernel<{dhp},{esz}{', x3' if x3 == '1' else ''}, dlse>", "vgpr": vgpr, "scratch": n}
+        report.append(row)
+        twin = prep.get((dhp, esz, x3, False))
+        if twin is None or n > twin[0]:
+            problems.append(f"{row['kernel']} has {n} scratch accesses, its twin without dlse {twin and twin[0]}")
+    # the merge kernels (gta_merge.hip): the partials' pointers and strides are indexed by unrolled constants -- no scratch at all (hard)
+    mtext = _asm("gta_merge.hip")
+    n_merge = 0
+    for name, (esz,), body, vgpr in _kernels(mtext, r"gta_merge_(?:bwd_)?kernelILi(\d+)E"):
+        kind = "gta_merge_bwd_kernel" if "merge_bwd" in name else "gta_merge_kernel"
+        row = {"kernel": f"{kind}<{esz}>", "vgpr": vgpr, "scratch": body.count("scratch_")}
+        report.append(row)
+        n_merge += 1
+        if row["scratch"]:
+            problems.append(f"{row['kernel']}: {row['scratch']} scratch accesses")
+    if n_merge != 4:
+        problems.append(f"gta_merge.hip: {n_merge} kernel instances found (expected 4)")
     text = _asm("gta_wgrad.hip")
     for name, _, body, vgpr in _kernels(text, r"wgrad_kernelILb(\d)E"):
         lines = body.split("\n")

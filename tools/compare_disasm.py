@@ -14,12 +14,14 @@ import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SOURCES = ["gta_reps", "gta_fwd", "gta_prep", "gta_fwd2", "gta_fwd_gen", "gta_fwd_cl", "gta_fwd64", "gta_bwd", "gta_apply", "gta_plain32", "gta_repgrad"]
+SOURCES = ["gta_reps", "gta_fwd", "gta_prep", "gta_fwd2", "gta_fwd_gen", "gta_fwd_cl", "gta_fwd64", "gta_bwd", "gta_apply", "gta_plain32", "gta_repgrad", "gta_merge"]
 NO_SLP = {"gta_fwd2", "gta_fwd64", "gta_fwd_gen", "gta_fwd_cl", "gta_bwd", "gta_prep"}          # (FLAGS_* of the Makefile)
 VARLEN = ("gta_fwd2_kernel", "gta_kv_prep_kernel", "gta_gen_prep_kernel", "gta_gen_attn_kernel", "gta_bwd_prep_kernel")
 
 
 def assembly(tree, name, out):
+    if not os.path.exists(os.path.join(tree, "gta_amd", "csrc", name + ".hip")):      # a source the tree does not have yet: no functions
+        return ""
     cmd = [HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function", *(["-fno-slp-vectorize"] if name in NO_SLP else []),
            "-S", "--cuda-device-only", "-o", out, os.path.join(tree, "gta_amd", "csrc", name + ".hip")]
     subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
