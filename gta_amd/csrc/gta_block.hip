@@ -385,6 +385,7 @@ inline bool make_drop(float p, uint64_t seed, Drop* d) {
     d->scale = 1.0f / (1.0f - p);
     return true;
 }
+// (the cap of 8192 workgroups sizes N_EW of tests/test_gpu_block_regimes.py, where the element-wise kernels take a second trip)
 inline unsigned ew_grid(int64_t n8) {
     const int64_t want = (n8 + 255) / 256;
     return (unsigned)(want < 8192 ? want : 8192);
@@ -395,11 +396,14 @@ inline int launch_status() { return hipGetLastError() == hipSuccess ? GTA_OK : G
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 constexpr int LN_BWD_MAX_WG = 1024;      // 4 workgroups of 4 waves per CU
+// (sizes the rows of test_layernorm_backward_regimes, tests/test_gpu_block_regimes.py, and of the 4352-row layer of
+// test_fused_transformer_matches_modulewise_on_the_training_path, tests/test_gpu_block.py: both assert the partial count)
 inline int ln_bwd_grid(int64_t rows) {
     int64_t g = (rows + 3) / 4;
     return (int)(g < LN_BWD_MAX_WG ? g : LN_BWD_MAX_WG);
 }
 constexpr int COLSUM_MAX_STRIPS = 512;
+// (with the 64 rows per strip below: test_colsum_finish_unrolled_body_then_tail, tests/test_gpu_block_regimes.py, asserts its strip count)
 inline int colsum_strips(int64_t m, int n) {
     const int64_t per = (n + 511) / 512;                         // workgroups per strip
     int64_t cap = COLSUM_MAX_STRIPS / per;

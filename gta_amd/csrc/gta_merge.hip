@@ -168,6 +168,7 @@ __global__ __launch_bounds__(256) void gta_merge_bwd_kernel(const GtaMergeBwdPar
 }
 
 // rows fit an int (the kernels divide the row index); 256 >> lg rows per workgroup and step, at most 8 workgroups per CU of work in flight
+// (the cap of 2048 workgroups sizes the rows of test_merge_past_the_grid_cap, tests/test_gpu_lse_merge.py)
 template <class P>
 long merge_grid(const P& p, int esz) {
     const long R = (long)p.B * p.Tq * p.H;

@@ -48,6 +48,7 @@ constexpr int WG_BT = 32;                          // tokens per step (two 16-to
 constexpr int WG_OPER = WG_BT * WG_TILE * 2;       // one operand tile [32][256] bf16, bytes (16 KiB)
 constexpr int WG_STAGE = 2 * WG_OPER;              // G tile + X tile (32 KiB)
 constexpr int WG_NSTAGE = 4;        // ring depth: NSTAGE - 1 steps of DMA in flight under the MFMAs
+// (test_wgrad_kernel, tests/test_gpu_block.py, picks its row counts around this depth: 1, 3, 5, 6, 7 steps in one split, 9 + 8 in two)
 constexpr int WG_LDS = WG_NSTAGE * WG_STAGE;
 constexpr int WG_WAVES = 4;          // 4: 2 (n) x 2 (k), 128 x 128 of the tile per wave, one wave per SIMD, accumulators
                                                    //    in AGPRs;  8: 2 x 4, 128 x 64 per wave, two waves per SIMD

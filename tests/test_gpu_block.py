@@ -14,6 +14,7 @@ from gta_amd import fused, layers, synth
 from gta_amd.native import GtaError
 from gta_amd import native_block as nb
 from tests import _hip_cases as C
+from tests import _philox
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -28,6 +29,11 @@ def _err(a, b):
                                     (41, 180), (6, 4), (17, 1020), (3, 2044)])
 @pytest.mark.parametrize("xdt,ydt", [(torch.float32, BF), (torch.float32, torch.float32), (BF, BF)])
 def test_layernorm_forward_backward(rows, d, xdt, ydt):
+    _check_layernorm(rows, d, xdt, ydt)
+
+
+def _check_layernorm(rows, d, xdt, ydt):
+    """ln_fwd and ln_bwd against fp64 F.layer_norm + autograd (also run at larger row counts by tests/test_gpu_block_regimes.py)"""
     g = torch.Generator(device=DEV).manual_seed(rows * 7 + d)
     x = (torch.randn(rows, d, device=DEV, generator=g) * 1.7 + 0.4).to(xdt)
     gam = torch.randn(d, device=DEV, generator=g) * 0.3 + 1.0
@@ -143,27 +149,28 @@ def test_gemm_epilogues(cdt):
             nb.gemm(a, W, trans_b=True, epilogue=nb.EPI_BIAS, bias=b.to(BF), out_dtype=torch.float32)
 
 
-def _transformer(cross, seed=0, dim=128):
+def _transformer(cross, seed=0, dim=128, heads=2, B=2, V=3, hw=6, tq=40, kv_dim=96):
+    """Two layers of `heads` heads of 64 channels on B scenes of V views of hw x hw tokens (cross: `tq` query tokens per scene,
+    a `kv_dim`-wide z)."""
     torch.manual_seed(seed)
     f_dims = {"triv": 0, "se3": 32, "so3": 0, "so2": 32}
     ak = {"f_dims": f_dims, "so2": 8, "so3": 0, "max_freq_h": 1, "max_freq_w": 1}
-    tr = gta_amd.Transformer(dim, 2, 2, 64, 2 * dim, 0.0, not cross, 96 if cross else None, False,
+    tr = gta_amd.Transformer(dim, 2, heads, 64, 2 * dim, 0.0, not cross, kv_dim if cross else None, False,
                              {"method": {"name": "gta", "args": ak}}).to(DEV)
     for n, p in tr.named_parameters():                      # biases and norms away from their trivial initial values
         if n.endswith("bias") or "norm" in n:
             with torch.no_grad():
                 p.add_(torch.randn_like(p) * 0.1)
-    B, V, hw = 2, 3, 6
     gen = torch.Generator().manual_seed(3)
     ex = {"input_transforms": synth.random_extrinsics(B, V, gen).to(DEV),
           "input_coord": torch.rand(B, V, hw, hw, 2, generator=gen).to(DEV)}
     gta_amd.pre_compute_reps_encoder(ak, ex)
     if cross:
         ex["target_transforms"] = synth.random_extrinsics(B, 1, gen).to(DEV)
-        ex["target_coord"] = torch.rand(B, 40, 2, generator=gen).to(DEV)
+        ex["target_coord"] = torch.rand(B, tq, 2, generator=gen).to(DEV)
         gta_amd.pre_compute_reps_decoder(ak, ex)
-    x = torch.randn(B, 40 if cross else V * hw * hw, dim, device=DEV)
-    z = torch.randn(B, V * hw * hw, 96, device=DEV) if cross else None
+    x = torch.randn(B, tq if cross else V * hw * hw, dim, device=DEV)
+    z = torch.randn(B, V * hw * hw, kv_dim, device=DEV) if cross else None
     return tr, ex, x, z
 
 
@@ -210,6 +217,64 @@ def test_fused_transformer_matches_modulewise(cross, dim, autocast):
         if n.endswith("trans_coeff"):
             continue                                               # cancellation-dominated scalar (operator tests)
         assert st["max_abs"] <= (8e-2 if autocast else 4e-2) * max(st["ref_max"], 1e-3) + 1e-5, (n, st)
+
+
+@pytest.mark.parametrize("cross", [False, True])
+def test_fused_transformer_matches_modulewise_on_the_training_path(cross):
+    """test_fused_transformer_matches_modulewise under autocast at the smallest shape on which the layer runs what the MSN model
+    trains with: dim 256, 4 heads of 64, mlp 512, 34 scenes of 2 views of 8 x 8 tokens (cross: 128 query tokens, a 256-wide z) =
+    4352 rows.  A multiple of 32 with every Linear a multiple of 256 wide, so every weight gradient of the fused functions
+    comes from the hand-written kernel (`nb.wgrad`; spied on: to_qkv / to_q, to_out and the two feed-forward layers of each
+    layer), and more than 4096 rows, so the LayerNorm backward runs under its capped grid (1024 partials, two rows per wave).
+
+    Bars: those of test_fused_transformer_matches_modulewise (set at 216 rows).  The module-by-module path under autocast is
+    measured against the same fp32 yardstick in this test; where ITS error is above half of a bar, that quantity's bar is
+    twice the module path's error -- never anything derived from the fused path.  Measured at this shape on an MI355X
+    (module path | fused path | bar of the 216-row test; self-attention, cross-attention):
+        y, rel_rms              3.13e-3 | 2.87e-3 | 3e-2        3.09e-3 | 2.84e-3 | 3e-2
+        dx, rel_rms             3.53e-3 | 3.51e-3 | 6e-2        3.36e-3 | 3.34e-3 | 6e-2
+        parameter gradients     max |error| of either path is at most 0.12 of its bar (8e-2 max |ref| + 1e-5) for every parameter
+    so the module path is nowhere above half of a bar and every bar here is the 216-row test's."""
+    tr, ex, x, z = _transformer(cross, dim=256, heads=4, B=34, V=2, hw=8, tq=128, kv_dim=256)
+    rows = x.shape[0] * x.shape[1]
+    assert rows == 4352 and rows % 32 == 0 and rows > 4096
+    assert nb.lib().gta_ln_bwd_workspace_bytes(rows, 256) / (8 * 256) == 1024
+    y0, dx0, g0 = _run(tr, ex, x, z, False, False)                 # fp32 module-by-module: the yardstick
+    ym, dxm, gm = _run(tr, ex, x, z, False, True)                  # the module path under autocast: what bf16 costs at this shape
+    ln_calls, wgrad_calls = [], []
+    orig_ln, orig_wgrad = nb.ln_fwd, nb.wgrad
+    nb.ln_fwd = lambda *a, **k: (ln_calls.append(1), orig_ln(*a, **k))[1]
+    nb.wgrad = lambda g, a, want_bias: (wgrad_calls.append((g.shape[0], g.shape[1], a.shape[1])), orig_wgrad(g, a, want_bias))[1]
+    try:
+        y1, dx1, g1 = _run(tr, ex, x, z, True, True)
+    finally:
+        nb.ln_fwd, nb.wgrad = orig_ln, orig_wgrad
+    assert len(ln_calls) == 4
+    per_layer = [(rows, 256 if cross else 768, 256), (rows, 256, 256), (rows, 512, 256), (rows, 256, 512)]   # to_q(kv), to_out, net[0], net[3]
+    assert sorted(wgrad_calls) == sorted(per_layer * 2), wgrad_calls
+
+    def bar_for(name, module_err, bar):
+        print(f"FUSED_4352 cross={cross} {name}: module path {module_err:.3e} | bar at 216 rows {bar:.3e}")
+        return bar if module_err <= 0.5 * bar else 2.0 * module_err
+
+    rel, missed = 3e-2, []
+    for name, got, mod, want, bar in (("y", y1, ym, y0, rel), ("dx", dx1, dxm, dx0, 2 * rel)):
+        st, sm = C.err_stats(got.cpu(), want.cpu()), C.err_stats(mod.cpu(), want.cpu())
+        bar = bar_for(name, sm["rel_rms"], bar)
+        print(f"FUSED_4352 cross={cross} {name}: fused path {st['rel_rms']:.3e} | bar {bar:.3e}")
+        if not (st["finite"] and sm["finite"] and st["rel_rms"] < bar):
+            missed.append((name, st, bar))
+    for n in g0:
+        st, sm = C.err_stats(g1[n].float().cpu(), g0[n].cpu()), C.err_stats(gm[n].float().cpu(), g0[n].cpu())
+        if not (st["finite"] and sm["finite"]):
+            missed.append((n, st, sm))
+        if n.endswith("trans_coeff"):
+            continue                                               # cancellation-dominated scalar (operator tests)
+        bar = bar_for(n, sm["max_abs"], 8e-2 * max(st["ref_max"], 1e-3) + 1e-5)
+        print(f"FUSED_4352 cross={cross} {n}: fused path {st['max_abs']:.3e} | bar {bar:.3e} | ref_max {st['ref_max']:.3e}")
+        if not st["max_abs"] <= bar:
+            missed.append((n, st, bar))
+    assert not missed, missed                                      # (every figure is printed before the first one can fail)
 
 
 def test_fused_path_is_taken_and_launch_count():
@@ -308,10 +373,13 @@ def test_packed_projection_gradient_matches_separate_tensors():
             assert same(kv.grad[:, :, i].permute(0, 2, 1, 3), t.grad), (dt, "kv", i)
 
 
-@pytest.mark.parametrize("m,n,k", [(256, 256, 256), (1280, 512, 256), (4160, 768, 256), (64, 256, 512), (40960, 768, 768)])
+@pytest.mark.parametrize("m,n,k", [(256, 256, 256), (1280, 512, 256), (4160, 768, 256), (64, 256, 512), (40960, 768, 768),
+                                   (32, 256, 256), (96, 256, 256), (160, 256, 256), (192, 512, 256), (224, 256, 512), (544, 256, 256)])
 def test_wgrad_kernel(m, n, k):
     """The hand-written TN weight-gradient kernel (gta_wgrad) against fp64, with and without the fused bias gradient,
-    on strided operands (slices of wider matrices, as the packed projections are)."""
+    on strided operands (slices of wider matrices, as the packed projections are).  The second line of shapes walks the
+    boundaries of the DMA ring (WG_NSTAGE = 4 stages, 32 rows per step): one split of 1 and 3 steps (a prologue shorter
+    than the ring), of 5, 6 and 7 (one to three steady steps, then four tail steps), and two splits of 9 and 8."""
     g = torch.Generator(device=DEV).manual_seed(m + n + k)
     G = torch.randn(m, n + 64, device=DEV, generator=g).to(BF)[:, 32:32 + n]
     X = torch.randn(m, k + 8, device=DEV, generator=g).to(BF)[:, :k]
@@ -354,6 +422,7 @@ def test_dropout_kernels():
     n = (1 << 20)
     for p in (0.01, 0.3):
         m = _mask((n,), p, 1234)
+        assert torch.equal(m > 0, torch.from_numpy(_philox.keep_mask(n, p, 1234)).to(DEV))      # the host Philox (tests/_philox.py)
         kept = (m > 0).float().mean().item()
         assert abs(kept - (1 - p)) < 4 * (p * (1 - p) / n) ** 0.5 + 1e-4, (p, kept)
         assert torch.all((m == 0) | ((m - 1 / (1 - p)).abs() < 1e-6))

@@ -4,7 +4,9 @@
 Shapes are those of tests/test_gpu_key_views.py: 5 scenes, 2 heads, 13 views of 20 tokens, `clevrtr/gta` (dh 64) and `msn/gta_so3` (dh 96), a
 decoder leg of 150 query rows and an encoder leg of 260; test 8 has 20 views of 8 tokens.  The merge kernels are checked alone at
 n in {1, 2, 3, 8} partials and dh in {8, 64, 96, 128} (1, 2, 8, 12, 16, 24, 32 sixteen-byte units per row: every lane-group width) on 900 rows
-(no multiple of the rows a workgroup takes per step).
+(no multiple of the rows a workgroup takes per step), and past the cap of their grid (`merge_grid`: 2048 workgroups) at 3 partials on
+32 811 to 1 049 859 rows, one size per lane-group width 32, 16, 16, 1: two full sweeps, five more steps and a ragged step of 3 rows, with a row
+without keys (and NaN in its out row) in each of those regions (test_merge_past_the_grid_cap).
 
 Bars (none new).  Merge against its fp64 formula: 1e-5 of max |ref| for fp32 operands (fp32 arithmetic: a few ulp of the largest term), one
 bf16 rounding (2^-8 |ref| + 1e-6) for bf16 ones.  Attention against the fp64 oracle: forward REL_MAX / REL_RMS and the 2e-2 LSE bar of
@@ -99,11 +101,20 @@ MB, MH, MT = 2, 3, 150
 
 @functools.lru_cache(maxsize=None)
 def _partials(n, dh, dtype):
+    return _partials_of(n, dh, dtype, MB, MH, MT)
+
+
+def _partials_of(n, dh, dtype, MB, MH, MT, empty=None):
     """n partial attentions as strided views of [B,Tq,H,dh] memory (masters on the CPU, rounded to dtype), weights for a loss, and the fp64
-    formula with its autograd gradients"""
+    formula with its autograd gradients.  `empty` = (i, [(b, h, t), ...]): partial i saw no key on those rows (lse_i = -inf; its out_i row is
+    zero in these masters, so the formula stays finite: the caller puts NaN there on the device)"""
     g = torch.Generator().manual_seed(1000 * n + dh)
     outs = [torch.randn(MB, MT, MH, dh, generator=g).to(dtype).float() for _ in range(n)]
     lses = [3.0 * torch.randn(MB, MH, MT, generator=g) for _ in range(n)]
+    if empty is not None:
+        for b_, h_, t_ in empty[1]:
+            outs[empty[0]][b_, t_, h_] = 0.0
+            lses[empty[0]][b_, h_, t_] = float("-inf")
     w, u = torch.randn(MB, MT, MH, dh, generator=g).to(dtype).float(), torch.randn(MB, MH, MT, generator=g)
     o64 = [t.double().permute(0, 2, 1, 3).requires_grad_() for t in outs]
     l64 = [t.double().requires_grad_() for t in lses]
@@ -151,6 +162,43 @@ def test_merge_forward_and_backward_vs_fp64_formula(n, dh, dtype):
     for i in range(n):
         _close(outs[i].grad, p.d_outs[i], dtype, f"dout_{i}")
         _close(lses[i].grad, p.d_lses[i], torch.float32, f"dlse_{i}")
+
+
+@pytest.mark.parametrize("dh,dtype,rpb", [(128, torch.float32, 8), (96, torch.bfloat16, 16), (64, torch.float32, 16), (8, torch.bfloat16, 256)])
+def test_merge_past_the_grid_cap(dh, dtype, rpb):
+    """`merge_grid` caps at 2048 workgroups of rpb = 256 / (lane-group width) rows per step: R = 2 2048 rpb + 5 rpb + 3 rows are two full
+    sweeps of the grid, five more steps and a ragged step of 3 rows (in the backward every lane of that workgroup still takes the step).
+    The fp64 formula and the `_close` bars of test_merge_forward_and_backward_vs_fp64_formula with both dout and dlse; one row of each region
+    (first sweep, second sweep, ragged step) is without keys in partial 1, whose out row holds NaN there, as in
+    test_merge_selects_out_partials_without_keys."""
+    Hh, n = 3, 3
+    U = dh * (2 if dtype == torch.bfloat16 else 4) // 16
+    assert rpb == 256 >> (U - 1).bit_length()                # (the lane group of gta_merge.hip's merge_map)
+    R = 2 * 2048 * rpb + 5 * rpb + 3
+    assert R % Hh == 0
+    Tq = R // Hh
+    empty_rows = [7, 2048 * rpb + 11, R - 2]                 # in memory order: row r is (t, h) = (r // H, r % H)
+    empty = [(0, r % Hh, r // Hh) for r in empty_rows]
+    p = _partials_of(n, dh, dtype, 1, Hh, Tq, empty=(1, empty))
+    mem = [t.to(dtype).cuda() for t in p.outs]               # [B,Tq,H,dh]
+    for b_, h_, t_ in empty:
+        mem[1][b_, t_, h_] = float("nan")
+    outs = [t.permute(0, 2, 1, 3).requires_grad_() for t in mem]
+    lses = [t.cuda().requires_grad_() for t in p.lses]
+    out, lse = gta_amd.gta_attention_merge(outs, lses)
+    ((out.float() * p.w.cuda().permute(0, 2, 1, 3)).sum() + (lse * p.u.cuda()).sum()).backward()
+    torch.cuda.synchronize()
+    assert out.dtype == dtype and tuple(out.shape) == (1, Hh, Tq, dh) and tuple(lse.shape) == (1, Hh, Tq)
+    assert not torch.isnan(out).any() and not torch.isnan(lse).any()
+    _close(out, p.ref_out, dtype, "out")
+    lse_err = (lse.double().cpu() - p.ref_lse).abs()
+    assert bool((lse_err <= 1e-5 * p.ref_lse.abs().clamp_min(1.0)).all()), lse_err.max().item()
+    for i in range(n):
+        assert not torch.isnan(outs[i].grad).any() and not torch.isnan(lses[i].grad).any(), i
+        _close(outs[i].grad, p.d_outs[i], dtype, f"dout_{i}")
+        _close(lses[i].grad, p.d_lses[i], torch.float32, f"dlse_{i}")
+    for b_, h_, t_ in empty:
+        assert bool((outs[1].grad[b_, h_, t_] == 0).all()) and lses[1].grad[b_, h_, t_].item() == 0.0, (h_, t_)
 
 
 def test_merge_with_one_output_unused():
