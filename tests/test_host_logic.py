@@ -10,6 +10,7 @@ import torch
 import gta_amd
 from gta_amd import native
 from tests import _golden as G
+from tests._images import swz          # the Python model of swz<UNITS>() in gta_amd/csrc/gta_common.h: one definition for the suite
 
 
 def test_library_exports_every_declared_symbol():
@@ -113,18 +114,6 @@ B128_GROUPS = [
     [32, 33, 34, 35, 44, 45, 46, 47, 52, 53, 54, 55, 56, 57, 58, 59],
     [36, 37, 38, 39, 40, 41, 42, 43, 48, 49, 50, 51, 60, 61, 62, 63],
 ]
-
-
-def swz(units, r, u):
-    """Python model of swz<UNITS>() in gta_amd/csrc/gta_common.h."""
-    if units == 8:
-        rot = 4 * ((r >> 1) & 1) + ((r >> 2) & 3)
-    elif units == 16:
-        rot = 4 * (r & 3) + ((r >> 2) & 3)
-    else:
-        tz = 4 if units % 16 == 0 else 3 if units % 8 == 0 else 2 if units % 4 == 0 else 1 if units % 2 == 0 else 0
-        rot = (r >> (4 - tz)) & ((1 << tz) - 1)
-    return (u + rot) % units
 
 
 @pytest.mark.parametrize("units", [4, 8, 12, 16, 24, 32])
