@@ -13,8 +13,9 @@ What this file guarantees on the CPU (run by `make` and by tests/test_host_logic
     with and without forced rebase steps): every MFMA sees exactly the fragments / P words / accumulators it must,
     every score is exponentiated, summed and packed exactly once, no register is overwritten while a consumer is
     outstanding, every LDS read is behind its DMA's wait + barrier and every use of a read behind its lgkmcnt wait;
-  * the manual wait-state rules of the ISA on that same order (XDL write -> VALU read, VALU write -> XDL read,
-    transcendental forwarding, permlane, M0 -> LDS-DMA).
+  * the manual wait-state rules of the ISA on that same order: isa_model.check_wait_states, the one table every generated
+    stream goes through (the MFMAs here carry their operand lists for it).
+The instruction type, the control instructions and the emission helpers are isa_model.py's.
 Numerical parity is the GPU tests' job (tests/test_gpu_forward.py runs every fixture through this kernel).
 
 Register map (dh = 96: KS = 6 k-steps, DB = 3 channel blocks, RB = 2 row blocks of 32 query rows per wave)
@@ -31,7 +32,8 @@ Register map (dh = 96: KS = 6 k-steps, DB = 3 channel blocks, RB = 2 row blocks 
   its last MFMA (the XDL-write -> VALU-read distance: hipcc places no wait states behind inline asm).
 """
 import argparse
-import sys
+
+from isa_model import CheckError, Ins, barrier, branch, check_wait_states, clobber_list, label, nop, wait, write_macro
 
 RB = 2
 KS, DB, CHP = 6, 3, 12       # dh = 96 (configure() below: dh = 64 -> 4, 2, 8)
@@ -189,49 +191,14 @@ S_KPTR_LO, S_KPTR_HI, S_VPTR_LO, S_VPTR_HI = "s90", "s91", "s92", "s93"
 S_NM1, S_NMR, S_NMR1 = "s94", "s95", "s96"           # n-1, n-R, n-R+1
 
 
-class Ins:
-    __slots__ = ("text", "kind", "rd", "wr", "sem", "label", "target")
-
-    def __init__(self, text, kind, rd=(), wr=(), sem=None, label=None, target=None):
-        self.text, self.kind, self.rd, self.wr, self.sem = text, kind, tuple(rd), tuple(wr), sem
-        self.label, self.target = label, target
-
-    def __repr__(self):
-        return self.text
-
-
-def nop(n):
-    return Ins(f"s_nop {n - 1}", "nop", sem=("nop", n))
-
-
-def lgkm(n):
-    return Ins(f"s_waitcnt lgkmcnt({n})", "wait", sem=("lgkm", n))
-
-
-def vmw(n):
-    return Ins(f"s_waitcnt vmcnt({n})", "wait", sem=("vm", n))
-
-
-def barrier():
-    return Ins("s_barrier", "barrier", sem=("barrier",))
-
-
 def ready(regs):
     """scheduling hint for insert_waits: all of `regs` must have landed here (one counted wait for a group of fragments
     instead of one in front of each MFMA that first uses one of them)"""
     return Ins("", "ready", regs, (), None)
 
 
-def label(name):
-    return Ins(f"{name}:", "label", label=name)
-
-
 def salu(text, rd=(), wr=(), sem=None):
     return Ins(text, "salu", rd, wr, sem)
-
-
-def branch(text, target, sem):
-    return Ins(f"{text} {target}", "branch", sem=sem, target=target)
 
 
 class Gen:
@@ -261,22 +228,28 @@ class Gen:
         return Ins(f"ds_read_b64_tr_b16 {V(sl, d, half)}, {VOFF[d][half]} offset:{off}", "ds", [VOFF[d][half]],
                    Vregs(sl, d, half), ("ds_v", slot, sl, d, half))
 
+    @staticmethod
+    def mfma(text, d, a, b, c, sem):
+        """v_mfma_f32_32x32x16_bf16 d, a, b, c with the register lists behind the operand texts (c: 0 for a zero C): fx tells the
+        wait-state table an A / B operand from C"""
+        return Ins("v_mfma_f32_32x32x16_bf16 " + text, "mfma", a + b + (c or []), d, sem, ("mfma", d, a, b, c))
+
     def qk(self, p, rb, hh, ks, tile_rel, c_zero=False):
         c = "0" if c_zero else (MS(rb) if ks == 0 else S(p, rb, hh))
-        rd = Kregs(ks, hh) + Qregs(rb, ks) + ([] if c_zero else (MSregs(rb) if ks == 0 else Sregs(p, rb, hh)))
-        return Ins(f"v_mfma_f32_32x32x16_bf16 {S(p, rb, hh)}, {K(ks, hh)}, {Q(rb, ks)}, {c}", "mfma", rd, Sregs(p, rb, hh),
-                   ("qk", p, rb, hh, ks, tile_rel, c_zero))
+        cregs = 0 if c_zero else (MSregs(rb) if ks == 0 else Sregs(p, rb, hh))
+        return self.mfma(f"{S(p, rb, hh)}, {K(ks, hh)}, {Q(rb, ks)}, {c}", Sregs(p, rb, hh), Kregs(ks, hh), Qregs(rb, ks), cregs,
+                         ("qk", p, rb, hh, ks, tile_rel, c_zero))
 
     def pv(self, p, sl, d, rb):
         hh, t = sl >> 1, sl & 1
-        return Ins(f"v_mfma_f32_32x32x16_bf16 {O(rb, d)}, {V(sl, d)}, {P(p, rb, hh, t)}, {O(rb, d)}", "mfma",
-                   Vregs(sl, d) + Pregs(p, rb, hh, t) + Oregs(rb, d), Oregs(rb, d), ("pv", p, sl, d, rb))
+        return self.mfma(f"{O(rb, d)}, {V(sl, d)}, {P(p, rb, hh, t)}, {O(rb, d)}", Oregs(rb, d), Vregs(sl, d), Pregs(p, rb, hh, t), Oregs(rb, d),
+                         ("pv", p, sl, d, rb))
 
     def pl(self, p, sl, rb):
         """l^T[rb] += 1 (32 x 16) P (16 keys of slab sl x 32 rows): every output row is the rows' sum over the slab's keys"""
         hh, t = sl >> 1, sl & 1
-        return Ins(f"v_mfma_f32_32x32x16_bf16 {Lacc(rb)}, {ONES}, {P(p, rb, hh, t)}, {Lacc(rb)}", "mfma",
-                   ONESregs() + Pregs(p, rb, hh, t) + Lregs(rb), Lregs(rb), ("pl", p, sl, rb))
+        return self.mfma(f"{Lacc(rb)}, {ONES}, {P(p, rb, hh, t)}, {Lacc(rb)}", Lregs(rb), ONESregs(), Pregs(p, rb, hh, t), Lregs(rb),
+                         ("pl", p, sl, rb))
 
     def pv_list(self, c):
         """the P V MFMAs of a step in issue order: per slab (d, rb) pairs, then (msum) the slab's two row-sum MFMAs"""
@@ -361,7 +334,7 @@ class Gen:
         out = []
         # landed before this step: with R = 4 everything but the last two boundaries' requests (K'(j+2), V'(j+1) and older);
         # with R = 2 everything (K'(j+1), V'(j) were requested one boundary ago)
-        out.append(vmw(2 * NP if R == 4 else 0))
+        out.append(wait(vm=2 * NP if R == 4 else 0))
         out.append(barrier())
         out += self.dma_requests(c)
         return out
@@ -658,9 +631,9 @@ class Gen:
             out.append(Ins(f"v_mov_b32 {T[0]}, 0x3f803f80", "valu", [], [T[0]]))
             for r in ONESregs():
                 out.append(Ins(f"v_accvgpr_write_b32 {r}, {T[0]}", "valu", [T[0]], [r]))
-        out.append(lgkm(0))
+        out.append(wait(lgkm=0))
         # tile 0 (and whatever else of this item's first tiles was requested by the previous item / the kernel prologue)
-        out.append(vmw(0))
+        out.append(wait(vm=0))
         out.append(barrier())
         out.append(Ins("", "pseudo", sem=("item_begin",)))
         for ks in range(KS):
@@ -722,7 +695,7 @@ class Gen:
         # ---- slow continuations: O += V'(j) P(j) alone, rebase for tile j + 1, its hh = 0 half, on to the next step ----
         for c in range(R):
             out.append(label(L(f"slow{c}")))
-            out.append(lgkm(0))
+            out.append(wait(lgkm=0))
             out += self.phase_b(c, plain=True)
             out += self.rebase((c + 1) & 1, False, 1, uid=f"_c{c}")
             out += self.exph0_plain((c + 1) & 1, 1)
@@ -730,7 +703,7 @@ class Gen:
             out.append(branch("s_branch", L(f"step{(c + 1) % R}"), ("br_always",)))
         # ---- last step ----
         out.append(label(L("tail")))
-        out.append(lgkm(0))
+        out.append(wait(lgkm=0))
         out += self.tail_step()
         out.append(nop(16))                   # the last XDL writes of O retire before the epilogue's v_accvgpr_read
         for rb in range(RB):
@@ -788,7 +761,7 @@ def insert_waits(prog, carry=True, seed_state=None):
                     pend = [set(x) for x in step_state]
             else:
                 if pend and fallthrough:
-                    out.append(lgkm(0))
+                    out.append(wait(lgkm=0))
                 pend = []
             out.append(ins)
             prev = ins
@@ -798,7 +771,7 @@ def insert_waits(prog, carry=True, seed_state=None):
             to_step = ins.target.startswith("L_step")
             rare = ins.target.startswith("L_slow") or ins.target.startswith("L_tail")     # (those blocks start with lgkmcnt(0))
             if pend and ((uncond and not (to_step and carry)) or (not uncond and not rare)):
-                out.append(lgkm(0))
+                out.append(wait(lgkm=0))
                 pend = []
             if uncond and to_step and carry and pend:
                 if step_state is None:
@@ -808,9 +781,8 @@ def insert_waits(prog, carry=True, seed_state=None):
             out.append(ins)
             prev = ins
             continue
-        if ins.kind == "wait" and ins.sem[0] == "lgkm":
-            n = ins.sem[1]
-            del pend[:max(0, len(pend) - n)]
+        if ins.kind == "wait" and ins.fx[2] is not None:
+            del pend[:max(0, len(pend) - ins.fx[2])]
             out.append(ins)
             prev = ins
             continue
@@ -818,7 +790,7 @@ def insert_waits(prog, carry=True, seed_state=None):
         i = need(touched)
         if i >= 0:
             left = min(len(pend) - 1 - i, 15)            # (the counter has four bits)
-            out.append(lgkm(left))
+            out.append(wait(lgkm=left))
             del pend[:len(pend) - left]
         if ins.kind == "ready":
             continue
@@ -827,7 +799,7 @@ def insert_waits(prog, carry=True, seed_state=None):
             pend.append(set(ins.wr))
         prev = ins
     if pend:
-        out.append(lgkm(0))
+        out.append(wait(lgkm=0))
     if carry and seed_state is None and step_state is not None:
         return insert_waits(prog, carry=True, seed_state=step_state)      # second pass: the head's way into step 0 knows the state too
     return out
@@ -836,10 +808,6 @@ def insert_waits(prog, carry=True, seed_state=None):
 # ------------------------------------------------------------------------------------------------------------------
 # checker: dynamic order of one wave, typed registers, counters, wait states
 # ------------------------------------------------------------------------------------------------------------------
-class CheckError(Exception):
-    pass
-
-
 class Sim:
     def __init__(self, gen, prog, n_tiles, rebase_at=(), has_tail=False, items=2, first_rebase=True):
         self.g, self.prog, self.n, self.rebase_at, self.has_tail, self.items = gen, prog, n_tiles, set(rebase_at), has_tail, items
@@ -925,7 +893,7 @@ class Sim:
             if cur.kind == "label":
                 continue
             stats["instr"] += 1
-            self.check_wait_states(cur)
+            check_wait_states(self.hist, cur)
             sem = cur.sem
             k = cur.kind
             # any access to a register with an outstanding LDS read
@@ -940,14 +908,12 @@ class Sim:
             op = sem[0]
             if op == "nop":
                 pass
-            elif op == "lgkm":
-                keep = sem[1]
-                while len(pend_ds) > keep:
+            elif op == "waitcnt":
+                vm, lgkm = sem[1:]
+                while lgkm is not None and len(pend_ds) > lgkm:
                     for r in pend_ds.pop(0):
                         pending_regs.discard(r)
-            elif op == "vm":
-                keep = sem[1]
-                while len(self.vmq) > keep:
+                while vm is not None and len(self.vmq) > vm:
                     self.land(self.vmq.pop(0))
             elif op == "barrier":
                 # every wave has waited for its share of the same tiles: a tile whose three pieces of THIS wave have landed
@@ -1195,40 +1161,6 @@ class Sim:
             self.fail(f"rebased tiles {sorted(rebased_tiles)} != {sorted(want)}")
         return sc["kptr"], sc["vptr"]
 
-    # -- manual wait states (cdna4 ISA 4.5; LLVM GCNHazardRecognizer gfx940 rows), conservative: every instruction = 1 state --
-    def check_wait_states(self, cur):
-        if cur.kind in ("label", "pseudo"):
-            return
-        dist = 0
-        for prev in reversed(self.hist):
-            if prev.kind == "pseudo":
-                continue
-            need = 0
-            if prev.kind == "mfma" and cur.kind != "mfma":
-                if set(prev.wr) & (set(cur.rd) | set(cur.wr)):
-                    need = 12                                    # XDL (8 pass) write -> VALU / LDS read or write (ISA: 11)
-            elif prev.kind == "mfma" and cur.kind == "mfma":
-                ov = set(prev.wr) & set(cur.rd)
-                if ov and not (set(prev.wr) == set(cur.wr) and ov == set(prev.wr)):
-                    need = 12                                    # XDL write -> XDL read as A / B (or a different C)
-            elif prev.kind in ("valu", "trans", "perm") and cur.kind == "mfma":
-                if set(prev.wr) & set(cur.rd):
-                    need = 2                                     # VALU write -> XDL read
-            elif prev.kind == "trans" and cur.kind in ("valu", "perm"):
-                if set(prev.wr) & set(cur.rd):
-                    need = 1                                     # transcendental forwarding
-            elif prev.kind in ("valu", "trans") and cur.kind == "perm":
-                if set(prev.wr) & set(cur.rd):
-                    need = 2
-            elif prev.kind == "salu" and cur.kind == "dma":
-                if "m0" in prev.wr:
-                    need = 1
-            if need and dist < need:
-                raise CheckError(f"wait states: '{cur.text}' needs {need} states after '{prev.text}', has {dist}")
-            dist += prev.sem[1] if (prev.kind == "nop") else 1
-            if dist > 20:
-                break
-
 
 def stats_of(gen, prog):
     """static listing: instructions per MFMA gap of the steady-state step copies"""
@@ -1262,12 +1194,7 @@ def emit(progs, path):
     with open(path, "w") as f:
         f.write("// generated by gen_attn64.py (python3 gen_attn64.py --out gta_attn64_loop.inc) -- do not edit\n")
         for name, prog in progs.items():
-            f.write(f"#define {name} \\\n")
-            for ins in prog:
-                if ins.kind == "pseudo":
-                    continue
-                f.write(f'    "{ins.text}\\n\\t" \\\n')
-            f.write('    ""\n')
+            write_macro(f, name, prog)
         # Per head dimension: what the statement TAKES in the accumulator file (the Q' fragments, written by the compiled prologue) and what it
         # LEAVES there (O) are operands of the statement by register -- "+{a[124:127]}"(qfr[0][0]), "={a[28:43]}"(oacc[0][0]) -- so hipcc knows
         # what lives where on both sides (r05; before, literal v_accvgpr_write / _read statements beside it did the hand-off behind its back);
@@ -1278,7 +1205,7 @@ def emit(progs, path):
             left = [(f"oacc[{rb}][{d}]", AB + 16 * (rb * DB + d), 16) for rb in range(RB) for d in range(DB)]
             named = {a0 + i for _, a0, n in taken + left for i in range(n)}
             regs = [f"v{i}" for i in range(32, 256)] + [f"a{i}" for i in range(AB, 256) if i not in named] + [f"s{i}" for i in range(84, 97)]
-            f.write(f"#define GTA_ATTN64_CLOBBERS_{dh} \\\n    " + ", ".join(f'"{r}"' for r in regs) + ', "m0", "vcc", "scc", "memory"\n')
+            f.write(f"#define GTA_ATTN64_CLOBBERS_{dh} \\\n    " + clobber_list(regs) + "\n")
             f.write(f"#define GTA_ATTN64_RESULTS_{dh} \\\n    " + ", ".join(f'"={{a[{a0}:{a0 + n - 1}]}}"({lv})' for lv, a0, n in left) + "\n")
             f.write(f"#define GTA_ATTN64_QFRAGS_{dh} \\\n    " + ", ".join(f'"+{{a[{a0}:{a0 + n - 1}]}}"({lv})' for lv, a0, n in taken) + "\n")
 

@@ -35,14 +35,12 @@ Register map
   v[248:255]  temporaries               v[0:23], s[0:19] and what the statement names as operands: the compiler's
 """
 import argparse
-import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
-from isa_model import (LANES, Asm, CheckError, Wave, XI, as_u32, bf16_rne, bf16_to_f32, check_wait_states, regs, rtext, u2f)
+from isa_model import (LANES, Asm, CheckError, Wave, as_u32, auto_waits, bf16_rne, bf16_to_f32, check_wait_states, clobber_list,
+                       regs, rtext, u2f, write_macro)
 
 KS, DB, KB, CHP = 6, 3, 2, 12
 ROW = CHP * 16                     # 192 bytes per image row
@@ -663,43 +661,6 @@ def check_dq(verbose=False, cases=((1, 0), (2, 1), (5, 3), (6, 2))):
     return stats
 
 
-def auto_waits(prog):
-    """lgkmcnt waits in front of the first use of every LDS read's destination (LDS operations complete in order); vmcnt waits for the
-    global loads of the head.  Labels and branches sit where nothing is outstanding (the generator's iteration tops)."""
-    out = []
-    lg, vm = [], []
-    for ins in prog:
-        if ins.kind in ("label", "branch"):
-            if lg:
-                raise CheckError(f"LDS operations outstanding at {ins.text}")
-            out.append(ins)
-            continue
-        if ins.kind == "wait":
-            _, nv, nl = ins.fx
-            if nl is not None:
-                del lg[:max(0, len(lg) - nl)]
-            if nv is not None:
-                del vm[:max(0, len(vm) - nv)]
-            out.append(ins)
-            continue
-        touched = set(ins.rd) | set(ins.wr)
-        for q, name in ((lg, "lgkm"), (vm, "vm")):
-            idx = max((i for i, d in enumerate(q) if d & touched), default=-1)
-            if idx >= 0:
-                left = min(len(q) - 1 - idx, 15 if name == "lgkm" else 63)
-                out.append(XI(f"s_waitcnt {'lgkmcnt' if name == 'lgkm' else 'vmcnt'}({left})", "wait",
-                              fx=("waitcnt", left if name == "vm" else None, left if name == "lgkm" else None)))
-                del q[:len(q) - left]
-        out.append(ins)
-        if ins.kind == "ds":
-            lg.append(set(ins.wr))
-        elif ins.kind == "vmem":
-            vm.append(set(ins.wr))
-        elif ins.kind == "dma":
-            vm.append(set())
-    return out
-
-
 # ------------------------------------------------------------------------------------------------------------------
 # numpy model and the simulation
 # ------------------------------------------------------------------------------------------------------------------
@@ -855,41 +816,12 @@ def emit(path, prog, macro="GTA_BWD64_DKV", vops=VOPS, sops=SOPS, results=DKV_RE
         f.write("// generated by gen_bwd64.py (make regen) -- do not edit\n")
         for name, val in (("STAGES", R), ("OFF_STATS", OFF_STATS), ("HI_BASE", HI_BASE)):
             f.write(f"#ifndef GTA_BWD64_{name}\n#define GTA_BWD64_{name} {val}\n#endif\n")
-        f.write(f"#define {macro} \\\n")
-        for ins in prog:
-            if ins.kind != "pseudo":
-                f.write(f'    "{ins.text}\\n\\t" \\\n')
-        f.write('    ""\n')
+        write_macro(f, macro, prog)
         out_regs = {a0 + i for _, a0 in results for i in range(16)}
         regs_ = [f"v{i}" for i in CLOBBER_V] + [f"a{i}" for i in range(256) if i not in out_regs] + [f"s{i}" for i in CLOBBER_S]
-        f.write(f"#define {macro}_CLOBBERS \\\n    " + ", ".join(f'"{r}"' for r in regs_) + ', "m0", "vcc", "scc", "memory"\n')
+        f.write(f"#define {macro}_CLOBBERS \\\n    " + clobber_list(regs_) + "\n")
         f.write(f"#define {macro}_RESULTS \\\n    " + ", ".join(f'"={{a[{a0}:{a0 + 15}]}}"({lv})' for lv, a0 in results) + "\n")
         f.write(f"#define {macro}_OPERANDS \\\n    " + ", ".join(f'[{n}] "v"({n})' for n in vops) + ", \\\n    " + ", ".join(f'[{n}] "s"({n})' for n in sops) + "\n")
-
-
-def assemble_check(prog, vops=VOPS, sops=SOPS):
-    """the text through the assembler alone (operands replaced by registers hipcc could pick): syntax, encodable operands"""
-    rep = {f"%[{n}]": f"v{i}" for i, n in enumerate(vops)}
-    rep.update({f"%[{n}]": f"s{i}" for i, n in enumerate(sops)})
-    lines = [".amdgcn_target \"amdgcn-amd-amdhsa--gfx950\"", ".text", "k:"]
-    for ins in prog:
-        if ins.kind == "pseudo":
-            continue
-        t = ins.text.replace("%=", "0")
-        for k in sorted(rep, key=len, reverse=True):
-            t = t.replace(k, rep[k])
-        lines.append("  " + t)
-    clang = "/opt/rocm/lib/llvm/bin/clang"
-    if not os.path.exists(clang):
-        return None
-    with tempfile.TemporaryDirectory() as td:
-        src = os.path.join(td, "k.s")
-        open(src, "w").write("\n".join(lines) + "\n")
-        r = subprocess.run([clang, "-x", "assembler", "-target", "amdgcn-amd-amdhsa", "-mcpu=gfx950", "-c", src, "-o", os.path.join(td, "k.o")],
-                           capture_output=True, text=True)
-        if r.returncode:
-            raise CheckError("the assembler rejects the stream:\n" + r.stderr[:3000])
-    return True
 
 
 if __name__ == "__main__":

@@ -25,15 +25,12 @@ pointers, O rows and LSE are compared with a numpy model of the C++ code it repl
 dynamic instruction order.  The tile loop inside is gen_attn64.py's own (its typed-dataflow simulation is unchanged).
 """
 import argparse
-import os
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 
 import gen_attn64 as G
-from isa_model import (LANES, Asm, CheckError, Wave, XI, as_u32, bf16_rne, bf16_to_f32, check_wait_states, fma32, regs, rtext, u2f)
+from isa_model import (LANES, Asm, CheckError, Ins, Wave, as_u32, assemble_check, auto_waits, bf16_rne, bf16_to_f32, check_wait_states, clobber_list,
+                       regs, rtext, u2f, write_macro)
 
 # ------------------------------------------------------------------------------------------------------------------
 # shapes and the LDS map (A64<96, GTA_LAYOUT_MS> of gta_fwd64.hip with coalesced item I/O and no view records: the kernel
@@ -127,58 +124,6 @@ def cur(d, k=2):
 
 def nxt(d, k=2):
     return Sr(S_NXT + d, k) if k > 1 else f"s{S_NXT + d}"
-
-
-# ------------------------------------------------------------------------------------------------------------------
-# s_waitcnt for the straight-line parts: LDS operations and vector memory operations complete in order
-# ------------------------------------------------------------------------------------------------------------------
-def auto_waits(prog):
-    out = []
-    lg, vm = [], []            # outstanding operations, oldest first: sets of destination registers (empty for stores / DMA)
-    smem = False
-    for ins in prog:
-        if ins.kind in ("label", "branch"):
-            if lg or smem:
-                raise CheckError(f"LDS / scalar memory operations outstanding at {ins.text}: put an explicit lgkmcnt(0) in front")
-            vm = []            # (what crosses the item loop's back edge is waited for explicitly; the simulation checks it)
-            out.append(ins)
-            continue
-        if ins.kind == "wait":
-            _, nv, nl = ins.fx
-            if nl is not None:
-                del lg[:max(0, len(lg) - nl)]
-                if nl == 0:
-                    smem = False
-            if nv is not None:
-                del vm[:max(0, len(vm) - nv)]
-            out.append(ins)
-            continue
-        touched = set(ins.rd) | set(ins.wr)
-        for q, name in ((lg, "lgkm"), (vm, "vm")):
-            idx = max((i for i, d in enumerate(q) if d & touched), default=-1)
-            if idx >= 0:
-                left = min(len(q) - 1 - idx, 15 if name == "lgkm" else 63)      # (the counters have four / six bits)
-                if name == "lgkm" and smem:
-                    left = 0
-                w = XI(f"s_waitcnt {'lgkmcnt' if name == 'lgkm' else 'vmcnt'}({left})", "wait",
-                       fx=("waitcnt", left if name == "vm" else None, left if name == "lgkm" else None))
-                out.append(w)
-                del q[:len(q) - left]
-                if name == "lgkm" and left == 0:
-                    smem = False
-        out.append(ins)
-        if ins.kind == "ds":
-            lg.append(set(ins.wr))
-        elif ins.kind == "dsw":
-            lg.append(set())
-        elif ins.kind == "smem":
-            smem = True
-            lg.append(set(ins.wr))
-        elif ins.kind == "vmem":
-            vm.append(set(ins.wr))
-        elif ins.kind in ("vmemst", "dma"):
-            vm.append(set())
-    return out
 
 
 class ItemGen:
@@ -670,16 +615,13 @@ class ItemGen:
         for ins in gen.program():
             if ins.sem and ins.sem[0] == "ds_tab":
                 continue
-            if head_vm and ins.kind == "wait" and ins.sem == ("vm", 0):
+            if head_vm and ins.kind == "wait" and ins.fx == ("waitcnt", 0, None):
                 # the loop's own wait for its first tiles: in the item stream the prologue's vmcnt(14) has already seen them land
                 # (they were requested before the item's inputs), and what is still in flight here -- the previous item's O / LSE
                 # stores -- must not hold the loop's first matrix instructions
                 head_vm = False
                 continue
-            text = ins.text
-            for k, v in LOOP_OPERANDS.items():
-                text = text.replace(k, v)
-            out.append(XI(text, ins.kind, ins.rd, ins.wr, None, ins.sem, ins.label, ins.target))
+            out.append(ins.bound(LOOP_OPERANDS))
         return gen, out
 
     def program(self, stub_loop=False, pad4=False):
@@ -716,7 +658,7 @@ class ItemGen:
         a.pseudo("end")
         tail = auto_waits(a.out)
         if stub_loop:
-            mid = [XI("", "pseudo", fx=("pseudo", "loop"))]
+            mid = [Ins("", "pseudo", fx=("pseudo", "loop"))]
         else:
             mid = self.loop_program()[1]
         return head + mid + tail
@@ -1050,11 +992,6 @@ def check(verbose=False, waves=(0, 1, 2, 3), **kw):
 # ------------------------------------------------------------------------------------------------------------------
 # emission
 # ------------------------------------------------------------------------------------------------------------------
-def clobbers():
-    regs_ = [f"v{i}" for i in range(8, 256)] + [f"a{i}" for i in range(256)] + [f"s{i}" for i in CLOBBER_S]
-    return ", ".join(f'"{r}"' for r in regs_) + ', "m0", "vcc", "scc", "memory"'
-
-
 def emit(path, prog, prog_p4=None, prog_ph=None):
     with open(path, "w") as f:
         f.write("// generated by gen_item64.py (make regen) -- do not edit\n")
@@ -1062,50 +999,15 @@ def emit(path, prog, prog_p4=None, prog_ph=None):
                           ("LDS_BYTES", LDS_BYTES), ("D_Q", D_Q), ("D_O", D_O), ("D_CS", D_CS), ("D_LSE", D_LSE), ("D_IMG", D_IMG), ("D_KN", D_KN),
                           ("D_AQ", D_AQ), ("D_V", D_V)):
             f.write(f"#define GTA_ITEM64_{name} {val}\n")
-        f.write("#define GTA_ATTN64_ITEMS \\\n")
-        for ins in prog:
-            if ins.kind == "pseudo":
-                continue
-            f.write(f'    "{ins.text}\\n\\t" \\\n')
-        f.write('    ""\n')
+        write_macro(f, "GTA_ATTN64_ITEMS", prog)
         if prog_p4 is not None:
-            f.write("#ifdef GTA_ATTN64_DIAG\n#define GTA_ATTN64_ITEMS_P4 \\\n")
-            for ins in prog_p4:
-                if ins.kind != "pseudo":
-                    f.write(f'    "{ins.text}\\n\\t" \\\n')
-            f.write('    ""\n')
+            f.write("#ifdef GTA_ATTN64_DIAG\n")
+            write_macro(f, "GTA_ATTN64_ITEMS_P4", prog_p4)
             if prog_ph is not None:
-                f.write("#define GTA_ATTN64_ITEMS_PH \\\n")
-                for ins in prog_ph:
-                    if ins.kind != "pseudo":
-                        f.write(f'    "{ins.text}\\n\\t" \\\n')
-                f.write('    ""\n')
+                write_macro(f, "GTA_ATTN64_ITEMS_PH", prog_ph)
             f.write("#endif\n")
-        f.write("#define GTA_ATTN64_ITEMS_CLOBBERS \\\n    " + clobbers() + "\n")
-
-
-def assemble_check(prog):
-    """the text through the assembler alone (operands replaced by registers hipcc could pick): syntax, encodable operands"""
-    rep = {f"%[{n}]": f"s{i}" for i, n in enumerate(OPERANDS)}
-    lines = [".amdgcn_target \"amdgcn-amd-amdhsa--gfx950\"", ".text", "k:"]
-    for ins in prog:
-        if ins.kind == "pseudo":
-            continue
-        t = ins.text.replace("%=", "0")
-        for k, v in rep.items():
-            t = t.replace(k, v)
-        lines.append("  " + t)
-    clang = "/opt/rocm/lib/llvm/bin/clang"
-    if not os.path.exists(clang):
-        return None
-    with tempfile.TemporaryDirectory() as td:
-        src = os.path.join(td, "k.s")
-        open(src, "w").write("\n".join(lines) + "\n")
-        r = subprocess.run([clang, "-x", "assembler", "-target", "amdgcn-amd-amdhsa", "-mcpu=gfx950", "-c", src, "-o", os.path.join(td, "k.o")],
-                           capture_output=True, text=True)
-        if r.returncode:
-            raise CheckError("the assembler rejects the stream:\n" + r.stderr[:3000])
-    return True
+        regs_ = [f"v{i}" for i in range(8, 256)] + [f"a{i}" for i in range(256)] + [f"s{i}" for i in CLOBBER_S]
+        f.write("#define GTA_ATTN64_ITEMS_CLOBBERS \\\n    " + clobber_list(regs_) + "\n")
 
 
 if __name__ == "__main__":
@@ -1119,6 +1021,6 @@ if __name__ == "__main__":
         if a_.verbose:
             print("item stream without the tile loop:", st)
     full = ItemGen().program()
-    assemble_check(full)
+    assemble_check(full, sops=OPERANDS)
     if a_.out:
         emit(a_.out, full, ItemGen().program(pad4=True), ItemGen(phases=True).program())

@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
-"""isa_model.py -- a small gfx950 assembler DSL and a FUNCTIONAL one-wave simulator for the generated instruction streams of
-gta_attn64 (gen_item64.py: an item's prologue and epilogue around the tile loop of gen_attn64.py).
+"""isa_model.py -- the ISA toolkit under the stream generators (gen_attn64.py: the tile loop of gta_attn64; gen_item64.py: an item's
+prologue and epilogue around that loop; gen_bwd64.py: the backward's dK/dV and dQ walks).  The generators import from here, never
+the other way.
 
-Test infrastructure of the build, not product code: the kernel includes only the TEXT the generators emit.  What this file gives
+Test infrastructure of the build, not product code: the kernels include only the TEXT the generators emit.  What this file gives
 the generators on the CPU (run by tests/test_host_logic.py on every build):
 
+  * `Ins`, the one instruction type of every stream, and one constructor per control instruction (`wait`, `nop`, `barrier`,
+    `label`, `branch`): what they return is readable by every pass and by both simulators.
   * `Asm`: one method per instruction form the streams use.  A call records the assembly text AND an executable description of
     the same instruction (mnemonic + operands), so the text that hipcc assembles and the semantics that are simulated cannot
-    drift apart; `rd` / `wr` register sets feed the wait-state checker of gen_attn64.py.
+    drift apart; `rd` / `wr` register sets feed `check_wait_states` and `auto_waits`.
   * `Wave`: 64 lanes x (256 VGPRs + 256 AGPRs), SGPRs, VCC / EXEC / SCC / M0, a byte-addressed LDS and a flat global memory made of
     registered numpy buffers.  Arithmetic is bit-level (fp32 via numpy, fused multiply-add via float64, bf16 round-to-nearest-even,
     v_mfma_f32_32x32x16_bf16 with the lane layouts of cdna_hip_programming.md section 3: A / B lane (i, kh) holds row / column i,
@@ -16,24 +19,72 @@ the generators on the CPU (run by tests/test_host_logic.py on every build):
     order under vmcnt (scalar loads: out of order, any use needs lgkmcnt(0)).  A load's destination is POISONED from issue until a
     wait covers it -- reading or overwriting it earlier is an error -- so a missing or mis-counted s_waitcnt fails the simulation
     instead of passing by luck, across the item loop's back edge too.
+  * `check_wait_states`: the one table of the wait states the ISA leaves to the program, run by both simulators on the executed
+    order; `auto_waits`: s_waitcnt insertion for straight-line code; the emission helpers (`write_macro`, `clobber_list`,
+    `assemble_check`).
 """
+import os
 import re
 import struct
+import subprocess
+import tempfile
 
 import numpy as np
-
-from gen_attn64 import CheckError, Ins
 
 LANES = 64
 
 
-class XI(Ins):
-    """an instruction with an executable description: fx = (mnemonic, operand, ...)"""
-    __slots__ = ("fx",)
+class CheckError(Exception):
+    pass
 
-    def __init__(self, text, kind, rd=(), wr=(), fx=None, sem=None, label=None, target=None):
-        super().__init__(text, kind, rd, wr, sem, label, target)
-        self.fx = fx
+
+class Ins:
+    """one instruction of a stream.  sem: the typed-dataflow tag that gen_attn64.Sim reads; fx: the executable description
+    (mnemonic, operand, ...) that Wave reads.  A generator fills in the one its simulator needs; control instructions carry both."""
+    __slots__ = ("text", "kind", "rd", "wr", "sem", "fx", "label", "target")
+
+    def __init__(self, text, kind, rd=(), wr=(), sem=None, fx=None, label=None, target=None):
+        self.text, self.kind, self.rd, self.wr, self.sem, self.fx = text, kind, tuple(rd), tuple(wr), sem, fx
+        self.label, self.target = label, target
+
+    def __repr__(self):
+        return self.text
+
+    def bound(self, operands):
+        """a copy with the statement operands {"%[name]": register text} substituted in the text"""
+        text = self.text
+        for k, v in operands.items():
+            text = text.replace(k, v)
+        return Ins(text, self.kind, self.rd, self.wr, self.sem, self.fx, self.label, self.target)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# control instructions: one constructor each, sem == fx
+# ------------------------------------------------------------------------------------------------------------------
+def wait(vm=None, lgkm=None):
+    """s_waitcnt: at most `vm` vector memory / `lgkm` LDS and scalar memory operations stay outstanding (None: not waited for)"""
+    parts = ([f"vmcnt({vm})"] if vm is not None else []) + ([f"lgkmcnt({lgkm})"] if lgkm is not None else [])
+    w = ("waitcnt", vm, lgkm)
+    return Ins("s_waitcnt " + " ".join(parts), "wait", sem=w, fx=w)
+
+
+def nop(n):
+    """n wait states (1..16) in one instruction"""
+    assert 1 <= n <= 16
+    return Ins(f"s_nop {n - 1}", "nop", sem=("nop", n), fx=("nop", n))
+
+
+def barrier():
+    return Ins("s_barrier", "barrier", sem=("barrier",), fx=("barrier",))
+
+
+def label(name):
+    return Ins(f"{name}:", "label", fx=("label", name), label=name)
+
+
+def branch(mn, target, sem=None):
+    """sem: what gen_attn64.Sim decides the branch by (Wave evaluates the mnemonic)"""
+    return Ins(f"{mn} {target}", "branch", ["scc"] if "scc" in mn else [], [], sem, ("branch", mn, target), target=target)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -84,13 +135,13 @@ def rdset(*ops):
 
 
 class Asm:
-    """collects XI instructions; every emitter returns nothing and appends"""
+    """collects instructions; every emitter returns nothing and appends"""
 
     def __init__(self):
         self.out = []
 
-    def add(self, text, kind, rd, wr, fx, **kw):
-        self.out.append(XI(text, kind, rd, wr, fx, **kw))
+    def add(self, text, kind, rd, wr, fx):
+        self.out.append(Ins(text, kind, rd, wr, fx=fx))
 
     def raw(self, ins):
         self.out.append(ins)
@@ -296,27 +347,25 @@ class Asm:
         self.add(f"s_memrealtime {rtext(d2)}", "smem", [], list(d2), ("s_memtime", list(d2)))
 
     def label(self, name):
-        self.out.append(XI(f"{name}:", "label", fx=("label", name), label=name))
+        self.out.append(label(name))
 
     def branch(self, mn, target):
-        self.out.append(XI(f"{mn} {target}", "branch", rdset("scc") if "scc" in mn else [], [], ("branch", mn, target), target=target))
+        self.out.append(branch(mn, target))
 
     def waitcnt(self, vm=None, lgkm=None):
-        parts = ([f"vmcnt({vm})"] if vm is not None else []) + ([f"lgkmcnt({lgkm})"] if lgkm is not None else [])
-        self.out.append(XI("s_waitcnt " + " ".join(parts), "wait", fx=("waitcnt", vm, lgkm)))
+        self.out.append(wait(vm, lgkm))
 
     def nop(self, n):
         while n > 0:
-            k = min(n, 16)
-            self.out.append(XI(f"s_nop {k - 1}", "nop", fx=("nop", k), sem=("nop", k)))
-            n -= k
+            self.out.append(nop(min(n, 16)))
+            n -= 16
 
     def barrier(self):
-        self.out.append(XI("s_barrier", "barrier", fx=("barrier",)))
+        self.out.append(barrier())
 
     def pseudo(self, *fx):
         """no text: a hook for the simulation (checkpoints, stubs)"""
-        self.out.append(XI("", "pseudo", fx=("pseudo",) + tuple(fx)))
+        self.out.append(Ins("", "pseudo", fx=("pseudo",) + tuple(fx)))
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -503,10 +552,9 @@ class Wave:
                 hist.append(ins)
                 if len(hist) > 64:
                     del hist[:32]
-            fx = getattr(ins, "fx", None)
-            if fx is None:
+            if ins.fx is None:
                 raise CheckError(f"instruction without semantics: {ins.text}")
-            tgt = self.step(ins, fx)
+            tgt = self.step(ins, ins.fx)
             if tgt == "__end__":
                 return
             if tgt is not None:
@@ -794,56 +842,148 @@ class Wave:
 # instruction counts as one state, an s_nop N as N + 1.
 # ------------------------------------------------------------------------------------------------------------------
 def check_wait_states(hist, cur):
+    """hist: the instructions executed before `cur`, oldest first (the last 20 states of it are looked at)"""
     if cur.kind in ("label", "pseudo"):
         return
     crd, cwr = set(cur.rd), set(cur.wr)
+    touched = crd | cwr
     dist = 0
     for prev in reversed(hist):
         if prev.kind == "pseudo":
             continue
-        pwr = set(prev.wr)
         need = 0
-        vgpr_w = {r for r in pwr if r[0] in "va"}
-        sgpr_w = {r for r in pwr if r[0] == "s" and r != "scc"}
         if prev.kind == "mfma":
             if cur.kind != "mfma":
-                if pwr & (crd | cwr):
+                if not touched.isdisjoint(prev.wr):
                     need = 12                            # XDL (8 pass) write -> VALU / memory read or write of the result
-                elif set(prev.rd) & cwr:
+                elif not cwr.isdisjoint(prev.rd):
                     need = 8                             # XDL reads its operands over its passes -> overwrite by a later instruction
                     if cur.kind in ("ds", "vmem") and prev.fx is not None and prev.fx[0] == "mfma":
                         # a LOAD's data arrives tens of cycles after it issues, and it issues after the MFMA has (in-order issue): only the C
                         # operand, read late, keeps the margin
                         c16 = prev.fx[4]
-                        if c16 == 0 or not (set(c16) & cwr):
+                        if c16 == 0 or cwr.isdisjoint(c16):
                             need = 0
             else:
-                ov = pwr & crd
-                if ov and not (pwr == cwr and ov == pwr):
+                ov = crd.intersection(prev.wr)
+                if ov and not (ov == cwr and len(ov) == len(prev.wr)):
                     need = 12                            # XDL write -> XDL read as A / B, or as another instruction's C
         elif prev.kind in ("valu", "trans", "perm", "vread"):
-            if cur.kind == "mfma" and (vgpr_w & crd):
+            fwd = crd.intersection(prev.wr)              # what prev wrote and cur reads ("vcc" counts as a vector register)
+            vgpr = bool(fwd) and any(r[0] in "va" for r in fwd)
+            if cur.kind == "mfma" and vgpr:
                 need = 2                                 # VALU write -> XDL read
-            elif prev.kind == "trans" and cur.kind in ("valu", "perm", "vread", "dsw", "vmemst", "ds", "vmem") and (vgpr_w & crd):
+            elif prev.kind == "trans" and cur.kind in ("valu", "perm", "vread", "dsw", "vmemst", "ds", "vmem") and vgpr:
                 need = 1                                 # transcendental result forwarded
-            elif cur.kind == "perm" and (vgpr_w & crd):
+            elif cur.kind == "perm" and vgpr:
                 need = 2
-            elif cur.kind == "vread" and (vgpr_w & crd):
+            elif cur.kind == "vread" and vgpr:
                 need = 1                                 # VALU write VGPR -> v_readfirstlane / v_readlane
-            elif cur.kind in ("vmem", "vmemst", "dma") and (sgpr_w & crd):
+            elif cur.kind in ("vmem", "vmemst", "dma") and fwd and any(r[0] == "s" and r != "scc" for r in fwd):
                 need = 5                                 # VALU write SGPR -> vector memory reads it as base
-            elif "vcc" in pwr and cur.fx is not None and cur.fx[0] == "v_div_fmas_f32":
+            elif "vcc" in prev.wr and cur.fx is not None and cur.fx[0] == "v_div_fmas_f32":
                 need = 4                                 # VALU write VCC -> v_div_fmas
         elif prev.kind == "salu":
-            if cur.kind == "dma" and "m0" in pwr:
-                need = 1
+            if cur.kind == "dma" and "m0" in prev.wr:
+                need = 1                                 # SALU write M0 -> LDS-DMA
         elif prev.kind in ("vmemst", "dsw"):
-            data = set(prev.rd[1:]) if prev.kind == "dsw" else set(prev.rd[1:-2])
+            data = prev.rd[1:] if prev.kind == "dsw" else prev.rd[1:-2]
             wide = prev.fx is not None and prev.fx[1] >= 3
-            if wide and cur.kind in ("valu", "trans", "perm", "mfma", "ds", "vmem") and (data & cwr):
+            if wide and cur.kind in ("valu", "trans", "perm", "mfma", "ds", "vmem") and not cwr.isdisjoint(data):
                 need = 2                                 # store of more than 64 bits -> overwrite of its data registers
         if need and dist < need:
             raise CheckError(f"wait states: '{cur.text}' needs {need} states after '{prev.text}', has {dist}")
-        dist += prev.sem[1] if (prev.kind == "nop") else 1
+        dist += prev.fx[1] if (prev.kind == "nop") else 1
         if dist > 20:
             break
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# s_waitcnt for straight-line code: LDS operations complete in order under lgkmcnt, vector memory operations under vmcnt
+# ------------------------------------------------------------------------------------------------------------------
+def auto_waits(prog):
+    """a counted wait in front of the first use of every load's destination.  Labels and branches must sit where no LDS or scalar
+    memory operation is outstanding (the generators put an explicit lgkmcnt(0) there)."""
+    out = []
+    lg, vm = [], []            # outstanding operations, oldest first: sets of destination registers (empty for stores / DMA)
+    smem = False
+    for ins in prog:
+        if ins.kind in ("label", "branch"):
+            if lg or smem:
+                raise CheckError(f"LDS / scalar memory operations outstanding at {ins.text}: put an explicit lgkmcnt(0) in front")
+            vm = []            # (what crosses a back edge is waited for explicitly; the simulation checks it)
+            out.append(ins)
+            continue
+        if ins.kind == "wait":
+            _, nv, nl = ins.fx
+            if nl is not None:
+                del lg[:max(0, len(lg) - nl)]
+                if nl == 0:
+                    smem = False
+            if nv is not None:
+                del vm[:max(0, len(vm) - nv)]
+            out.append(ins)
+            continue
+        touched = set(ins.rd) | set(ins.wr)
+        for q, name in ((lg, "lgkm"), (vm, "vm")):
+            idx = max((i for i, d in enumerate(q) if d & touched), default=-1)
+            if idx >= 0:
+                left = min(len(q) - 1 - idx, 15 if name == "lgkm" else 63)      # (the counters have four / six bits)
+                if name == "lgkm" and smem:
+                    left = 0                                                    # (scalar loads return out of order)
+                out.append(wait(**{name: left}))
+                del q[:len(q) - left]
+                if name == "lgkm" and left == 0:
+                    smem = False
+        out.append(ins)
+        if ins.kind == "ds":
+            lg.append(set(ins.wr))
+        elif ins.kind == "dsw":
+            lg.append(set())
+        elif ins.kind == "smem":
+            smem = True
+            lg.append(set(ins.wr))
+        elif ins.kind == "vmem":
+            vm.append(set(ins.wr))
+        elif ins.kind in ("vmemst", "dma"):
+            vm.append(set())
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# emission: what every generator's emit() writes the same way
+# ------------------------------------------------------------------------------------------------------------------
+def write_macro(f, name, prog):
+    """#define name as the program's text, one string literal per instruction (pseudos have no text)"""
+    f.write(f"#define {name} \\\n")
+    for ins in prog:
+        if ins.kind != "pseudo":
+            f.write(f'    "{ins.text}\\n\\t" \\\n')
+    f.write('    ""\n')
+
+
+def clobber_list(regs_):
+    """the clobber list of a statement that names `regs_` literally"""
+    return ", ".join(f'"{r}"' for r in regs_) + ', "m0", "vcc", "scc", "memory"'
+
+
+def assemble_check(prog, vops=(), sops=()):
+    """the text through the assembler alone, the statement's operands `vops` / `sops` replaced by registers hipcc could pick (v0.. /
+    s0..): syntax, encodable operands"""
+    rep = {f"%[{n}]": f"v{i}" for i, n in enumerate(vops)}
+    rep.update({f"%[{n}]": f"s{i}" for i, n in enumerate(sops)})
+    lines = [".amdgcn_target \"amdgcn-amd-amdhsa--gfx950\"", ".text", "k:"]
+    for ins in prog:
+        if ins.kind != "pseudo":
+            lines.append("  " + ins.bound(rep).text.replace("%=", "0"))
+    clang = "/opt/rocm/lib/llvm/bin/clang"
+    if not os.path.exists(clang):
+        return None
+    with tempfile.TemporaryDirectory() as td:
+        src = os.path.join(td, "k.s")
+        open(src, "w").write("\n".join(lines) + "\n")
+        r = subprocess.run([clang, "-x", "assembler", "-target", "amdgcn-amd-amdhsa", "-mcpu=gfx950", "-c", src, "-o", os.path.join(td, "k.o")],
+                           capture_output=True, text=True)
+        if r.returncode:
+            raise CheckError("the assembler rejects the stream:\n" + r.stderr[:3000])
+    return True

@@ -226,13 +226,8 @@ def test_attn64_loop_generator_checks_and_is_current():
     """gen_attn64.py emits the tile loop of gta_attn64_kernel and simulates it (typed dataflow of one wave over several tile
     counts, with forced rebase steps and a masked tail; LDS / DMA counters; the ISA's manual wait states).  The committed
     gta_attn64_loop.inc must be what the generator emits now."""
-    import importlib.util
     import os
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    path = os.path.join(root, "gta_amd", "csrc", "gen_attn64.py")
-    spec = importlib.util.spec_from_file_location("gen_attn64", path)
-    g = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(g)
+    g, d = _load_csrc_module("gen_attn64")
     progs = {}
     for name, dh, kw in g.production_variants():
         gen, prog = g.build_program(dh, kw)               # (simulated inside)
@@ -243,11 +238,11 @@ def test_attn64_loop_generator_checks_and_is_current():
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "loop.inc")
         g.emit(progs, out)
-        assert open(out).read() == open(os.path.join(root, "gta_amd", "csrc", "gta_attn64_loop.inc")).read(), \
+        assert open(out).read() == open(os.path.join(d, "gta_attn64_loop.inc")).read(), \
             "gta_attn64_loop.inc is stale: python3 gta_amd/csrc/gen_attn64.py --out gta_amd/csrc/gta_attn64_loop.inc"
     # the simulation does catch what it is there for: a P.V MFMA moved in front of its fragment's wait, a dropped exp
     gen, prog = g.build_program(96, dict(g.production_variants()[0][2]))
-    i = next(i for i, x in enumerate(prog) if x.kind == "wait" and x.sem[0] == "lgkm" and prog[i + 1].kind == "mfma")
+    i = next(i for i, x in enumerate(prog) if x.kind == "wait" and x.fx[2] is not None and prog[i + 1].kind == "mfma")
     bad = prog[:i] + [prog[i + 1], prog[i]] + prog[i + 2:]
     with pytest.raises(g.CheckError):
         g.check_all(gen, bad)
@@ -271,6 +266,102 @@ def _load_csrc_module(name):
     return m, d
 
 
+def _isa():
+    """isa_model.py as the generators import it: one module, so the CheckError it raises is the one they re-raise"""
+    import sys
+    if "isa_model" not in sys.modules:
+        _load_csrc_module("isa_model")
+    return sys.modules["isa_model"]
+
+
+def _pair(isa, first, second):
+    """two instructions built on isa.Asm (each argument emits one); -> check(states between them)"""
+    a = isa.Asm()
+    first(a)
+    second(a)
+    x, y = a.out
+
+    def check(states):
+        pad = isa.Asm()
+        pad.nop(states)
+        isa.check_wait_states([x] + pad.out, y)
+    return check
+
+
+def test_wait_state_table_rule_by_rule():
+    """isa_model.check_wait_states, the one table every generated stream goes through: each rule raises with one state too few between
+    its two instructions and passes with exactly the states it asks for; the exemptions hold (a load onto an MFMA's A / B operand needs
+    none, onto its C operand 8; an MFMA accumulating into its own C needs none; an MFMA without an operand list is treated as if every
+    operand were C)."""
+    isa = _isa()
+    V = lambda n, k=1: isa.regs("v", n, k)
+    D, A, B, C, D2 = V(0, 16), V(16, 4), V(20, 4), V(24, 16), V(40, 16)
+    mf = lambda a: a.mfma(D, A, B, C)
+    dma = lambda a: a.add("global_load_lds_dwordx4 v60, s[4:5]", "dma", ["m0", "v60", "s4", "s5"], [], ("global_load_lds", "v60", ["s4", "s5"], 0))
+    rules = [
+        ("XDL write -> VALU read", mf, lambda a: a.v_mov_b32("v60", D[3]), 12),
+        ("XDL write -> VALU overwrite", mf, lambda a: a.v_mov_b32(D[3], 0), 12),
+        ("XDL write -> LDS store of it", mf, lambda a: a.ds_write(32, "v60", [D[0]]), 12),
+        ("XDL write -> XDL read as B", mf, lambda a: a.mfma(D2, A, D[0:4], 0), 12),
+        ("XDL write -> another MFMA's C", mf, lambda a: a.mfma(D2, A, B, D), 12),
+        ("XDL operand read over its passes -> VALU overwrite", mf, lambda a: a.v_mov_b32(A[0], 0), 8),
+        ("... of its C operand by a load", mf, lambda a: a.ds_read(128, C[0:4], "v60"), 8),
+        ("... by a global load", mf, lambda a: a.global_load(4, C[4:8], "v60", ["s4", "s5"]), 8),
+        ("VALU write -> XDL read", lambda a: a.v_mov_b32(A[0], 0), mf, 2),
+        ("transcendental -> VALU read", lambda a: a.v_exp_f32("v60", "v61"), lambda a: a.v_add_f32("v62", "v60", "v60"), 1),
+        ("VALU write -> permlane", lambda a: a.v_mov_b32("v60", 0), lambda a: a.v_permlane32_swap_b32("v60", "v61"), 2),
+        ("VALU write -> v_readfirstlane", lambda a: a.v_mov_b32("v60", 0), lambda a: a.v_readfirstlane_b32("s4", "v60"), 1),
+        ("VALU write of an SGPR -> vector memory base", lambda a: a.v_readfirstlane_b32("s4", "v60"),
+         lambda a: a.global_load(1, ["v61"], "v62", ["s4", "s5"]), 5),
+        ("... -> store base", lambda a: a.v_readfirstlane_b32("s5", "v60"), lambda a: a.global_store(1, "v62", ["v61"], ["s4", "s5"]), 5),
+        ("VALU write of VCC -> v_div_fmas", lambda a: a.v_cmp("lt", "f32", "v60", "v61"), lambda a: a.v_div_fmas_f32("v62", "v63", "v64", "v65"), 4),
+        ("SALU write of M0 -> LDS-DMA", lambda a: a.add("s_add_u32 m0, s6, 64", "salu", ["s6"], ["m0", "scc"], ("s_add_m0", "s6", 64)), dma, 1),
+        ("128-bit global store -> overwrite of its data", lambda a: a.global_store(4, "v60", V(64, 4), ["s4", "s5"]), lambda a: a.v_mov_b32("v66", 0), 2),
+        ("128-bit LDS store -> overwrite of its data", lambda a: a.ds_write(128, "v60", V(64, 4)), lambda a: a.v_mov_b32("v64", 0), 2),
+    ]
+    for name, first, second, need in rules:
+        check = _pair(isa, first, second)
+        with pytest.raises(isa.CheckError, match=f"needs {need} states"):
+            check(need - 1)
+        check(need)
+    free = [
+        ("LDS load onto A", mf, lambda a: a.ds_read(128, A, "v60")),
+        ("global load onto B", mf, lambda a: a.global_load(4, B, "v60", ["s4", "s5"])),
+        ("transpose-read onto A", mf, lambda a: a.ds_read_tr(A[0:2], "v60")),
+        ("MFMA accumulating into its own C", lambda a: a.mfma(D, A, B, D), lambda a: a.mfma(D, A, B, D)),
+        ("load onto A of an MFMA with a zero C", lambda a: a.mfma(D, A, B, 0), lambda a: a.ds_read(128, A, "v60")),
+        ("64-bit store -> overwrite of its data", lambda a: a.ds_write(64, "v60", V(64, 2)), lambda a: a.v_mov_b32("v64", 0)),
+    ]
+    for name, first, second in free:
+        _pair(isa, first, second)(0)
+    # an MFMA that does not say which operand is C: conservative, not a crash
+    bare = isa.Ins("v_mfma_f32_32x32x16_bf16 v[0:15], v[16:19], v[20:23], v[24:39]", "mfma", A + B + C, D)
+    load = isa.Asm()
+    load.ds_read(128, A, "v60")
+    with pytest.raises(isa.CheckError, match="needs 8 states"):
+        isa.check_wait_states([bare, isa.nop(7)], load.out[0])
+    isa.check_wait_states([bare, isa.nop(8)], load.out[0])
+
+
+def test_full_item_stream_keeps_wait_states_across_both_seams():
+    """The item stream with the REAL tile loop inside (ItemGen().program(), and its pad4 / phases twins) through check_wait_states in
+    program order around both seams, item prologue -> loop and loop -> item epilogue: the last 30 instructions before each seam and
+    the first 24 behind it.  (check() executes the stream with a stub for the loop, and the loop's own simulation starts at its first
+    instruction: neither sees a pair of instructions that straddles a seam.)"""
+    g, d = _load_csrc_module("gen_item64")
+    isa = _isa()
+    for prog in (g.ItemGen().program(), g.ItemGen().program(pad4=True), g.ItemGen(phases=True).program()):
+        head = next(i for i, x in enumerate(prog) if x.sem == ("j0",))                     # the loop's first instruction
+        tail = next(i for i, x in enumerate(prog) if x.sem == ("item_end",)) + 1           # the first one behind it
+        assert 30 < head < tail - 1000 and tail + 24 < len(prog)
+        for seam in (head, tail):
+            hist = []
+            for ins in prog[seam - 30:seam + 24]:
+                if ins.kind != "label":
+                    isa.check_wait_states(hist, ins)
+                    hist.append(ins)
+
+
 def test_item_stream_generator_simulates_and_is_current():
     """gen_item64.py emits the whole work item of gta_attn64_items_kernel (prologue, tile loop, epilogue, request for the next item) as
     one instruction stream.  Its check() EXECUTES the stream -- the tile loop replaced by a stub that verifies the prologue's results
@@ -288,7 +379,7 @@ def test_item_stream_generator_simulates_and_is_current():
     assert st["mfma"] == 72 and st["instructions"] < 1900, st
     full = g.ItemGen().program()
     if os.path.exists("/opt/rocm/lib/llvm/bin/clang"):
-        assert g.assemble_check(full)
+        assert _isa().assemble_check(full, sops=g.OPERANDS)
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "items.inc")
         g.emit(out, full, g.ItemGen().program(pad4=True), g.ItemGen(phases=True).program())
@@ -338,7 +429,7 @@ def test_dkv64_stream_generator_simulates_and_is_current():
     assert st["mfma"] == 480 and st["instructions"] < 2700, st          # tile 0: 48; four stage copies of 96; the tail: 48
     prog = g.Gen().program()
     if os.path.exists("/opt/rocm/lib/llvm/bin/clang"):
-        assert g.assemble_check(prog)
+        assert _isa().assemble_check(prog, g.VOPS, g.SOPS)
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "dkv.inc")
         g.emit(out, prog)
@@ -356,7 +447,7 @@ def test_dq64_stream_generator_simulates_and_is_current():
     assert st["mfma"] == 360 and st["instructions"] < 2100, st          # tile 0: 48; four stage copies of 72; the tail: 24
     prog = g.GenDQ().program()
     if os.path.exists("/opt/rocm/lib/llvm/bin/clang"):
-        assert g.assemble_check(prog, g.Q_VOPS, g.Q_SOPS)
+        assert _isa().assemble_check(prog, g.Q_VOPS, g.Q_SOPS)
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "dq.inc")
         g.emit(out, prog, "GTA_BWD64_DQ", g.Q_VOPS, g.Q_SOPS, g.DQ_RESULTS)
