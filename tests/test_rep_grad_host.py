@@ -7,34 +7,16 @@ from ctypes import c_int64, c_void_p
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 from gta_amd import native
 from gta_amd import repgrad as R
 from oracle import gta_oracle as O
+from tests import _repgrad_sums as S
 
-
-def _view_sums(pairs, lo, n, W, N, homog=False):
-    """per view: sum over heads, the view's tokens and the slab's groups of a b^T -> [B,N,4,4]"""
-    S = 0
-    for a, b in pairs:
-        B, H, T, _ = a.shape
-        av = a[..., lo:lo + n * W].reshape(B, H, N, T // N, n, W)
-        bv = b[..., lo:lo + n * W].reshape(B, H, N, T // N, n, W)
-        if homog:
-            av, bv = F.pad(av, (0, 1)), F.pad(bv, (0, 1), value=1.0)
-        S = S + torch.einsum("bhntgi,bhntgj->bnij", av, bv)
-    return S
-
-
-def _so2_sums(pairs, lo, n):
-    return sum(torch.einsum("bhtgi,bhtgj->btgij", a[..., lo:lo + 2 * n].unflatten(-1, (n, 2)), b[..., lo:lo + 2 * n].unflatten(-1, (n, 2)))
-               for a, b in pairs)
-
-
-def _t2_sums(pairs, lo, n):
-    return sum(torch.einsum("bhtgi,bhtgj->btij", a[..., lo:lo + 3 * n].unflatten(-1, (n, 3)), b[..., lo:lo + 3 * n].unflatten(-1, (n, 3)))
-               for a, b in pairs)
+# the sums the kernel produces, in fp64 (each emulator also returns its absprod twin, which the algebra has no use for)
+_view_sums = lambda *a, **kw: S._view_sums(*a, **kw)[0]
+_so2_sums = lambda *a: S._so2_sums(*a)[0]
+_t2_sums = lambda *a: S._t2_sums(*a)[0]
 
 
 def _close(got, ref, name):
