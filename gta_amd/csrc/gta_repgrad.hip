@@ -7,6 +7,7 @@
 // holds 256 / H tokens of one view, so the per-view sums are split over P * H / 256 workgroups (1280 at the headline shape, 160 views).
 // Only the channels of the requested slabs are read.  No float atomics: per-token sums are finished inside the workgroup in head order,
 // per-view sums leave one partial per workgroup and gta_repgrad_finish_kernel adds them in workgroup order -- two runs, same bits.
+// With per-scene prefixes (gta_rep_grad_sums_varlen, batches that mix view counts) the VARLEN twins skip what lies past a scene's prefix.
 #include "gta_common.h"
 #include "gta_repgrad_params.h"
 #include "../../include/gta_hip.h"
@@ -38,7 +39,10 @@ GTA_DEV float head_sum(const float* red, int k, int tl, int H) {
     return s;
 }
 
-template <int ESZ, bool EUCLID, bool VEC>
+// VARLEN (gta_rep_grad_sums_varlen): a row at or past its scene's prefix p.lens[b] is dead -- never loaded, exact zero in every sum; a
+// workgroup wholly past the prefix writes +0.0 to its partial and to its per-token outputs and returns (uniform over the workgroup).
+// What is live runs the statements of the instance without VARLEN in the same order: the same bits.
+template <int ESZ, bool EUCLID, bool VEC, bool VARLEN = false>
 __global__ __launch_bounds__(NT) void gta_repgrad_kernel(const GtaRepGradParams p) {
     __shared__ float red[SO2_PASS * 4 * NT];
     const int tid = threadIdx.x;
@@ -48,7 +52,19 @@ __global__ __launch_bounds__(NT) void gta_repgrad_kernel(const GtaRepGradParams 
     const int h = tid % p.H, tl = tid / p.H;
     const int t0 = n * p.P + c * p.tpb;                        // first token of the workgroup
     const int ntok = min(p.tpb, p.P - c * p.tpb);
-    const bool live = tl < ntok;
+    int nlive = ntok;                                          // tokens of the workgroup whose rows are loaded
+    if (VARLEN) {
+        const int len = min(max(p.lens[b], 1), p.T);           // valid tokens of scene b, clamped to 1..T
+        if (t0 >= len) {                                       // a dead workgroup: nothing loaded, every word it owns is +0.0
+            if (p.n_se3 > 0 && tid < 16) p.part[(long)wg * 16 + tid] = 0.f;
+            for (int e = tid; e < ntok * p.n_so2 * 4; e += NT) p.so2_out[(long)(b * p.T + t0) * p.n_so2 * 4 + e] = 0.f;
+            if (p.n_t2 > 0)
+                for (int e = tid; e < ntok * 9; e += NT) p.t2_out[(long)(b * p.T + t0) * 9 + e] = 0.f;
+            return;
+        }
+        nlive = min(ntok, len - t0);                           // a workgroup that straddles the prefix: its tail adds zeros
+    }
+    const bool live = tl < nlive;
     const int t = t0 + (live ? tl : 0);
     const char* ar[2];
     const char* br[2];
@@ -229,13 +245,30 @@ bool vec_ok(const GtaRepGradParams& p, int esz, bool euclid) {
     return true;
 }
 
+// the VARLEN twin of each instance below, selected the same way
+void launch_varlen(const GtaRepGradParams& p, int esz, bool euclid, dim3 grid, dim3 block, hipStream_t stream) {
+    if (vec_ok(p, esz, euclid)) {
+        if (esz == 2) hipLaunchKernelGGL((gta_repgrad_kernel<2, false, true, true>), grid, block, 0, stream, p);
+        else          hipLaunchKernelGGL((gta_repgrad_kernel<4, false, true, true>), grid, block, 0, stream, p);
+    } else if (esz == 2) {
+        if (euclid) hipLaunchKernelGGL((gta_repgrad_kernel<2, true, false, true>), grid, block, 0, stream, p);
+        else        hipLaunchKernelGGL((gta_repgrad_kernel<2, false, false, true>), grid, block, 0, stream, p);
+    } else {
+        if (euclid) hipLaunchKernelGGL((gta_repgrad_kernel<4, true, false, true>), grid, block, 0, stream, p);
+        else        hipLaunchKernelGGL((gta_repgrad_kernel<4, false, false, true>), grid, block, 0, stream, p);
+    }
+}
+
 }  // namespace
 
+// p.lens != nullptr selects the VARLEN instances (gta_rep_grad_sums_varlen refuses a NULL lens before it comes here)
 int gta_repgrad_dispatch(const GtaRepGradParams& p, int esz, bool euclid, hipStream_t stream) {
     const long nwg = (long)p.B * p.N * p.chunks;
     if (nwg <= 0 || nwg > 0x7fffffffL) return GTA_E_UNSUPPORTED;
     const dim3 grid((unsigned)nwg), block(NT);
-    if (vec_ok(p, esz, euclid)) {
+    if (p.lens) {
+        launch_varlen(p, esz, euclid, grid, block, stream);
+    } else if (vec_ok(p, esz, euclid)) {
         if (esz == 2) hipLaunchKernelGGL((gta_repgrad_kernel<2, false, true>), grid, block, 0, stream, p);
         else          hipLaunchKernelGGL((gta_repgrad_kernel<4, false, true>), grid, block, 0, stream, p);
     } else if (esz == 2) {

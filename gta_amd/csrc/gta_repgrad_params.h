@@ -18,6 +18,7 @@ struct GtaRepGradParams {
     float* view_out;                  // [B*N][16]
     float* so2_out;                   // [B*T][n_so2][4]
     float* t2_out;                    // [B*T][9]
+    const int32_t* lens;              // [B] valid tokens of this side per scene (clamped to 1..T): the VARLEN instances; nullptr: every row is live
 };
 
 constexpr int GTA_REPGRAD_THREADS = 256;

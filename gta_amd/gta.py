@@ -676,15 +676,19 @@ def _varlen_forward(q, k, v, cfg, tables, trans_coeff, tau, key_lens, key_views=
 class _VarlenAttn(torch.autograd.Function):
     """The fused layouts with per-scene key prefixes under grad (``key_views_backward=True``): the forward of ``_varlen_forward``, whose workspace
     (the masked K'/V' tile images) and LSE serve ``gta_attn_bwd_varlen``.  ``q_lens`` (or None) masks padded query rows in the backward only.
-    Gradients: q, k, v, trans_coeff, tau -- as ``_GtaAttn``; none for the tables."""
+    ``views``: the validated host tuples (query_views or None, key_views) the two device tensors were built from.
+    Gradients: q, k, v, trans_coeff, tau -- as ``_GtaAttn``; and, with ``carriers`` (as in ``_GtaAttn``), the tables': the pass of
+    gta_amd/repgrad.py over the prefixes alone (``gta_rep_grad_sums_varlen``), exact zeros for padded views and tokens."""
 
     @staticmethod
-    def forward(ctx, q, k, v, trans_coeff, tau, cfg, key_lens, q_lens, vrep_q, vrep_k, cs_q, cs_k):
+    def forward(ctx, q, k, v, trans_coeff, tau, cfg, key_lens, q_lens, views, vrep_q, vrep_k, cs_q, cs_k, *carriers):
         c, ws = _varlen_forward(q, k, v, cfg, dict(vrep_q=vrep_q, vrep_k=vrep_k, cs_q=cs_q, cs_k=cs_k), trans_coeff, tau, key_lens)
         ctx.cfg = cfg
         ctx.kv_images = ws
         ctx.save_for_backward(c.q, c.k, c.v, c.out, c.lse, c.tc, c.ta, vrep_q, vrep_k, cs_q, cs_k, key_lens, q_lens)
         ctx.tc_meta, ctx.tau_meta = _scalar_meta(trans_coeff), _scalar_meta(tau)
+        ctx.views = views
+        ctx.carriers = _repgrad.carrier_meta(carriers)
         return c.out
 
     @staticmethod
@@ -694,7 +698,20 @@ class _VarlenAttn(torch.autograd.Function):
         want_dtau = ta is not None and ctx.needs_input_grad[4]
         dq, dk, dv, dtc, dta = _bw.attn_bwd(ctx.cfg, q, k, v, out, dout, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k,
                                             kv_images=ctx.kv_images, want_dtau=want_dtau, key_lens=key_lens, q_lens=q_lens)
-        return (dq, dk, dv, _restore_scalar(dtc, ctx.tc_meta), _restore_scalar(dta, ctx.tau_meta)) + (None,) * 7
+        grads = ()
+        if ctx.carriers:
+            # gradients of the tables over the prefixes: (q, dq), (dout, out) under q_lens (every row without it), (dk, k), (dv, v) under key_lens
+            meta = tuple(m if need else None for m, need in zip(ctx.carriers, ctx.needs_input_grad[13:]))
+            f_dims, so3_degree, Nq, Nk, scale, flags = ctx.cfg
+            desc = native.make_desc(q, k, v, out, f_dims, so3_degree, Nq, Nk, scale, flags)
+            do = _as_kernel_layout(dout.to(q.dtype))
+            vt = bool(flags & native.FLAG_V_TRANSFORM)
+            tables = dict(vrep_q=vrep_q, vrep_k=vrep_k, cs_q=cs_q, cs_k=cs_k)
+            query_views, key_views = ctx.views
+            grads = tuple(_repgrad.table_grads(desc, tables, meta, tc, ((q, dq), (do, out))[:1 + vt], ((dk, k), (dv, v))[:1 + vt],
+                                               direct=False, views=(query_views if q_lens is not None else None, key_views),
+                                               lens=(q_lens, key_lens)))
+        return (dq, dk, dv, _restore_scalar(dtc, ctx.tc_meta), _restore_scalar(dta, ctx.tau_meta)) + (None,) * 8 + grads
 
 
 def _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, kv_cache=None, key_views=None,
@@ -749,8 +766,12 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
              ``key_lens_tensor`` for these view counts (``ForwardPlan`` keeps one); built per call when None.
     key_views_backward: False (default): a call with ``key_views`` under grad raises "forward-only", as it always did.  True: the call is
              differentiable in q, k, v, trans_coeff and tau on the fused layouts (``gta_attn_fwd_varlen`` + ``gta_attn_bwd_varlen``): dk / dv rows
-             of padded views are exactly zero and nothing of a padded view is read.  Still refused, by name: the staged generic layouts under
-             grad, precise=True, pretransformed, kv_mode='fused', and any rep table or pose that requires grad.
+             of padded views are exactly zero and nothing of a padded view is read.  Rep tables and poses that require grad get their
+             gradients too (gta_amd/repgrad.py over the prefixes, ``gta_rep_grad_sums_varlen``): exact zeros for the padded views' records
+             and the padded tokens' entries -- with ``query_views`` on the query side as well --, whatever those hold (such tables must be
+             CUDA tensors: the pass has no CPU path, and a CPU one is refused by name before anything is launched).  Still refused, by
+             name: the staged generic layouts under grad, precise=True, pretransformed, kv_mode='fused', return_attmap, and return_lse
+             under grad.
     query_views: only with ``key_views_backward=True``; validated like ``key_views``, against Nq.  Backward only: the query rows of scene b's
              views past ``query_views[b]`` (self-attention over padded views, where they hold anything) send no gradient -- their ``dout`` is
              never read, their dq rows are zero.  The forward still computes (unspecified) output rows for them.
@@ -792,9 +813,10 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
             query_views = check_key_views(query_views, q.shape[0], Nq if "vrep_q" in packed else None, name="query_views")
             if q.shape[2] % Nq:
                 raise native.GtaError(f"query_views: {q.shape[2]} query tokens do not split evenly into {Nq} views")
-        if key_views_backward and carriers:
-            raise native.GtaError("key_views_backward: no gradient for rep tables or poses under key_views (gta_rep_grad_sums has no key mask): "
-                                  "detach the tables")
+        if key_views_backward and any(c is not None and not c.is_cuda for c in carriers):
+            # said here, by name, before the forward is launched: the pass that serves them has no CPU path
+            raise native.GtaError("key_views_backward: the gradients of rep tables or poses come from a GPU pass (gta_rep_grad_sums_varlen): "
+                                  "tables and poses that require grad must be CUDA tensors")
     how = dict(v_transform=v_transform, euclid=euclid, precise=bool(precise), needs_grad=needs_grad, key_views=key_views is not None,
                key_views_backward=bool(key_views_backward))
     flags = attention_route(tuple(q.shape), k.shape[2], q.dtype, f_dims, so3_degree, Nq, Nk, pretransformed=pretransformed, use_dma=use_dma,
@@ -818,7 +840,7 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
         return (_GtaAttnLse if return_lse else _GtaAttn).apply(q, k, v, trans_coeff, tau, kv_cache, cfg, *tables, *carriers)
     if needs_grad:          # (key_views_backward: anything else was refused above, return_lse included)
         q_lens = None if query_views is None else key_lens_tensor(query_views, q.shape[2] // Nq, q.device)
-        return _VarlenAttn.apply(q, k, v, trans_coeff, tau, cfg, key_lens, q_lens, *tables)
+        return _VarlenAttn.apply(q, k, v, trans_coeff, tau, cfg, key_lens, q_lens, (query_views, key_views), *tables, *carriers)
     c = _varlen_forward(q, k, v, cfg, packed, trans_coeff, tau, key_lens, key_views, kv_cache)[0]
     return (c.out, c.lse) if return_lse else c.out
 

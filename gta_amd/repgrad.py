@@ -11,6 +11,10 @@ Sums of a b^T, per batch, over heads, the tokens of a view (se3) or one token (s
     key side     (dk, k), (dv, v)           generic path: (dk', k), (dv', v)          [euclid se3: b homogenised]
 the second pair only under v_transform.  ``direct`` marks sums taken in the transformed space (generic path): they are the gradients
 of the matrices as applied; the fused path's sums are in the input space and go back through the matrix (A^-T, B^-T, R).
+
+Batches that mix view counts (``key_views_backward=True``): the sums come from ``gta_rep_grad_sums_varlen`` over each scene's prefix, and
+the algebra runs under masks built from the host view counts -- a padded view's matrix is never inverted, padded entries are selected to
+exact zero.
 """
 from __future__ import annotations
 
@@ -63,13 +67,25 @@ def scale_mask(tc, device) -> torch.Tensor:
     return m
 
 
-def view_grad(side: int, S, vrep, tc, direct: bool, euclid: bool = False, S_out=None) -> torch.Tensor:
+def live_mask(counts, n: int, per: int, device) -> torch.Tensor:
+    """[B, n * per] bool: entry i of scene b is live when i < counts[b] * per.  ``counts``: the validated HOST tuple of per-scene view
+    counts (``key_views`` / ``query_views``); per = 1: a mask of the n views, per = P: of the n * P tokens.  Built on the device from the
+    host tuple: nothing is read back."""
+    lim = (torch.tensor(counts, dtype=torch.int64) * per).to(device, non_blocking=True)
+    return torch.arange(n * per, device=device)[None, :] < lim[:, None]
+
+
+def view_grad(side: int, S, vrep, tc, direct: bool, euclid: bool = False, S_out=None, live=None) -> torch.Tensor:
     """d vrep [B,N,72] (fp64; the E and inv(E) slots, zero elsewhere) from the view sums S [B,N,4,4].
     side 0: the q side's matrix A = E.m (q' = A^T q, out = A o~): dA = S A^-T (fused) or S (direct).
     side 1: B = inv(E_k).m (k' = B k, v' = B v): dB = B^-T S (fused) or S (direct).
     euclid (affine maps, generic path): S is the gradient of the matrix as applied -- query side S of (dq', [q;1]) for the
-    inv(E_q) slot and S_out of (dout, [o~;1]) for the E_q slot; key side S of (dk', [k;1]) + (dv', [v;1])."""
+    inv(E_q) slot and S_out of (dout, [o~;1]) for the E_q slot; key side S of (dk', [k;1]) + (dv', [v;1]).
+    live [B,N] bool (None: every view): a padded view's record may hold anything, a singular or non-finite matrix included -- the identity
+    stands in for it before the inverse, and with its zero sums (gta_rep_grad_sums_varlen) the view's gradient is exact zero."""
     S = S.double()
+    if live is not None:
+        S = torch.where(live[..., None, None], S, torch.zeros((), dtype=torch.float64, device=S.device))
     msk = scale_mask(tc, S.device)
     g = torch.zeros(*S.shape[:2], native.VREP_STRIDE, dtype=torch.float64, device=S.device)
     if euclid:
@@ -79,6 +95,8 @@ def view_grad(side: int, S, vrep, tc, direct: bool, euclid: bool = False, S_out=
         return g
     slot = INV if side == 0 else REP
     M = vrep[..., slot].double().reshape(S.shape) * msk
+    if live is not None:
+        M = torch.where(live[..., None, None], M, torch.eye(4, dtype=torch.float64, device=S.device))
     if direct:
         dM = S
     elif side == 0:
@@ -89,49 +107,69 @@ def view_grad(side: int, S, vrep, tc, direct: bool, euclid: bool = False, S_out=
     return g
 
 
-def so2_grad(side: int, T, cs, direct: bool) -> torch.Tensor:
+def so2_grad(side: int, T, cs, direct: bool, live=None) -> torch.Tensor:
     """dR [B,T,nb,2,2] (fp64) of the rotation blocks R = [[c,-s],[s,c]] from the per-token sums T [B,T,nb,2,2].
-    q side (q' = R q, out = R^T o~): dR = R T^T (fused) or T^T (direct); k side (k' = R k, v' = R v): R T or T."""
+    q side (q' = R q, out = R^T o~): dR = R T^T (fused) or T^T (direct); k side (k' = R k, v' = R v): R T or T.
+    live [B,T] bool (None: every token): a padded token's (cos, sin) may hold anything; its dR is selected to exact zero, not multiplied."""
     T = T.double()
     if side == 0:
         T = T.transpose(-1, -2)
-    if direct:
-        return T
-    c, s = cs[..., 0].double(), cs[..., 1].double()
-    R = torch.stack([torch.stack([c, -s], -1), torch.stack([s, c], -1)], -2)
-    return R @ T
+    if not direct:
+        c, s = cs[..., 0].double(), cs[..., 1].double()
+        R = torch.stack([torch.stack([c, -s], -1), torch.stack([s, c], -1)], -2)
+        T = R @ T
+    return _select(live, T, 3)
 
 
-def so2_packed(dR) -> torch.Tensor:
-    """dR of R = [[c,-s],[s,c]] -> d (cos, sin) [..., 2]"""
-    return torch.stack([dR[..., 0, 0] + dR[..., 1, 1], dR[..., 1, 0] - dR[..., 0, 1]], -1)
+def _select(live, x, trailing: int) -> torch.Tensor:
+    """x where live ([B,T] bool, broadcast over ``trailing`` more dimensions), exact zero elsewhere; live None: x"""
+    if live is None:
+        return x
+    return torch.where(live[(...,) + (None,) * trailing], x, torch.zeros((), dtype=x.dtype, device=x.device))
 
 
-def t2_packed(side: int, dM) -> torch.Tensor:
-    """dM of the t2 matrix -> d (cx, cy): q side A = inv(T) holds -c in row 2, k side T holds c"""
+def so2_packed(dR, live=None) -> torch.Tensor:
+    """dR of R = [[c,-s],[s,c]] [B,T,nb,2,2] -> d (cos, sin) [B,T,nb,2]; live [B,T] bool: exact zero at padded tokens"""
+    return _select(live, torch.stack([dR[..., 0, 0] + dR[..., 1, 1], dR[..., 1, 0] - dR[..., 0, 1]], -1), 2)
+
+
+def t2_packed(side: int, dM, live=None) -> torch.Tensor:
+    """dM of the t2 matrix [B,T,3,3] -> d (cx, cy): q side A = inv(T) holds -c in row 2, k side T holds c; live as in so2_packed"""
     d = dM[..., 2, :2]
-    return -d if side == 0 else d
+    return _select(live, -d if side == 0 else d, 1)
 
 
-def table_grads(desc, tables: dict, meta, tc, q_pairs, k_pairs, direct: bool, euclid: bool = False, q_view_pairs=None):
+def table_grads(desc, tables: dict, meta, tc, q_pairs, k_pairs, direct: bool, euclid: bool = False, q_view_pairs=None,
+                views=(None, None), lens=(None, None)):
     """The carriers' gradients (list of six, None where no gradient is asked): the sums of both sides through ``gta_rep_grad_sums``
-    (one launch per side; under euclid two more for the query side's view sums), then the algebra above."""
+    (one launch per side; under euclid two more for the query side's view sums), then the algebra above.
+    views, lens: per side (query, key) the validated host tuple of per-scene view counts (``query_views`` / ``key_views``) with the device
+    tensor of valid tokens built from it (``q_lens`` / ``key_lens``), or None for a side without padding.  A side that has them takes its
+    sums through ``gta_rep_grad_sums_varlen`` -- nothing of a padded view is read -- and the algebra works under masks built from the
+    host tuple: padded views' matrices are never inverted, and padded entries get exact zeros."""
     out = [None] * 6
     for side, pairs in ((0, q_pairs), (1, k_pairs)):
         mv, mc, mo = meta[side], meta[2 + side], meta[4 + side]
         if mv is None and mc is None and mo is None:
             continue
         want_view, want_so2, want_t2 = mv is not None and desc.d_se3 > 0, mc is not None and desc.d_so2 > 0, mo is not None and desc.d_t2 > 0
-        S = S_out = T2 = T3 = None
+        S = S_out = T2 = T3 = live_v = live_t = None
+        if views[side] is not None:
+            if euclid or direct or lens[side] is None:
+                raise native.GtaError("table_grads: per-scene view counts serve the fused layouts, with the device lens beside the host counts")
+            T, N = (desc.Tk, desc.Nk) if side else (desc.Tq, desc.Nq)
+            dev = pairs[0][0].device
+            live_v, live_t = live_mask(views[side], N, 1, dev), live_mask(views[side], N, T // N, dev)
         view_here = want_view and not (euclid and side == 0)
         if view_here or want_so2 or want_t2:
-            S, T2, T3 = native.rep_grad_sums(desc, side, pairs, view=view_here, so2=want_so2, t2=want_t2)
+            S, T2, T3 = native.rep_grad_sums(desc, side, pairs, view=view_here, so2=want_so2, t2=want_t2,
+                                             lens=lens[side] if views[side] is not None else None)
         if want_view and not view_here:
             S = native.rep_grad_sums(desc, 0, q_view_pairs[:1], view=True)[0]
             if len(q_view_pairs) > 1:
                 S_out = native.rep_grad_sums(desc, 0, q_view_pairs[1:], view=True)[0]
         if mv is not None:
-            g = (view_grad(side, S, tables[TABLES[side]], tc, direct, euclid, S_out) if want_view
+            g = (view_grad(side, S, tables[TABLES[side]], tc, direct, euclid, S_out, live=live_v) if want_view
                  else torch.zeros(mv[0], dtype=torch.float64, device=q_pairs[0][0].device))
             out[side] = g.to(mv[1])
         if mc is not None:
@@ -139,15 +177,15 @@ def table_grads(desc, tables: dict, meta, tc, q_pairs, k_pairs, direct: bool, eu
             if not want_so2:
                 out[2 + side] = torch.zeros(shape, dtype=dt, device=q_pairs[0][0].device)
             else:
-                dR = so2_grad(side, T2, tables[TABLES[2 + side]], direct)
-                out[2 + side] = (dR if len(shape) == 5 else so2_packed(dR)).reshape(shape).to(dt)
+                dR = so2_grad(side, T2, tables[TABLES[2 + side]], direct, live=live_t)
+                out[2 + side] = (dR if len(shape) == 5 else so2_packed(dR, live_t)).reshape(shape).to(dt)
         if mo is not None:
             shape, dt = mo
             if not want_t2:
                 out[4 + side] = torch.zeros(shape, dtype=dt, device=q_pairs[0][0].device)
             else:
-                dM = T3.double()                     # t2 runs on the generic path only: sums in the transformed space
-                out[4 + side] = (dM if len(shape) == 4 else t2_packed(side, dM)).reshape(shape).to(dt)
+                dM = _select(live_t, T3.double(), 2)  # t2 runs on the generic path only: sums in the transformed space
+                out[4 + side] = (dM if len(shape) == 4 else t2_packed(side, dM, live_t)).reshape(shape).to(dt)
     return out
 
 
@@ -155,11 +193,15 @@ def table_grads(desc, tables: dict, meta, tc, q_pairs, k_pairs, direct: bool, eu
 # the rep builders' chain rules
 # --------------------------------------------------------------------------------------------
 def extrinsic_grad(E, dvrep) -> torch.Tensor:
-    """dE (fp64) from d vrep: the E slot directly, the inv(E) slot through d inv(E) = -inv(E) dE inv(E)."""
-    Ei = torch.linalg.inv(E.double())
-    shape = Ei.shape
+    """dE (fp64) from d vrep: the E slot directly, the inv(E) slot through d inv(E) = -inv(E) dE inv(E).
+    A view whose incoming gradient is entirely zero (the padded views of a call with per-scene view counts) takes the identity for E
+    before the inverse: exact for any call (-E^-T 0 E^-T = 0), and such a view's extrinsic may then hold anything, all zeros included."""
+    E = E.double()
+    shape = E.shape
     dinv = dvrep[..., INV].double().reshape(shape)
     drep = dvrep[..., REP].double().reshape(shape)
+    idle = ((dinv == 0) & (drep == 0)).flatten(-2).all(-1)
+    Ei = torch.linalg.inv(torch.where(idle[..., None, None], torch.eye(shape[-1], dtype=torch.float64, device=E.device), E))
     return dinv - Ei.transpose(-1, -2) @ drep @ Ei.transpose(-1, -2)
 
 
@@ -172,10 +214,14 @@ def so2_weights(nfreqs: int, max_freq_h: float, max_freq_w: float, shared_freqs:
 
 
 def coord_grad(coord, dcs, nfreqs: int, max_freq_h: float, max_freq_w: float, shared_freqs: bool) -> torch.Tensor:
-    """d coord [..., 2] (fp64) from d (cos, sin) [..., 2F, 2]: d theta = -sin dcos + cos dsin, then through theta = w coord."""
+    """d coord [..., 2] (fp64) from d (cos, sin) [..., 2F, 2]: d theta = -sin dcos + cos dsin, then through theta = w coord.
+    A token whose incoming gradient is entirely zero (padded tokens under per-scene view counts) takes coordinate 0 for the sines: its
+    coordinates may hold anything, NaN and Inf included, and its gradient is exact zero."""
     w = so2_weights(nfreqs, max_freq_h, max_freq_w, shared_freqs, coord.device)
-    th = (coord.double()[..., None, :] * w).flatten(-2)                   # [..., 2F], block 2f + d
     dcs = dcs.double()
+    idle = (dcs == 0).flatten(-2).all(-1)
+    coord = torch.where(idle[..., None], torch.zeros((), dtype=torch.float64, device=coord.device), coord.double())
+    th = (coord[..., None, :] * w).flatten(-2)                            # [..., 2F], block 2f + d
     dth = -torch.sin(th) * dcs[..., 0] + torch.cos(th) * dcs[..., 1]
     return (dth.unflatten(-1, (nfreqs, 2)) * w).sum(-2)
 

@@ -177,8 +177,10 @@ class TransformingSRT(nn.Module):
         view counts: scene b's first ``input_views[b]`` views are its input, the rest of its [N, ...] slots is padding that no valid
         token ever attends to -- in the encoder's self-attention and in the decoder's cross-attention (``gta_attention``'s
         ``key_views``).  Inference only (call under ``torch.no_grad()``) unless ``input_views_backward=True``: every layer then runs the
-        differentiable route (``key_views_backward``; fused layouts, tables without grad), and the encoder's self-attention layers also get
-        ``query_views = input_views``, so the tokens of padded views send no gradient into the valid ones."""
+        differentiable route (``key_views_backward``; fused layouts), and the encoder's self-attention layers also get
+        ``query_views = input_views``, so the tokens of padded views send no gradient into the valid ones.  ``extras['input_transforms']``,
+        ``['input_coord']`` and ``['target_*']`` may require grad: poses and coordinates get their gradients as without ``input_views``,
+        exact zeros for the padded views' extrinsics and the padded tokens' coordinates, whatever those hold (zeros included)."""
         extras = {} if extras is None else extras
         if input_views is not None:
             extras = dict(extras)                      # the caller's dict never carries these counts into a later call (as render_image)

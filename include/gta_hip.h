@@ -200,8 +200,8 @@ int gta_attn_bwd(const GtaAttnDesc* desc,
  *       gta_attn_bwd (GTA_FLAG_BWD_KEYS32) on that scene alone with its keys (and, with q_lens, its queries) cut to the prefixes.
  *   gta_attn_bwd_varlen_supported: what gta_attn_fwd_varlen_supported answers -- GTA_E_UNSUPPORTED with the reason in gta_strerror() for
  *       GTA_FLAG_FP32_PRODUCTS, GTA_FLAG_FUSED_KV, GTA_FLAG_PRETRANSFORMED and for layouts without a fused kernel.
- *   workspace: >= gta_attn_bwd_workspace_bytes(desc).  Every other argument, check and error code: as in gta_attn_bwd.  No gradient for the
- *       reps / poses (gta_rep_grad_sums has no key mask). */
+ *   workspace: >= gta_attn_bwd_workspace_bytes(desc).  Every other argument, check and error code: as in gta_attn_bwd.  The gradients of the
+ *       reps / poses under the same prefixes: gta_rep_grad_sums_varlen. */
 int gta_attn_bwd_varlen_supported(const GtaAttnDesc* desc);
 int gta_attn_bwd_varlen(const GtaAttnDesc* desc,
                         const void* q, const void* k, const void* v, const void* out, const void* dout,
@@ -354,6 +354,21 @@ int gta_rep_grad_sums(const GtaAttnDesc* desc, int32_t side, int32_t n_pairs,
                       const void* a1, const int64_t* a1_stride, const void* b1, const int64_t* b1_stride,
                       float* view_sums, float* so2_sums, float* t2_sums,
                       void* workspace, int64_t workspace_bytes, void* stream);
+
+/* The sums with per-scene prefixes (the pass after gta_attn_bwd_varlen): gta_rep_grad_sums over the rows of the prefix alone.
+ *   lens: [B] int32 on the device, valid TOKENS of this side per scene (key_lens for side 1, q_lens for side 0), clamped to 1..T as in
+ *       gta_attn_bwd_varlen; NULL: GTA_E_BADARG.  A row (b, h, t) with t >= lens[b] is dead: none of its operands is loaded, in either
+ *       pair (it may hold anything, NaN and Inf included), and it adds exact zero to every sum.  The Python layer passes whole views.
+ *   Every requested output is written whole: per-token sums of dead tokens and the view sums of wholly dead views are +0.0 (all bits
+ *       zero).  A workgroup whose tokens all lie at or past the prefix loads nothing: padded views are skipped, not summed and dropped.
+ *   Live entries are bit for bit those of gta_rep_grad_sums on the same buffers (the VARLEN twin of the instance it selects: the same
+ *       thread-to-row map, pair and group order, tree, head order and finish order).
+ *   Workspace (gta_rep_grad_workspace_bytes serves both entries), every other argument, check and error code: as in gta_rep_grad_sums. */
+int gta_rep_grad_sums_varlen(const GtaAttnDesc* desc, int32_t side, int32_t n_pairs,
+                             const void* a0, const int64_t* a0_stride, const void* b0, const int64_t* b0_stride,
+                             const void* a1, const int64_t* a1_stride, const void* b1, const int64_t* b1_stride,
+                             const int32_t* lens, float* view_sums, float* so2_sums, float* t2_sums,
+                             void* workspace, int64_t workspace_bytes, void* stream);
 
 /* softmax((scale * q k^T + key_bias) / tau) v with no rep at all (the fused kernel on an identity layout).
  * key_bias: [B,H,bias_pitch] fp32, added to scale*q.k BEFORE the division by tau; bias_pitch a multiple of 64 >= Tk; or NULL.

@@ -306,12 +306,42 @@ def audit_gen():
     return report, problems
 
 
+def audit_repgrad():
+    """The rep-gradient sums (gta_repgrad.hip): the six <ESZ, EUCLID, VEC> instances and their VARLEN twins (gta_rep_grad_sums_varlen).
+    Registers as the code object's metadata counts them (.vgpr_count), the static LDS and scratch; DESIGN.md 4.8 / 4.8c: no scratch, the
+    32 KiB reduction array, 44-64 VGPRs.  Hard: twelve instances, no scratch, and a VARLEN twin with the LDS of its instance."""
+    text = _asm("gta_repgrad.hip")
+    report, problems, seen = [], [], {}
+    for name, (esz, euclid, vec, varlen), body, _ in _kernels(text, r"gta_repgrad_kernelILi(\d)ELb(\d)ELb(\d)ELb(\d)E"):
+        meta = text[text.index(".amdhsa_kernel " + name):][:4000]
+        lds = int(re.search(r"\.amdhsa_group_segment_fixed_size\s+(\d+)", meta).group(1))
+        private = int(re.search(r"\.amdhsa_private_segment_fixed_size\s+(\d+)", meta).group(1))
+        vgpr = int(re.search(r"\.name:\s+" + re.escape(name) + r"\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)", text).group(1))
+        key = (int(esz), euclid == "1", vec == "1", varlen == "1")
+        row = {"kernel": f"gta_repgrad_kernel<{esz}, {'euclid' if key[1] else 'se3'}, {'vec' if key[2] else 'scalar'}{', varlen' if key[3] else ''}>",
+               "vgpr": vgpr, "lds_bytes": lds, "scratch": body.count("scratch_") + private}
+        seen[key] = row
+        report.append(row)
+        if row["scratch"]:
+            problems.append(f"{row['kernel']}: scratch in use ({row['scratch']})")
+        if vgpr > 64:
+            problems.append(f"perf: {row['kernel']}: {vgpr} VGPRs (DESIGN.md 4.8: 44-64)")
+    if len(seen) != 12:
+        problems.append(f"gta_repgrad.hip: {len(seen)} kernel instances found (expected 12)")
+    for key, row in seen.items():
+        if key[3] and (key[:3] + (False,) not in seen or row["lds_bytes"] != seen[key[:3] + (False,)]["lds_bytes"]):
+            problems.append(f"{row['kernel']}: no twin without VARLEN, or another LDS size")
+    return report, problems
+
+
 if __name__ == "__main__":
     rep, prob = audit()
     rep2, prob2 = audit_others()
     rep3, prob3 = audit_attn64()
     rep4, prob4 = audit_dkv64()
     rep5, prob5 = audit_gen()
+    rep6, prob6 = audit_repgrad()
+    rep5, prob5 = rep5 + rep6, prob5 + prob6
     for r in rep + rep2 + rep3 + rep4 + rep5:
         print(r)
     # (ADVICE r05) the build fails on the CORRECTNESS criteria only -- what hipcc does to the accumulator file around the generated statements, the
