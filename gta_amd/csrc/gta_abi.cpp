@@ -229,18 +229,21 @@ int varlen_flags(const GtaAttnDesc* d) {
     return GTA_OK;
 }
 
-// both fused forward entries.  varlen (gta_attn_fwd_varlen) is the explicit selector of per-scene key prefixes -- never "key_lens is non-null":
+// the fused forward entries.  varlen (gta_attn_fwd_varlen) is the explicit selector of per-scene key prefixes -- never "key_lens is non-null":
 // always the two-stage plan, with the VARLEN instances of the pre-pass and of gta_fwd2_kernel (GtaFwdSel::varlen selects them in
-// gta_fwd2_dispatch), whatever attention kernel gta_fwd_select would give the shape.
+// gta_fwd2_dispatch), whatever attention kernel gta_fwd_select would give the shape.  gather (gta_attn_fwd_gather; with varlen) is the explicit selector
+// of the GATHER instances of the pre-pass -- never "key_idx is non-null": the keys are the tokens key_idx names, key_lens counts them, and the
+// attention step is the VARLEN gta_fwd2_kernel under the same key_lens.  With GTA_FLAG_KV_READY the indices are not read.
 int fwd_call(const GtaAttnDesc* d, const void* q, const void* k, const void* v,
              const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
-             const float* trans_coeff, const float* tau, bool varlen, const int32_t* key_lens, void* out, float* lse,
-             void* workspace, int64_t workspace_bytes, void* stream) {
+             const float* trans_coeff, const float* tau, bool varlen, const int32_t* key_lens, bool gather, const int32_t* key_idx,
+             void* out, float* lse, void* workspace, int64_t workspace_bytes, void* stream) {
     int rc = check_common(d);
     if (rc) return rc;
     if (!k || !v || ((!q || !out) && !(d->flags & GTA_FLAG_PREP_ONLY))) return fail(GTA_E_BADARG, "null q/k/v/out");
     if (varlen) {
         if (!key_lens) return fail(GTA_E_BADARG, "null key_lens");
+        if (gather && !key_idx && !(d->flags & GTA_FLAG_KV_READY)) return fail(GTA_E_BADARG, "null key_idx");
         if (!workspace) return fail(GTA_E_BADARG, "per-scene key prefixes need the workspace of gta_attn_fwd_workspace_bytes()");
     }
     GtaFwdParams p;
@@ -258,6 +261,7 @@ int fwd_call(const GtaAttnDesc* d, const void* q, const void* k, const void* v,
     if (varlen) {       // (the selection gave the layout of the chunk table; the kernel is fixed)
         s.kind = GTA_FWD_FWD2; s.coal = false; s.qtiles = false; s.rows = 128; s.name = "gta_fwd2_kernel"; s.varlen = true;
         p.key_lens = key_lens;
+        if (gather) { s.gather = true; s.key_idx = (d->flags & GTA_FLAG_KV_READY) ? nullptr : key_idx; }
     } else if (t_prof && !(d->flags & GTA_FLAG_PREP_ONLY)) {      // (start / end stamps of every work item: gta_debug_profile_next_attention_kernel)
         if ((int64_t)d->B * d->H * ((d->Tq + s.rows - 1) / s.rows) <= t_prof_items) p.prof = t_prof;
         t_prof = nullptr;
@@ -281,7 +285,7 @@ extern "C" int gta_attn_fwd(const GtaAttnDesc* d, const void* q, const void* k, 
                             const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
                             const float* trans_coeff, const float* tau, void* out, float* lse,
                             void* workspace, int64_t workspace_bytes, void* stream) {
-    return fwd_call(d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, false, nullptr, out, lse, workspace, workspace_bytes, stream);
+    return fwd_call(d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, false, nullptr, false, nullptr, out, lse, workspace, workspace_bytes, stream);
 }
 
 extern "C" int gta_attn_fwd_varlen_supported(const GtaAttnDesc* desc) {
@@ -293,7 +297,17 @@ extern "C" int gta_attn_fwd_varlen(const GtaAttnDesc* d, const void* q, const vo
                                    const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
                                    const float* trans_coeff, const float* tau, const int32_t* key_lens, void* out, float* lse,
                                    void* workspace, int64_t workspace_bytes, void* stream) {
-    return fwd_call(d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, true, key_lens, out, lse, workspace, workspace_bytes, stream);
+    return fwd_call(d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, true, key_lens, false, nullptr, out, lse, workspace, workspace_bytes, stream);
+}
+
+// Any per-scene subset of the key tokens: the rules and the workspace of gta_attn_fwd_varlen, the GATHER instances of the pre-pass
+extern "C" int gta_attn_fwd_gather_supported(const GtaAttnDesc* desc) { return gta_attn_fwd_varlen_supported(desc); }
+
+extern "C" int gta_attn_fwd_gather(const GtaAttnDesc* d, const void* q, const void* k, const void* v,
+                                   const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
+                                   const float* trans_coeff, const float* tau, const int32_t* key_idx, const int32_t* key_lens, void* out, float* lse,
+                                   void* workspace, int64_t workspace_bytes, void* stream) {
+    return fwd_call(d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, true, key_lens, true, key_idx, out, lse, workspace, workspace_bytes, stream);
 }
 
 

@@ -36,6 +36,7 @@
 #include "gta_fwd2_tile.h"
 
 int gta_prep_dispatch(const GtaFwdParams& p, int dhp, int esz, bool varlen, hipStream_t stream);                  // gta_prep.hip
+int gta_prep_gather_dispatch(const GtaFwdParams& p, const int32_t* key_idx, int dhp, int esz, hipStream_t stream);
 int gta_qtiles_dispatch(const GtaFwdParams& p, hipStream_t stream);                                  // gta_fwd64.hip
 int gta_attn64_dispatch(const GtaFwdParams& p, const GtaFwdSel& s, int esz, hipStream_t stream);
 int gta_fwdc_dispatch(const GtaFwdParams& p, int layout, hipStream_t stream);                        // gta_fwd_cl.hip
@@ -838,7 +839,8 @@ int gta_fwd2_dispatch(GtaFwdParams& p, const GtaFwdSel& s, int dhp, int esz, boo
     // the q-side rep tiles (rho_q / rho_q^-1 on the matrix cores) only where this call's attention kernel uses them
     if (!run_flash || !s.qtiles) p.qtiles = nullptr;
     if (s.varlen && !p.key_lens) return GTA_E_BADARG;
-    if (run_prep) rc = gta_prep_dispatch(p, dhp, esz, s.varlen, stream);
+    if (s.gather && (!s.varlen || (run_prep && !s.key_idx))) return GTA_E_BADARG;
+    if (run_prep) rc = s.gather ? gta_prep_gather_dispatch(p, s.key_idx, dhp, esz, stream) : gta_prep_dispatch(p, dhp, esz, s.varlen, stream);
     else if (p.qtiles) rc = gta_qtiles_dispatch(p, stream);
     if (rc != GTA_OK || !run_flash) return rc;
     if (s.varlen) {

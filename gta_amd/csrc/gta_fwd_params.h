@@ -47,6 +47,10 @@ struct GtaFwdSel {
     int rows;                                   // query rows per work item
     const char* name;                           // the kernel's own name
     bool varlen = false;                        // the VARLEN instances of the pre-pass and of gta_fwd2_kernel: p.key_lens is the slot's reader (gta_attn_fwd_varlen sets it)
+    // the GATHER instances of the pre-pass (gta_attn_fwd_gather sets both, with varlen): the scene's keys are the tokens key_idx names, [B, Tk]
+    // int32 on the device, compacted into the prefix p.key_lens counts.  The attention kernel is the VARLEN one and never sees the indices.
+    bool gather = false;
+    const int32_t* key_idx = nullptr;
 };
 // p: the argument block with the operands of the call (p.kp = the workspace or null; p.kn, p.qtiles inside it)
 GtaFwdSel gta_fwd_select(const GtaFwdParams& p, int dhp, int esz);

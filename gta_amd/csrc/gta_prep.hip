@@ -47,10 +47,21 @@ GTA_DEV void dma_piece(const char* lds_dst, const char* src) {
 // those of padded views included: they are loaded but never used, since no valid row belongs to such a view.  So nothing a padded token
 // or view holds (NaN included) reaches the workspace.  The scene's images
 // and norms are then byte for byte those of a call on the scene alone with its key side cut to the prefix.
-template <int DHP, int ESZ, bool X3 = false, bool VARLEN = false>
-__global__ __launch_bounds__(256) void gta_kv_prep_kernel(const GtaFwdParams p) {
+//
+// GATHER (gta_attn_fwd_gather; VARLEN plus a gather): scene b's keys are ANY p.key_lens[b] of its tokens, compacted -- row r of tile j is built
+// from token key_idx[b * Tk + 64 j + r] (clamped into [0, Tk): no value moves a load out of the scene's K, V or table rows).  The token number
+// drives the raw-row DMA source, the (cos, sin) row and the view record; the rows past the count take the dead-row path above with the token
+// of the tile's row 0, which is live in every tile that is not skipped.  key_idx entries at or past the count are never read.  The GATHER
+// instances alone take the trailing argument (IDX = const int32_t*: key_idx, [B, Tk] on the device); without it IDX is empty and the kernel's
+// signature and argument block are what they were.
+GTA_DEV const int32_t* first_idx() { return nullptr; }
+GTA_DEV const int32_t* first_idx(const int32_t* a) { return a; }
+template <int DHP, int ESZ, bool X3 = false, bool VARLEN = false, bool GATHER = false, class... IDX>
+__global__ __launch_bounds__(256) void gta_kv_prep_kernel(const GtaFwdParams p, IDX... idx) {
     static_assert(!X3 || ESZ == 4, "split-bf16 images are for fp32 inputs");
     static_assert(!(X3 && VARLEN), "no fp32-faithful VARLEN instances");
+    static_assert(!GATHER || VARLEN, "the gather compacts into a per-scene prefix");
+    static_assert(sizeof...(IDX) == (GATHER ? 1 : 0), "key_idx comes with GATHER");
     using S = PrepSmem<DHP, ESZ, X3>;
     constexpr int CHP = S::CHP, U = S::RAW_UNITS;
     constexpr int IMG = BN * DHP * 2;                       // bytes of one bf16 tile image
@@ -99,6 +110,13 @@ __global__ __launch_bounds__(256) void gta_kv_prep_kernel(const GtaFwdParams p) 
         if (j * BN >= tk_b) return;
     }
 #define GTA_TKB (VARLEN ? tk_b : p.Tk)
+    // (GATHER) this lane's row's token: requested first of all, the DMA addresses depend on it
+    int t_idx = 0;
+    if constexpr (GATHER) {
+        const int32_t* key_idx = first_idx(idx...);
+        if (j * BN + lane < tk_b) t_idx = key_idx[(long)b * p.Tk + j * BN + lane];
+        t_idx = t_idx < 0 ? 0 : t_idx >= p.Tk ? p.Tk - 1 : t_idx;
+    }
 
     const char* kg = (const char*)p.k + ((long)b * p.k_sb + (long)h * p.k_sh) * ESZ;
     const char* vg = (const char*)p.v + ((long)b * p.v_sb + (long)h * p.v_sh) * ESZ;
@@ -124,7 +142,8 @@ __global__ __launch_bounds__(256) void gta_kv_prep_kernel(const GtaFwdParams p) 
     const int r = lane;
     const int t_raw = j * BN + r;
     const bool valid = t_raw < GTA_TKB;
-    const int t = valid ? t_raw : GTA_TKB - 1;
+    int t = valid ? t_raw : GTA_TKB - 1;
+    if constexpr (GATHER) t = valid ? t_idx : __builtin_amdgcn_readlane(t_idx, 0);      // (row 0 of a tile that is not skipped is live)
     f32x4_t cs_pre[CHP / 4][2] = {};
     if (p.cs_k) {
         const float* cs_base = p.cs_k + ((long)b * p.Tk + t) * 2 * p.nso2;
@@ -140,6 +159,13 @@ __global__ __launch_bounds__(256) void gta_kv_prep_kernel(const GtaFwdParams p) 
     }
     // raw rows -> LDS (coalesced LDS-DMA; the per-lane source address carries the swizzle): all of K, then all of V
     constexpr int NI = BN * U / 256;
+    // (GATHER) a lane serves row u / U here, not row `lane`: that row's token by a cross-lane read, once for the K and the V piece
+    int t_piece[GATHER ? NI : 1];
+    (void)t_piece;
+    if constexpr (GATHER) {
+#pragma unroll
+        for (int i = 0; i < NI; ++i) t_piece[i] = __shfl(t, ((wave * NI + i) * 64 + lane) / U);
+    }
 #pragma unroll
     for (int w2 = 0; w2 < 2; ++w2) {
         const char* g = w2 ? vg : kg;
@@ -154,6 +180,7 @@ __global__ __launch_bounds__(256) void gta_kv_prep_kernel(const GtaFwdParams p) 
             gu = gu < real_units ? gu : real_units - 1;
             int gr = j * BN + r;
             gr = gr < GTA_TKB ? gr : GTA_TKB - 1;
+            if constexpr (GATHER) gr = t_piece[i];
 #if defined(GTA_PREP_ABL) && GTA_PREP_ABL >= 4       // (levels 4, 5: no loads)
             if (p.Tk < 0)
 #endif
@@ -327,19 +354,32 @@ __global__ __launch_bounds__(256) void gta_kv_prep_kernel(const GtaFwdParams p) 
 #undef GTA_TKB
 }
 
-template <int DHP, int ESZ, bool X3 = false, bool VARLEN = false>
-int launch_prep(const GtaFwdParams& p, hipStream_t stream) {
+template <int DHP, int ESZ, bool X3 = false, bool VARLEN = false, class... IDX>
+int launch_prep(const GtaFwdParams& p, hipStream_t stream, IDX... idx) {
     using S = PrepSmem<DHP, ESZ, X3>;
-    if (int rc = gta_lds_optin<&gta_kv_prep_kernel<DHP, ESZ, X3, VARLEN>>(S::total(GTA_MAX_VIEWS))) return rc;
+    constexpr bool GATHER = sizeof...(IDX) == 1;
+    if (int rc = gta_lds_optin<&gta_kv_prep_kernel<DHP, ESZ, X3, VARLEN, GATHER, IDX...>>(S::total(GTA_MAX_VIEWS))) return rc;
     const int n_tiles = (p.Tk + BN - 1) / BN;
     const long rows = (long)p.B * n_tiles;
     long grid = (rows + 7) / 8 * 8 * p.H;
     if (p.qtiles && p.vrep_q) grid += ((long)p.B * p.Nq + 7) / 8 * 8;        // the q-side tile builders (see the kernel's head)
     if (grid > 0x7fffffffL) return GTA_E_UNSUPPORTED;
-    hipLaunchKernelGGL((gta_kv_prep_kernel<DHP, ESZ, X3, VARLEN>), dim3((unsigned)grid), dim3(256), S::total(p.vrep_k ? p.Nk : 0), stream, p);
+    hipLaunchKernelGGL((gta_kv_prep_kernel<DHP, ESZ, X3, VARLEN, GATHER, IDX...>), dim3((unsigned)grid), dim3(256), S::total(p.vrep_k ? p.Nk : 0), stream, p, idx...);
     return hipGetLastError() == hipSuccess ? GTA_OK : GTA_E_LAUNCH;
 }
 }  // namespace
+
+// the GATHER instances (gta_attn_fwd_gather): p.key_lens counts the compacted keys, key_idx names them
+int gta_prep_gather_dispatch(const GtaFwdParams& p, const int32_t* key_idx, int dhp, int esz, hipStream_t stream) {
+    if (!key_idx || !p.key_lens || (p.flags & GTA_FLAG_FP32_PRODUCTS)) return GTA_E_BADARG;
+    switch (dhp) {
+        case 32: return esz == 2 ? launch_prep<32, 2, false, true>(p, stream, key_idx) : launch_prep<32, 4, false, true>(p, stream, key_idx);
+        case 64: return esz == 2 ? launch_prep<64, 2, false, true>(p, stream, key_idx) : launch_prep<64, 4, false, true>(p, stream, key_idx);
+        case 96: return esz == 2 ? launch_prep<96, 2, false, true>(p, stream, key_idx) : launch_prep<96, 4, false, true>(p, stream, key_idx);
+        case 128: return esz == 2 ? launch_prep<128, 2, false, true>(p, stream, key_idx) : launch_prep<128, 4, false, true>(p, stream, key_idx);
+    }
+    return GTA_E_UNSUPPORTED;
+}
 
 int gta_prep_dispatch(const GtaFwdParams& p, int dhp, int esz, bool varlen, hipStream_t stream) {
     if (p.flags & GTA_FLAG_FP32_PRODUCTS) {             // split-bf16 images (gta_x3_takes: fp32 inputs, dh <= 64)

@@ -611,16 +611,58 @@ def key_lens_tensor(key_views: Tuple[int, ...], Pk: int, device) -> torch.Tensor
     return torch.tensor([n * Pk for n in key_views], dtype=torch.int32).to(device, non_blocking=True)
 
 
+def _key_mask_refusals(*, needs_grad=False, precise=False, pretransformed=False, kv_mode="auto"):
+    """what a call with ``key_mask`` cannot be combined with: said here, before anything is launched"""
+    if needs_grad:
+        raise native.GtaError("key_mask is forward-only (no backward through the gathered keys yet): call under torch.no_grad()")
+    if precise:
+        raise native.GtaError("key_mask has no precise=True (fp32-faithful) instances")
+    if pretransformed:
+        raise native.GtaError("key_mask with pretransformed=True: the gather lives in the K/V pre-pass, which that mode skips")
+    if kv_mode == "fused":
+        raise native.GtaError("key_mask runs the two-stage plan: kv_mode='fused' has no gather")
+
+
+def check_key_mask(key_mask, B: Optional[int] = None, Tk: Optional[int] = None):
+    """Validation of a key mask: a bool [B, Tk] tensor (the shape is held against B and Tk where given).  The values of a CPU mask are looked
+    at -- every scene needs at least one valid key --, those of a device mask are not: that would sync."""
+    if not torch.is_tensor(key_mask) or key_mask.dtype != torch.bool or key_mask.dim() != 2:
+        raise native.GtaError("key_mask must be a bool tensor of shape [B, Tk] (True: the key is attended)")
+    if B is not None and tuple(key_mask.shape) != (B, Tk):
+        raise native.GtaError(f"key_mask has shape {tuple(key_mask.shape)} for {B} scenes of {Tk} key tokens")
+    if not key_mask.is_cuda:
+        empty = (~key_mask.any(1)).nonzero().flatten().tolist()
+        if empty:
+            raise native.GtaError(f"key_mask: scenes {empty} have no valid key (every scene attends at least one)")
+
+
+def key_index_tensors(key_mask: torch.Tensor, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """key_mask (bool [B, Tk], True = attend) -> (key_idx [B, Tk] int32, key_lens [B] int32) on ``device``: what ``gta_attn_fwd_gather``
+    reads.  key_idx[b, :key_lens[b]] are scene b's valid tokens in ascending order (a stable sort of ~mask), the rest of the row its
+    masked tokens, which the kernel never reads.
+
+    A CPU mask is validated here -- every scene needs at least one valid key, else ``GtaError`` -- and uploaded.  A CUDA mask is turned into
+    indices on the device without a sync, so its values are not looked at: a scene with NO valid key then attends its token 0 alone (the
+    kernels clamp the count to 1, and the first index of an all-false row is 0)."""
+    check_key_mask(key_mask)
+    if key_mask.is_cuda and key_mask.device != torch.device(device):
+        raise native.GtaError(f"key_mask lives on {key_mask.device}, the call on {device}")
+    idx = torch.sort((~key_mask).to(torch.uint8), dim=1, stable=True).indices.to(torch.int32)
+    lens = key_mask.sum(1, dtype=torch.int32)
+    return idx.contiguous().to(device, non_blocking=True), lens.to(device, non_blocking=True)
+
+
 def _plan_key(family: str, flags, dt, B, H, Tk, dh, f_dims, so3_degree, Nk, scale, key_views):
     """what the images of a cache depend on besides the keys, reps and trans_coeff (the caller's contract, see gta_attention): the family
     ('fused' / 'staged': different tile images), the key side's shape and layout, the dtype (bf16 / fp32 inputs pick different instances), the
     arithmetic mode -- the fp32-faithful plan stores FOUR images per tile [K'hi | V'hi | K'lo | V'lo], the default plan two: a cache written
     under one plan must never be streamed under the other (the byte-size check alone let that through) --, under euclid the scale,
-    which the cached key bias -0.5 scale |k'|^2 carries, and last the view counts of a call with key_views (else None)."""
+    which the cached key bias -0.5 scale |k'|^2 carries, and last the view counts of a call with key_views (else None; the word "key_mask"
+    for a call with one: the cache then holds the indices and lengths its images were built under)."""
     euclid = bool(flags & native.FLAG_EUCLID)
     return (family, bool(flags & native.FLAG_FP32_PRODUCTS), bool(flags & native.FLAG_V_TRANSFORM), euclid, str(dt), B, H, int(Tk), dh,
             tuple(sorted((g, int(n)) for g, n in f_dims.items() if n)), int(so3_degree), int(Nk), float(scale) if euclid else None,
-            None if key_views is None else tuple(key_views))
+            None if key_views is None else key_views if isinstance(key_views, str) else tuple(key_views))
 
 
 def _two_stage_workspace(desc, flags, plan_key, kv_cache, device, need, cache_bytes=0):
@@ -670,6 +712,25 @@ def _varlen_forward(q, k, v, cfg, tables, trans_coeff, tau, key_lens, key_views=
     ws = _fused_workspace(c, cfg, kv_cache, key_views)
     native.attn_fwd_varlen(c.desc, c.q, c.k, c.v, tables.get("vrep_q"), tables.get("vrep_k"), tables.get("cs_q"), tables.get("cs_k"),
                            c.tc, c.ta, key_lens, c.out, c.lse, ws)
+    return c, ws
+
+
+def _gather_forward(q, k, v, cfg, tables, trans_coeff, tau, key_mask, kv_cache=None, key_idx=None, key_lens=None):
+    """The fused layouts with a key mask: ``gta_attn_fwd_gather`` -- the GATHER instances of the pre-pass compact the valid keys, the VARLEN
+    gta_fwd2_kernel attends over them.  ``key_idx`` / ``key_lens``: the ready-made tensors of ``key_index_tensors`` (``ForwardPlan``), built
+    here when None.  With ``kv_cache`` the first call stores both beside the images (plan key: "key_mask"); later calls run on the stored
+    lengths under GTA_FLAG_KV_READY and build nothing from their mask.  -> (the call, its workspace)"""
+    c = _setup_call(q, k, v, *cfg, tables, trans_coeff, tau)
+    ws = _fused_workspace(c, cfg, kv_cache, "key_mask")
+    if c.desc.flags & native.FLAG_KV_READY:
+        key_idx, key_lens = None, kv_cache["key_lens"]
+    else:
+        if key_lens is None:
+            key_idx, key_lens = key_index_tensors(key_mask, c.q.device)
+        if kv_cache is not None:
+            kv_cache["key_idx"], kv_cache["key_lens"] = key_idx, key_lens
+    native.attn_fwd_gather(c.desc, c.q, c.k, c.v, tables.get("vrep_q"), tables.get("vrep_k"), tables.get("cs_q"), tables.get("cs_k"),
+                           c.tc, c.ta, key_idx, key_lens, c.out, c.lse, ws)
     return c, ws
 
 
@@ -740,7 +801,7 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
                   euclid: bool = False, pretransformed: bool = False, use_dma: bool = True,
                   kv_mode: str = "auto", kv_cache: Optional[dict] = None, precise: Optional[bool] = None,
                   key_views=None, key_lens: Optional[torch.Tensor] = None, key_views_backward: bool = False,
-                  query_views=None, return_lse: bool = False):
+                  query_views=None, return_lse: bool = False, key_mask: Optional[torch.Tensor] = None):
     """Fused GTA attention on packed reps.  q [B,H,Tq,dh], k/v [B,H,Tk,dh] -> out [B,H,Tq,dh].
 
     kv_mode: 'prepass' = K/V rep pre-pass + lean attention kernel (two launches; at dh = 96 in the MSN layout the attention kernel is
@@ -781,7 +842,19 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
              rho-apply).  Under grad lse is a differentiable output like out -- the backward takes (dout, dlse), either may be missing -- in
              the default arithmetic (fused layouts and the rho-apply route) and with precise=True where the fused fp32-faithful backward runs
              (float32, dh <= 64); ``key_views_backward`` and the exact-fp32 route of precise=True (gta_plain32) raise ``GtaError``.
+    key_mask: a bool [B, Tk] tensor (True: the key is attended; None: every key is) -- ANY per-scene subset of the key tokens: views of
+             different size padded inside their slots, a missing view that is not the last, patches to ignore.  out (and lse, with
+             ``return_lse``) are those of the attention over the valid keys alone; whatever k, v and cs_k hold at masked tokens is never
+             used, NaN and Inf included.  The K/V pre-pass compacts the valid keys (``key_index_tensors``, ``gta_attn_fwd_gather``) and
+             masked tiles are skipped, not computed.  A CPU mask is validated (every scene needs a valid key); a CUDA mask is used without
+             a sync, and a scene of it with no valid key attends its token 0.  In self-attention the output rows of masked tokens are
+             computed like any other.  With ``kv_cache`` later calls must pass ``key_mask`` again (it is not looked at: they run on the
+             indices and lengths the first call stored).  Forward only, default arithmetic, two-stage plan, fused layouts; refused by name:
+             a call under grad, precise=True, pretransformed, kv_mode='fused', ``key_views`` beside it, and the staged and rho-apply
+             layouts (t2, euclid, so3 of degree 1, unaligned slabs), which have no gather pre-pass.
     """
+    if key_mask is not None and (key_views is not None or key_lens is not None or key_views_backward or query_views is not None):
+        raise native.GtaError("key_mask with key_views (or its companions): a call takes one key mask -- a prefix of views is a mask too")
     if query_views is not None and not key_views_backward:
         raise native.GtaError("query_views masks padded query rows in the backward: it needs key_views_backward=True")
     if key_views_backward and key_views is None:
@@ -819,6 +892,14 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
                                   "tables and poses that require grad must be CUDA tensors")
     how = dict(v_transform=v_transform, euclid=euclid, precise=bool(precise), needs_grad=needs_grad, key_views=key_views is not None,
                key_views_backward=bool(key_views_backward))
+    if key_mask is not None:
+        check_key_mask(key_mask, q.shape[0], k.shape[2])
+        flags = attention_route(tuple(q.shape), k.shape[2], q.dtype, f_dims, so3_degree, Nq, Nk, pretransformed=pretransformed, use_dma=use_dma,
+                                kv_mode=kv_mode, kv_cache=kv_cache is not None, v_transform=v_transform, euclid=euclid, precise=bool(precise),
+                                needs_grad=needs_grad, key_mask=True)
+        cfg = ({k_: int(v_) for k_, v_ in f_dims.items()}, int(so3_degree), Nq, Nk, float(scale), flags)
+        c = _gather_forward(q, k, v, cfg, packed, trans_coeff, tau, key_mask, kv_cache)[0]
+        return (c.out, c.lse) if return_lse else c.out
     flags = attention_route(tuple(q.shape), k.shape[2], q.dtype, f_dims, so3_degree, Nq, Nk, pretransformed=pretransformed, use_dma=use_dma,
                             kv_mode=kv_mode, kv_cache=kv_cache is not None, **how)
     # no fused kernel: 'staged' or 'apply' (under key_views: 'staged', or it raises)
@@ -900,13 +981,13 @@ def gta_attention_by_view_groups(q, k, v, f_dims: Dict[str, int], packed: dict, 
     K and V of a group are token slices of k and v (tokens are view-major: no copy where the slice keeps 16-byte rows); the key-side tables'
     rows are copied per group (vrep_k per view, cs_k / coord_k per token).  The number of key views is that of ``packed['vrep_k']``;
     a layout without view tables says it with ``num_key_views``.  Differentiable wherever ``gta_attention(..., return_lse=True)`` is.  Every
-    other keyword goes to ``gta_attention``; ``kv_cache``, ``key_views`` (with its companions) and ``return_attmap`` are refused."""
-    for name in ("kv_cache", "key_views", "key_lens", "key_views_backward", "query_views", "return_attmap"):
+    other keyword goes to ``gta_attention``; ``kv_cache``, ``key_views`` (with its companions), ``key_mask`` and ``return_attmap`` are refused."""
+    for name in ("kv_cache", "key_views", "key_lens", "key_views_backward", "query_views", "return_attmap", "key_mask"):
         if kw.get(name) is not None and kw.get(name) is not False:
             raise native.GtaError(f"gta_attention_by_view_groups takes no {name}: every group is a call of its own")
     return_lse = bool(kw.get("return_lse", False))
     kw = {n_: v_ for n_, v_ in kw.items() if n_ not in ("kv_cache", "key_views", "key_lens", "key_views_backward", "query_views", "return_attmap",
-                                                         "return_lse")}
+                                                         "return_lse", "key_mask")}
     sizes = None if isinstance(views_per_call, (int, np.integer)) and not isinstance(views_per_call, bool) else views_per_call
     try:
         sizes = None if sizes is None else [int(x) for x in sizes if not isinstance(x, bool) and isinstance(x, (int, np.integer))]
@@ -962,7 +1043,7 @@ KV_MODES = {
 def attention_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree: int, Nq: int, Nk: int, *, v_transform: bool = True,
                     euclid: bool = False, pretransformed: bool = False, use_dma: bool = True, kv_mode: str = "auto",
                     kv_cache: bool = False, precise: bool = False, needs_grad: bool = False, key_views: bool = False,
-                    key_views_backward: bool = False) -> Optional[int]:
+                    key_views_backward: bool = False, key_mask: bool = False) -> Optional[int]:
     """How ``gta_attention`` runs a call: the descriptor flags of the fused path, or None for the generic one (rho-apply kernels around the
     plain attention kernel).  q_shape = (B, H, Tq, dh); Tk keys; dtype of q.
 
@@ -972,11 +1053,24 @@ def attention_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree:
     key_views=True (the call comes with per-scene view counts): the flags are those of ``gta_attn_fwd_varlen`` -- always the two-stage plan,
     whatever ``kv_mode`` 'auto' would pick for the shape -- or None for the generic layouts (``generic_route`` then answers for its varlen
     entry); the combinations that have no masked kernel raise ``GtaError``.  key_views_backward=True lets needs_grad through: the same flags
-    serve ``gta_attn_bwd_varlen``."""
+    serve ``gta_attn_bwd_varlen``.
+
+    key_mask=True (the call comes with a key mask): the flags of ``gta_attn_fwd_gather`` -- the two-stage plan --, never None: the layouts
+    without a fused kernel have no gather pre-pass and raise ``GtaError`` like every other combination without one."""
     if kv_mode not in KV_MODES:
         raise ValueError(f"kv_mode {kv_mode!r}")
     flags = KV_MODES[kv_mode] | _layout_flags(v_transform, euclid) | (0 if use_dma else native.FLAG_NO_DMA)
     probe = lambda fl: _probe(dtype, q_shape, Tk, f_dims, so3_degree, Nq, Nk, fl)
+    if key_mask:
+        if key_views:
+            raise native.GtaError("key_mask with key_views: a call takes one key mask")
+        _key_mask_refusals(needs_grad=needs_grad, precise=precise, pretransformed=pretransformed, kv_mode=kv_mode)
+        rc = native.attn_fwd_supported(probe(flags))
+        if rc == native.E_UNSUPPORTED:
+            raise native.GtaError("key_mask: the staged and rho-apply layouts (t2, euclid, so3 of degree 1, unaligned slabs) have no gather "
+                                  f"pre-pass: gta_attn_fwd_supported: {native.lib().gta_strerror(rc).decode()}")
+        native.check(native.attn_fwd_gather_supported(probe(flags)), "gta_attn_fwd_gather_supported")
+        return flags
     if key_views:
         _key_views_refusals(needs_grad=needs_grad, precise=precise, pretransformed=pretransformed, kv_mode=kv_mode,
                             key_views_backward=key_views_backward)

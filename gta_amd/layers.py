@@ -160,6 +160,8 @@ class Attention(nn.Module):
         if self.elementwise_mul:                                          # layers.py:410-419
             if extras.get("key_views") is not None:
                 raise _gta.native.GtaError("key_views: the elementwise_mul ablation has no per-scene key mask")
+            if extras.get("key_mask") is not None:
+                raise _gta.native.GtaError("key_mask: the elementwise_mul ablation has no key mask")
             ex = dict(vecrep_q=self.rep_to_vec(extras["flattened_rep_q"]), vecrep_k=self.rep_to_vec(extras["flattened_rep_k"]),
                       vecinvrep_q=self.rep_to_vec(extras["flattened_invrep_q"]))
             out, _ = _gta.multihead_vecrep_attention(q, k, v, attn_fn=self, extras=ex, tau=tau)
@@ -173,6 +175,10 @@ class Attention(nn.Module):
         key_views = extras.get("key_views") if extras is not None else None
         if key_views is not None and return_attmap:
             raise _gta.native.GtaError("key_views with return_attmap: the dense attention map has no per-scene key mask")
+        # a bool [B, Tk] mask of the keys to attend (srt.TransformingSRT's input_mask): absent by default
+        key_mask = extras.get("key_mask") if extras is not None else None
+        if key_mask is not None and return_attmap:
+            raise _gta.native.GtaError("key_mask with return_attmap: the dense attention map has no key mask")
         # (training on such batches) the opt-in backward, and the valid query views of a self-attention layer -- both absent by default
         kvb = bool(extras.get("key_views_backward")) if extras is not None else False
         query_views = extras.get("query_views") if extras is not None else None
@@ -183,7 +189,7 @@ class Attention(nn.Module):
             trans_coeff=self.trans_coeff, tau=tau,
             scale=self.scale, v_transform=self.method_args.get("v_transform", True), euclid=self.euclid,
             kv_cache=kv_cache, precise=self.precise and q.dtype == torch.float32 and kv_cache is None,
-            **({"key_views": key_views} if key_views is not None else {}),
+            **({"key_views": key_views} if key_views is not None else {}), **({"key_mask": key_mask} if key_mask is not None else {}),
             **({"key_views_backward": True} if kvb else {}), **({"query_views": query_views} if query_views is not None else {}))
         out = out.permute(0, 2, 1, 3).reshape(B, Tq, H * dh)              # free: out is [B,Tq,H,dh] in memory
         attn = None

@@ -51,6 +51,7 @@ ABI_SYMBOLS = (
     "gta_attn_fwd_varlen", "gta_attn_fwd_varlen_supported", "gta_attn_fwd_staged_varlen", "gta_attn_fwd_staged_varlen_supported",
     "gta_attn_bwd_varlen", "gta_attn_bwd_varlen_supported",
     "gta_attn_bwd_dlse", "gta_attn_bwd_dlse_supported", "gta_attn_merge", "gta_attn_merge_bwd",
+    "gta_attn_fwd_gather", "gta_attn_fwd_gather_supported",
 )
 MERGE_MAX = 8           # partial attentions per gta_attn_merge call
 
@@ -140,6 +141,9 @@ def lib():
         # per-scene key prefixes: the signatures above with key_lens ([B] int32, device) in front of out
         L.gta_attn_fwd_varlen.argtypes = [ctypes.POINTER(GtaAttnDesc)] + [c_void_p] * 13 + [c_int64, c_void_p]
         L.gta_attn_fwd_varlen_supported.argtypes = [ctypes.POINTER(GtaAttnDesc)]
+        # gta_attn_fwd_varlen with key_idx ([B, Tk] int32, device) in front of key_lens
+        L.gta_attn_fwd_gather.argtypes = [ctypes.POINTER(GtaAttnDesc)] + [c_void_p] * 14 + [c_int64, c_void_p]
+        L.gta_attn_fwd_gather_supported.argtypes = [ctypes.POINTER(GtaAttnDesc)]
         L.gta_attn_fwd_staged_varlen.argtypes = [ctypes.POINTER(GtaAttnDesc)] + [c_void_p] * 15 + [c_int64, c_void_p]
         L.gta_attn_fwd_staged_varlen_supported.argtypes = [ctypes.POINTER(GtaAttnDesc)]
         # gta_attn_bwd with key_lens, q_lens ([B] int32, device; q_lens may be NULL) in front of kv_images
@@ -326,14 +330,25 @@ def _check_key_lens(key_lens, B: int, device):
         raise GtaError(f"key_lens must be a contiguous int32 tensor of shape ({B},) on {device}")
 
 
-def _fwd_call(entry: str, desc: GtaAttnDesc, qkv, tables, out, lse, workspace, key_lens=None):
-    """The four forward entries: ``tables`` are the float operands between v and out in the entry's order; the *_varlen entries take
-    ``key_lens`` ([B] int32 on the device) in front of out."""
-    _require_cuda(*qkv, out, workspace, key_lens)
+def _check_key_idx(key_idx, B: int, Tk: int, device):
+    if (not torch.is_tensor(key_idx) or key_idx.dtype != torch.int32 or key_idx.device != device or tuple(key_idx.shape) != (B, Tk)
+            or not key_idx.is_contiguous()):
+        raise GtaError(f"key_idx must be a contiguous int32 tensor of shape ({B}, {Tk}) on {device}")
+
+
+def _fwd_call(entry: str, desc: GtaAttnDesc, qkv, tables, out, lse, workspace, key_lens=None, key_idx=None):
+    """The forward entries: ``tables`` are the float operands between v and out in the entry's order; the *_varlen entries take
+    ``key_lens`` ([B] int32 on the device) in front of out, gta_attn_fwd_gather ``key_idx`` ([B, Tk] int32 on the device; None only under
+    FLAG_KV_READY) and ``key_lens``."""
+    _require_cuda(*qkv, out, workspace, key_lens, key_idx)
     lens = ()
-    if entry.endswith("_varlen"):
+    if entry.endswith("_varlen") or entry.endswith("_gather"):
         _check_key_lens(key_lens, desc.B, workspace.device)
         lens = (_ptr(key_lens),)
+    if entry.endswith("_gather"):
+        if key_idx is not None or not desc.flags & FLAG_KV_READY:
+            _check_key_idx(key_idx, desc.B, desc.Tk, workspace.device)
+        lens = (_ptr(key_idx),) + lens
     check(getattr(lib(), entry)(ctypes.byref(desc), *map(_ptr, qkv), *map(_ptr, tables), *lens, _ptr(out), _ptr(lse), _ptr(workspace),
                                 0 if workspace is None else workspace.numel(), _stream()), entry)
 
@@ -349,6 +364,13 @@ def attn_fwd_varlen(desc: GtaAttnDesc, q, k, v, vrep_q, vrep_k, cs_q, cs_k, tran
     """``attn_fwd`` on the two-stage plan with scene b attending over its first key_lens[b] key tokens ([B] int32 on the device);
     workspace: uint8 CUDA tensor of >= attn_fwd_workspace_bytes(desc) bytes (sized by Tk, not by the prefixes)."""
     _fwd_call("gta_attn_fwd_varlen", desc, (q, k, v), (vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau), out, lse, workspace, key_lens)
+
+
+def attn_fwd_gather(desc: GtaAttnDesc, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, key_idx, key_lens, out, lse, workspace: torch.Tensor):
+    """``attn_fwd_varlen`` with scene b attending over the key_lens[b] tokens key_idx[b, :key_lens[b]] names (any order; [B, Tk] int32 on the
+    device, see ``gta.key_index_tensors``): the pre-pass compacts them into the prefix the attention kernel walks.  key_idx may be None
+    under FLAG_KV_READY (it is not read)."""
+    _fwd_call("gta_attn_fwd_gather", desc, (q, k, v), (vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau), out, lse, workspace, key_lens, key_idx)
 
 
 def attn_fwd_staged(desc: GtaAttnDesc, q, k, v, vrep_q, vrep_k, cs_q, cs_k, coord_q, coord_k, trans_coeff, tau, out, lse,
@@ -385,6 +407,11 @@ def attn_fwd_staged_supported(desc: GtaAttnDesc) -> int:
 def attn_fwd_varlen_supported(desc: GtaAttnDesc) -> int:
     """0 when gta_attn_fwd_varlen (per-scene key prefixes on the two-stage plan) serves desc, else a GTA_E_* code; needs no GPU"""
     return lib().gta_attn_fwd_varlen_supported(ctypes.byref(desc))
+
+
+def attn_fwd_gather_supported(desc: GtaAttnDesc) -> int:
+    """0 when gta_attn_fwd_gather (any per-scene subset of the key tokens, fused layouts) serves desc, else a GTA_E_* code; needs no GPU"""
+    return lib().gta_attn_fwd_gather_supported(ctypes.byref(desc))
 
 
 def attn_fwd_staged_varlen_supported(desc: GtaAttnDesc) -> int:

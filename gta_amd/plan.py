@@ -53,13 +53,22 @@ class ForwardPlan:
     to the plan and are overwritten by every call.
 
     ``key_views``: per-scene numbers of valid input views (``gta_attention``), fixed when the plan is built: validated on the host and
-    turned into the device tensor of key lengths once (``key_lens``); every call then goes through the varlen entry of its family."""
+    turned into the device tensor of key lengths once (``key_lens``); every call then goes through the varlen entry of its family.
+
+    ``key_mask``: a bool [B, Tk] mask of the keys to attend (``gta_attention``), fixed when the plan is built: its index and length tensors
+    are built once (``key_idx``, ``key_lens``) and every call goes through ``gta_attn_fwd_gather``.  Fused layouts only; not with ``key_views``."""
 
     def __init__(self, q, k, v, f_dims: dict, *, so3_degree: int = 0, Nq: int = 1, Nk: int = 1,
-                 scale: Optional[float] = None, v_transform: bool = True, flags: int = 0, euclid: bool = False, key_views=None):
+                 scale: Optional[float] = None, v_transform: bool = True, flags: int = 0, euclid: bool = False, key_views=None,
+                 key_mask=None):
         native._require_cuda(q, k, v)
         B, H, Tq, dh = q.shape
-        self.key_views = self.key_lens = None
+        self.key_views = self.key_lens = self.key_idx = None
+        if key_mask is not None:
+            from .gta import check_key_mask
+            if key_views is not None:
+                raise native.GtaError("key_mask with key_views: a plan takes one key mask")
+            check_key_mask(key_mask, B, k.shape[2])
         if key_views is not None:
             from .gta import check_key_views, key_lens_tensor
             self.key_views = check_key_views(key_views, B, Nk)
@@ -75,14 +84,21 @@ class ForwardPlan:
         self._staged = family == "staged"
         if self.key_views is not None:
             self.key_lens = key_lens_tensor(self.key_views, k.shape[2] // Nk, q.device)
+        if key_mask is not None:
+            from .gta import key_index_tensors
+            if self._staged:
+                raise native.GtaError("key_mask: the staged layouts (t2, euclid, so3 of degree 1, unaligned slabs) have no gather pre-pass")
+            native.check(native.attn_fwd_gather_supported(self.desc), "gta_attn_fwd_gather_supported")
+            self.key_idx, self.key_lens = key_index_tensors(key_mask, q.device)
         self.ws = torch.empty(native.attn_fwd_staged_workspace_bytes(self.desc) if self._staged else native.attn_fwd_workspace_bytes(self.desc),
                               device=q.device, dtype=torch.uint8)
         # the entry every call goes through, resolved once: its name (gta_attn_fwd[_staged][_varlen]), the bound function, whether the coordinate
         # tables are among its arguments, and the arguments that never change (key_lens where it takes them; the plan's own buffers)
-        self._entry = "gta_attn_fwd" + ("_staged" if self._staged else "") + ("_varlen" if self.key_lens is not None else "")
+        self._entry = "gta_attn_fwd" + ("_staged" if self._staged else "") + ("_gather" if self.key_idx is not None else
+                                                                              "_varlen" if self.key_lens is not None else "")
         self._fn = getattr(native.lib(), self._entry)
         p = native._ptr
-        self._tail = (() if self.key_lens is None else (p(self.key_lens),)) + (p(self.out), p(self.lse), p(self.ws), self.ws.numel())
+        self._tail = (() if self.key_idx is None else (p(self.key_idx),)) + (() if self.key_lens is None else (p(self.key_lens),)) + (p(self.out), p(self.lse), p(self.ws), self.ws.numel())
         self._sig = (tuple(q.shape), tuple(q.stride()), tuple(k.shape), tuple(k.stride()), tuple(v.stride()), q.dtype)
         self._need_view = f_dims.get("se3", 0) > 0 or f_dims.get("so3", 0) > 0
         self._need_cs = f_dims.get("so2", 0) > 0

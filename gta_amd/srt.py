@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 from torch.nn import init
 
+from . import native
 from .layers import Transformer
 from .reps import pre_compute_reps_decoder, pre_compute_reps_encoder
 
@@ -172,7 +173,7 @@ class TransformingSRT(nn.Module):
         return self.decoder(z, x, rays, extras)
 
     def forward(self, input_images, input_camera_pos, input_rays, target_camera_pos, target_rays, extras=None, input_views=None,
-                input_views_backward=False):
+                input_views_backward=False, input_mask=None):
         """``input_views``: per-scene numbers of valid input views (a host sequence of length B, each in 1..N) for batches that mix
         view counts: scene b's first ``input_views[b]`` views are its input, the rest of its [N, ...] slots is padding that no valid
         token ever attends to -- in the encoder's self-attention and in the decoder's cross-attention (``gta_attention``'s
@@ -180,8 +181,18 @@ class TransformingSRT(nn.Module):
         differentiable route (``key_views_backward``; fused layouts), and the encoder's self-attention layers also get
         ``query_views = input_views``, so the tokens of padded views send no gradient into the valid ones.  ``extras['input_transforms']``,
         ``['input_coord']`` and ``['target_*']`` may require grad: poses and coordinates get their gradients as without ``input_views``,
-        exact zeros for the padded views' extrinsics and the padded tokens' coordinates, whatever those hold (zeros included)."""
+        exact zeros for the padded views' extrinsics and the padded tokens' coordinates, whatever those hold (zeros included).
+
+        ``input_mask``: a bool [B, N, P] or [B, N * P] tensor over the scene tokens (N views of P patches; True: a valid token) -- any
+        subset: smaller views padded inside their slots, a missing view that is not the last, patches to ignore.  No token attends to a
+        masked one, in the encoder's self-attention and in the decoder's cross-attention (``gta_attention``'s ``key_mask``); the scene
+        tokens of masked positions are still computed and unspecified.  Inference only; not together with ``input_views``."""
         extras = {} if extras is None else extras
+        if input_mask is not None:
+            if input_views is not None:
+                raise native.GtaError("input_mask with input_views: a call takes one key mask -- a prefix of views is a mask too")
+            extras = dict(extras)
+            extras["key_mask"] = _token_mask(input_mask)
         if input_views is not None:
             extras = dict(extras)                      # the caller's dict never carries these counts into a later call (as render_image)
             extras["key_views"] = input_views
@@ -194,8 +205,16 @@ class TransformingSRT(nn.Module):
         return self.decode(z, target_camera_pos, target_rays, extras=extras)
 
 
+def _token_mask(input_mask):
+    """[B, N, P] or [B, N * P] bool -> [B, N * P] (view-major tokens, as the scene tokens are)"""
+    if not torch.is_tensor(input_mask) or input_mask.dtype != torch.bool or input_mask.dim() not in (2, 3):
+        raise native.GtaError("input_mask must be a bool tensor of shape [B, N, P] or [B, N * P]")
+    return input_mask.flatten(1)
+
+
 @torch.no_grad()
-def render_image(model: "TransformingSRT", z, camera_pos, rays, extras, max_num_rays: int = 8192, reuse_kv: bool = True, input_views=None):
+def render_image(model: "TransformingSRT", z, camera_pos, rays, extras, max_num_rays: int = 8192, reuse_kv: bool = True, input_views=None,
+                 input_mask=None):
     """Full-image decode of one target view per scene, in query chunks (trainer.py:137-181).
 
     z [B,K,C] scene tokens from ``model.encoder`` (whose call also left the key-side reps in ``extras``);
@@ -203,7 +222,9 @@ def render_image(model: "TransformingSRT", z, camera_pos, rays, extras, max_num_
     Returns ``(img [B,h,w,3], {})``.  The reference re-projects K/V and re-applies rho_k for every chunk of every
     layer; here (``reuse_kv``) each cross-attention layer keeps its K/V projection and its K'/V' tile images across
     the chunks (GTA_FLAG_KV_READY), so a chunk costs the query side plus the attention kernel only.
-    ``input_views``: per-scene numbers of valid input views (``TransformingSRT.forward``); the cached images are then the masked ones."""
+    ``input_views``: per-scene numbers of valid input views (``TransformingSRT.forward``); the cached images are then the masked ones.
+    ``input_mask``: a bool mask over the scene tokens (``TransformingSRT.forward``) instead: every layer's cache then holds the compacted
+    images with the indices and lengths they were built under."""
     from .gta import make_2dcoord
     B, h, w = rays.shape[:3]
     coord = torch.from_numpy(make_2dcoord(h, w)).to(z.device).flatten(0, 1)[None].expand(B, -1, -1)   # [B,h*w,2]
@@ -213,6 +234,10 @@ def render_image(model: "TransformingSRT", z, camera_pos, rays, extras, max_num_
     ex = dict(extras)                                  # the caller's dict keeps its own target_* entries
     if input_views is not None:
         ex["key_views"] = input_views
+    if input_mask is not None:
+        if input_views is not None:
+            raise native.GtaError("input_mask with input_views: a call takes one key mask -- a prefix of views is a mask too")
+        ex["key_mask"] = _token_mask(input_mask)
     if reuse_kv:
         ex["gta_kv_cache"] = {}
     for i in range(0, h * w, max_num_rays):

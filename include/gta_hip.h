@@ -331,6 +331,24 @@ int gta_attn_fwd_staged_varlen(const GtaAttnDesc* desc, const void* q, const voi
                                const float* coord_q, const float* coord_k, const float* trans_coeff, const float* tau,
                                const int32_t* key_lens, void* out, float* lse, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Any per-scene subset of the key tokens (gta_attention's key_mask): scene b attends over the key_lens[b] tokens
+ * key_idx[b, 0 .. key_lens[b]) names, in any order (softmax attention does not depend on the order of its keys).  The pre-pass compacts
+ * them: image row r of tile j of scene b is built from token key_idx[b, 64 j + r], with that token's K / V row, cs_k row and view record;
+ * the attention step is the VARLEN gta_fwd2_kernel of gta_attn_fwd_varlen under the same key_lens, and what that entry says of its
+ * workspace (sized by Tk, the first ceil(key_lens[b] / 64) tiles of a scene's slot written, the rest untouched) holds here.
+ *   key_idx: [B, Tk] int32 on the device, token numbers in [0, Tk) (the kernel clamps into that range, so no value moves a load out of the
+ *       scene's rows; the Python layer builds them from a mask).  Entries at or past key_lens[b] are never read.  Tokens no index names are
+ *       never loaded: their k, v and cs_k rows may hold anything, NaN and Inf included.  NULL: GTA_E_BADARG, unless GTA_FLAG_KV_READY is set
+ *       -- the images are there already and key_idx is not read.
+ *   key_lens: as in gta_attn_fwd_varlen (NULL: GTA_E_BADARG); a GTA_FLAG_KV_READY call must come with the key_lens the images were built under.
+ *   gta_attn_fwd_gather_supported: what gta_attn_fwd_varlen_supported answers.  Forward only; fused layouts only.
+ *   Every other argument, check and error code: as in gta_attn_fwd_varlen. */
+int gta_attn_fwd_gather_supported(const GtaAttnDesc* desc);
+int gta_attn_fwd_gather(const GtaAttnDesc* desc, const void* q, const void* k, const void* v,
+                        const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
+                        const float* trans_coeff, const float* tau, const int32_t* key_idx, const int32_t* key_lens, void* out, float* lse,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+
 /* -------------------------------------------------------------------------------------------
  * Gradients of the reps: camera poses and patch coordinates (what autograd over gta.py:134-279 gives the reference's
  * se3rep / inv_se3rep / so2rep / t2rep tensors; the Wigner-D blocks stay detached, gta.py:194-197,267).  A pass after the

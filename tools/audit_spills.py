@@ -84,9 +84,10 @@ def audit_others():
     one step's 32 MFMAs) free of scratch accesses."""
     report, problems = [], []
     text = _asm("gta_prep.hip", ("-fno-slp-vectorize",))
-    for name, (dhp, esz, x3, varlen), body, vgpr in _kernels(text, r"gta_kv_prep_kernelILi(\d+)ELi(\d+)ELb(\d)ELb(\d)E"):
-        row = {"kernel": f"gta_kv_prep_kernel<{dhp},{esz}{', x3' if x3 == '1' else ''}{', varlen' if varlen == '1' else ''}>", "vgpr": vgpr,
-               "scratch": body.count("scratch_")}
+    # template arguments <DHP, ESZ, X3, VARLEN, GATHER>; the GATHER instances (gta_attn_fwd_gather) are held to every rule of the others
+    for name, (dhp, esz, x3, varlen, gather), body, vgpr in _kernels(text, r"gta_kv_prep_kernelILi(\d+)ELi(\d+)ELb(\d)ELb(\d)ELb(\d)E"):
+        row = {"kernel": f"gta_kv_prep_kernel<{dhp},{esz}{', x3' if x3 == '1' else ''}{', varlen' if varlen == '1' else ''}{', gather' if gather == '1' else ''}>",
+               "vgpr": vgpr, "scratch": body.count("scratch_")}
         report.append(row)
         if row["scratch"]:
             problems.append(f"perf: {row['kernel']}: {row['scratch']} scratch accesses")
