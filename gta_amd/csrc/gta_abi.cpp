@@ -28,6 +28,7 @@ int gta_bwd_dispatch(const GtaBwdParams& p, const float* dlse, int dhp, int esz,
 int gta_merge_dispatch(const GtaMergeParams& p, int esz, hipStream_t stream);
 int gta_merge_bwd_dispatch(const GtaMergeBwdParams& p, int esz, hipStream_t stream);
 int gta_bwd_varlen_dispatch(const GtaBwdParams& p, const int32_t* key_lens, const int32_t* q_lens, int dhp, int esz, hipStream_t stream);
+int gta_bwd_gather_dispatch(const GtaBwdParams& p, const int32_t* key_idx, const int32_t* key_lens, int dhp, int esz, hipStream_t stream);
 
 namespace {
 
@@ -444,12 +445,13 @@ int bwd_flags(const GtaAttnDesc* d) {
     return GTA_OK;
 }
 
-// the three backward entries.  varlen (gta_attn_bwd_varlen) is the explicit selector of the VARLEN instances -- never "key_lens is non-null";
-// with_dlse (gta_attn_bwd_dlse) likewise selects the instances that read dlse
+// the four backward entries.  varlen (gta_attn_bwd_varlen) is the explicit selector of the VARLEN instances -- never "key_lens is non-null";
+// gather (gta_attn_bwd_gather; with varlen, q_lens null) that of the GATHER dK/dV walk -- never "key_idx is non-null"; with_dlse
+// (gta_attn_bwd_dlse) likewise selects the instances that read dlse
 int bwd_call(const GtaAttnDesc* d, const void* q, const void* k, const void* v, const void* out,
              const void* dout, const float* lse, const float* vrep_q, const float* vrep_k,
              const float* cs_q, const float* cs_k, const float* trans_coeff, const float* tau,
-             bool varlen, const int32_t* key_lens, const int32_t* q_lens, bool with_dlse, const float* dlse,
+             bool varlen, const int32_t* key_lens, const int32_t* q_lens, bool gather, const int32_t* key_idx, bool with_dlse, const float* dlse,
              const void* kv_images, void* dq, void* dk, void* dv, const int64_t* dqkv_stride,
              const int64_t* dout_stride, float* dtrans_coeff, float* dtau, void* workspace,
              int64_t workspace_bytes, void* stream) {
@@ -457,7 +459,10 @@ int bwd_call(const GtaAttnDesc* d, const void* q, const void* k, const void* v, 
     if (rc) return rc;
     if (varlen) {
         if (!key_lens) return fail(GTA_E_BADARG, "null key_lens");
+        if (gather && !key_idx) return fail(GTA_E_BADARG, "null key_idx (the backward scatters dk / dv through it, with kv_images too)");
         if ((rc = varlen_flags(d))) return rc;
+    } else if (gather) {
+        return fail(GTA_E_BADARG, "the gather comes with per-scene key counts");
     }
     if (!q || !k || !v || !out || !dout || !lse || !dq || !dk || !dv || !dqkv_stride || !dout_stride || !workspace)
         return fail(GTA_E_BADARG, "null argument");
@@ -484,6 +489,7 @@ int bwd_call(const GtaAttnDesc* d, const void* q, const void* k, const void* v, 
         if (varlen) {                      // the VARLEN instance of the pre-pass: the images of gta_attn_fwd_varlen under the same key_lens
             s.varlen = true;
             f.key_lens = key_lens;
+            if (gather) { s.gather = true; s.key_idx = key_idx; }      // (the GATHER instance: the images of gta_attn_fwd_gather under the same index)
         }
         rc = gta_fwd2_dispatch(f, s, dhp, esz, true, false, (hipStream_t)stream);
         if (rc) return fail(rc, "K/V pre-pass launch failed");
@@ -506,7 +512,8 @@ int bwd_call(const GtaAttnDesc* d, const void* q, const void* k, const void* v, 
     p.Pq = d->Tq / d->Nq; p.Pk = d->Tk / d->Nk; p.invPq = 1.0f / (float)p.Pq; p.invPk = 1.0f / (float)p.Pk;
     p.dh = d->dh; p.nso2 = d->d_so2 / 2; p.flags = d->flags; p.scale = d->scale;
     if (d->H > 65535 || d->B > 65535) return fail(GTA_E_UNSUPPORTED, "B or H above 65535");
-    return launch_status(varlen ? gta_bwd_varlen_dispatch(p, key_lens, q_lens, dhp, esz, (hipStream_t)stream)
+    return launch_status(gather ? gta_bwd_gather_dispatch(p, key_idx, key_lens, dhp, esz, (hipStream_t)stream)
+                         : varlen ? gta_bwd_varlen_dispatch(p, key_lens, q_lens, dhp, esz, (hipStream_t)stream)
                                 : gta_bwd_dispatch(p, with_dlse ? dlse : nullptr, dhp, esz, (hipStream_t)stream), "no kernel instance");
 }
 }  // namespace
@@ -518,7 +525,7 @@ extern "C" int gta_attn_bwd(const GtaAttnDesc* d, const void* q, const void* k, 
                             const int64_t* dout_stride, float* dtrans_coeff, float* dtau, void* workspace,
                             int64_t workspace_bytes,
                             void* stream) {
-    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, false, nullptr, nullptr, false, nullptr, kv_images, dq, dk, dv,
+    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, false, nullptr, nullptr, false, nullptr, false, nullptr, kv_images, dq, dk, dv,
                     dqkv_stride, dout_stride, dtrans_coeff, dtau, workspace, workspace_bytes, stream);
 }
 
@@ -534,7 +541,7 @@ extern "C" int gta_attn_bwd_dlse(const GtaAttnDesc* d, const void* q, const void
                                  const void* kv_images, void* dq, void* dk, void* dv, const int64_t* dqkv_stride,
                                  const int64_t* dout_stride, float* dtrans_coeff, float* dtau, void* workspace,
                                  int64_t workspace_bytes, void* stream) {
-    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, false, nullptr, nullptr, true, dlse, kv_images, dq, dk, dv,
+    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, false, nullptr, nullptr, false, nullptr, true, dlse, kv_images, dq, dk, dv,
                     dqkv_stride, dout_stride, dtrans_coeff, dtau, workspace, workspace_bytes, stream);
 }
 
@@ -548,8 +555,23 @@ extern "C" int gta_attn_bwd_varlen(const GtaAttnDesc* d, const void* q, const vo
                                    const void* kv_images, void* dq, void* dk, void* dv, const int64_t* dqkv_stride,
                                    const int64_t* dout_stride, float* dtrans_coeff, float* dtau, void* workspace,
                                    int64_t workspace_bytes, void* stream) {
-    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, true, key_lens, q_lens, false, nullptr, kv_images, dq, dk, dv,
+    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, true, key_lens, q_lens, false, nullptr, false, nullptr, kv_images, dq, dk, dv,
                     dqkv_stride, dout_stride, dtrans_coeff, dtau, workspace, workspace_bytes, stream);
+}
+
+// Backward over any per-scene subset of the key tokens: gta_attn_bwd_varlen (no q_lens) with the GATHER instances of the dK/dV walk and, when
+// the images are rebuilt, of the K/V pre-pass
+extern "C" int gta_attn_bwd_gather_supported(const GtaAttnDesc* desc) { return gta_attn_bwd_varlen_supported(desc); }
+
+extern "C" int gta_attn_bwd_gather(const GtaAttnDesc* d, const void* q, const void* k, const void* v, const void* out,
+                                   const void* dout, const float* lse, const float* vrep_q, const float* vrep_k,
+                                   const float* cs_q, const float* cs_k, const float* trans_coeff, const float* tau,
+                                   const int32_t* key_idx, const int32_t* key_lens,
+                                   const void* kv_images, void* dq, void* dk, void* dv, const int64_t* dqkv_stride,
+                                   const int64_t* dout_stride, float* dtrans_coeff, float* dtau, void* workspace,
+                                   int64_t workspace_bytes, void* stream) {
+    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, true, key_lens, nullptr, true, key_idx, false, nullptr, kv_images,
+                    dq, dk, dv, dqkv_stride, dout_stride, dtrans_coeff, dtau, workspace, workspace_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

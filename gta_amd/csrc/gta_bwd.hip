@@ -193,6 +193,22 @@ GTA_DEV void store_zero_rows(char* g, long row_stride_bytes, int t0, int t_end, 
     }
 }
 
+// GATHER (gta_attn_bwd_gather; VARLEN plus a gather): the token a compacted key position stands for, clamped into [0, Tk) as the K/V pre-pass
+// clamps it -- no value moves a load or a store out of the scene's rows.  idx: the scene's row of key_idx, pos < Tk
+GTA_DEV int tok_of(const int32_t* idx, int pos, int Tk) {
+    const int t = idx[pos];
+    return t < 0 ? 0 : t >= Tk ? Tk - 1 : t;
+}
+// store_zero_rows for compacted positions [pos0, pos_end) (at most 128): the zeros go to the rows of the tokens the index names there
+template <int ESZ>
+GTA_DEV void store_zero_rows_idx(char* g, long row_stride_bytes, const int32_t* idx, int Tk, int pos0, int pos_end, int ch_real, int tid) {
+    const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int i = tid; i < 128 * ch_real; i += 256) {
+        const int r = i / ch_real, c = i - r * ch_real;
+        if (pos0 + r < pos_end) g_store_chunk<ESZ>(g + (long)tok_of(idx, pos0 + r, Tk) * row_stride_bytes, c, z);
+    }
+}
+
 // ================================================================================================
 // 1. q-side pre-pass
 // ================================================================================================
@@ -741,8 +757,17 @@ struct DkvSmem {
 
 // VARLEN: a block of 128 keys wholly past the scene's prefix reads no image (those workspace tiles were never written) and stores zeros; a block
 // that straddles it holds ceil((Tk_b - k0) / 64) tiles and stores zeros for its keys past the prefix; the Q''/dO~ walk ends at ceil(Tq_b / 64) tiles.
-template <int DHP, int ESZ, bool VARLEN = false>
-GTA_DEV void bwd_dkv_body(const GtaBwdParams& p, char* smem, const int L, const int nwg, const int32_t* key_lens = nullptr, const int32_t* q_lens = nullptr) {
+// GATHER (with VARLEN; key_idx [B, Tk]): the images are those of the GATHER pre-pass -- row pos of the scene's images is token key_idx[b, pos],
+// key_lens[b] counts the compacted keys -- and the walk is the VARLEN walk as it is.  What follows the token instead of the position: the view
+// record (a compacted block holds tokens of any view, so the records of all Nk views are staged; those of views no valid token belongs to
+// are staged and never selected), the cs_k row, the raw K / V row of the d trans_coeff term and the destination row of dk / dv.  Positions at
+// or past the count store zeros at the tokens the index names there and load nothing of them: with every row of key_idx a permutation of
+// [0, Tk) (the valid tokens, then the masked ones: key_index_tensors) each row of dk and dv is written exactly once.  A row that is not a
+// permutation leaves the gradient rows of the tokens it does not name unwritten; the clamp keeps every store inside the scene's rows.
+template <int DHP, int ESZ, bool VARLEN = false, bool GATHER = false>
+GTA_DEV void bwd_dkv_body(const GtaBwdParams& p, char* smem, const int L, const int nwg, const int32_t* key_lens = nullptr, const int32_t* q_lens = nullptr,
+                          const int32_t* key_idx = nullptr) {
+    static_assert(!GATHER || VARLEN, "the gather compacts into a per-scene prefix");
     using S = DkvSmem<DHP>;
     constexpr int CHP = S::CHP, KS = DHP / 16, DB = DHP / 32, BK = 128;
     constexpr int DMA_PER_WAVE = S::STAGE / 1024 / 4;
@@ -769,8 +794,14 @@ GTA_DEV void bwd_dkv_body(const GtaBwdParams& p, char* smem, const int L, const 
         tq_b = len_of(q_lens, b, p.Tq);
         if (k0 >= tk_b) {                                 // a block wholly past the key prefix (workgroup-uniform): zeros, before any DMA or barrier
             const int t_end = k0 + BK < p.Tk ? k0 + BK : p.Tk;
-            store_zero_rows<ESZ>((char*)p.dk + ((long)b * p.dk_sb + (long)h * p.dk_sh) * ESZ, p.dk_st * ESZ, k0, t_end, ch_real, tid);
-            store_zero_rows<ESZ>((char*)p.dv + ((long)b * p.dv_sb + (long)h * p.dv_sh) * ESZ, p.dv_st * ESZ, k0, t_end, ch_real, tid);
+            if constexpr (GATHER) {                       // (the rows of the masked tokens these positions name)
+                const int32_t* idx = key_idx + (long)b * p.Tk;
+                store_zero_rows_idx<ESZ>((char*)p.dk + ((long)b * p.dk_sb + (long)h * p.dk_sh) * ESZ, p.dk_st * ESZ, idx, p.Tk, k0, t_end, ch_real, tid);
+                store_zero_rows_idx<ESZ>((char*)p.dv + ((long)b * p.dv_sb + (long)h * p.dv_sh) * ESZ, p.dv_st * ESZ, idx, p.Tk, k0, t_end, ch_real, tid);
+            } else {
+                store_zero_rows<ESZ>((char*)p.dk + ((long)b * p.dk_sb + (long)h * p.dk_sh) * ESZ, p.dk_st * ESZ, k0, t_end, ch_real, tid);
+                store_zero_rows<ESZ>((char*)p.dv + ((long)b * p.dv_sb + (long)h * p.dv_sh) * ESZ, p.dv_st * ESZ, k0, t_end, ch_real, tid);
+            }
             if (tid == 0) p.dc_partial[p.dc_off_dkv + w] = 0.f;
             return;
         }
@@ -793,8 +824,8 @@ GTA_DEV void bwd_dkv_body(const GtaBwdParams& p, char* smem, const int L, const 
     dma_stats(stats, gstats, wave, lane);
 
     const int t_last = (k0 + BK - 1 < GTA_TK ? k0 + BK - 1 : GTA_TK - 1);
-    const int n_first = k0 / p.Pk;
-    const int n_cnt = t_last / p.Pk - n_first + 1;
+    const int n_first = GATHER ? 0 : k0 / p.Pk;          // (GATHER: every view's record, see above)
+    const int n_cnt = GATHER ? p.Nk : t_last / p.Pk - n_first + 1;
     const float tc = p.trans_coeff ? *p.trans_coeff : 1.0f;
     if (p.vrep_k) stage_brec(rec, p.vrep_k, (long)b * p.Nk + n_first, n_cnt, 1, tc, tid, 256);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -959,6 +990,12 @@ GTA_DEV void bwd_dkv_body(const GtaBwdParams& p, char* smem, const int L, const 
     char* dvg = (char*)p.dv + ((long)b * p.dv_sb + (long)h * p.dv_sh) * ESZ;
     float* ost = reinterpret_cast<float*>(smem + S::OFF_RING);
     float dcpart = 0.f;
+    // (GATHER) the token of this thread's row, read once: item = wave + 4 it below, so every item of a thread is row lane + 64 (wave & 1)
+    int tok_g = 0;
+    if constexpr (GATHER) {
+        const int pos = k0 + lane + 64 * (wave & 1);
+        if (pos < p.Tk) tok_g = tok_of(key_idx + (long)b * p.Tk, pos, p.Tk);
+    }
 #pragma unroll 1
     for (int which = 0; which < 2; ++which) {            // 0: dK, 1: dV
         __syncthreads();
@@ -985,10 +1022,11 @@ GTA_DEV void bwd_dkv_body(const GtaBwdParams& p, char* smem, const int L, const 
             const int item = wave + 4 * it;
             const int c = item >> 1;
             const int r = lane + 64 * (item & 1);
-            const int t = k0 + r;
+            const int t = k0 + r;                                   // the key's position in the images ...
+            const int tok = GATHER ? tok_g : t;                     // ... and its token (GATHER: the one the index names at that position)
             if (VARLEN && c < ch_real && t >= tk_b && t < p.Tk) {   // a key past the prefix: zeros, nothing of the key is read
                 const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                g_store_chunk<ESZ>(outg + (long)t * out_st, c, z);
+                g_store_chunk<ESZ>(outg + (long)tok * out_st, c, z);
             } else if (c < ch_real && t < GTA_TK) {
                 const uint32_t desc = p.ctab[c];
                 float x[1][8];
@@ -997,20 +1035,20 @@ GTA_DEV void bwd_dkv_body(const GtaBwdParams& p, char* smem, const int L, const 
                 x[0][0] = a.x; x[0][1] = a.y; x[0][2] = a.z; x[0][3] = a.w;
                 x[0][4] = bb.x; x[0][5] = bb.y; x[0][6] = bb.z; x[0][7] = bb.w;
                 if (desc && xf) {
-                    const int n = view_of(t, p.Pk, p.invPk) - n_first;
+                    const int n = view_of(tok, p.Pk, p.invPk) - n_first;
                     const float* rc = rec + n * BREC;
                     if (!(desc & GTA_CHUNK_SO3) && (cd_lo(desc) == GTA_HALF_SE3 || cd_hi(desc) == GTA_HALF_SE3)) {
                         float r8[8];
-                        g_load_chunk<ESZ>(rawg + (long)t * raw_st, c, r8);
+                        g_load_chunk<ESZ>(rawg + (long)tok * raw_st, c, r8);
                         const float t0 = rc[BREC_T], t1 = rc[BREC_T + 1], t2 = rc[BREC_T + 2];
                         if (cd_lo(desc) == GTA_HALF_SE3) dcpart += (x[0][0] * t0 + x[0][1] * t1 + x[0][2] * t2) * r8[3];
                         if (cd_hi(desc) == GTA_HALF_SE3) dcpart += (x[0][4] * t0 + x[0][5] * t1 + x[0][6] * t2) * r8[7];
                     }
                     f32x2_t cs[4];
-                    if (p.cs_k) load_cs(desc, p.cs_k + ((long)b * p.Tk + t) * 2 * p.nso2, cs);
+                    if (p.cs_k) load_cs(desc, p.cs_k + ((long)b * p.Tk + tok) * 2 * p.nso2, cs);
                     chunk_apply<true, 1>(desc, rc + BREC_MT, rc + BREC_D1T, rc + BREC_D2T, cs, x);
                 }
-                g_store_chunk<ESZ>(outg + (long)t * out_st, c, x[0]);
+                g_store_chunk<ESZ>(outg + (long)tok * out_st, c, x[0]);
             }
         }
     }
@@ -1044,6 +1082,14 @@ template <int DHP, int ESZ>
 __global__ __launch_bounds__(256, (DHP > 96 ? 1 : 2)) void gta_bwd_dkv_varlen_kernel(const GtaBwdParams p, const int32_t* key_lens, const int32_t* q_lens) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     bwd_dkv_body<DHP, ESZ, true>(p, smem, blockIdx.x, gridDim.x, key_lens, q_lens);
+}
+// the GATHER instances of the dK/dV walk (gta_attn_bwd_gather): key_idx [B, Tk] beside the lengths.  That entry's dQ walk and q-side pre-pass are
+// the VARLEN ones above -- nothing on the query side knows about the gather
+template <int DHP, int ESZ>
+__global__ __launch_bounds__(256, (DHP > 96 ? 1 : 2)) void gta_bwd_dkv_gather_kernel(const GtaBwdParams p, const int32_t* key_lens, const int32_t* q_lens,
+                                                                                      const int32_t* key_idx) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    bwd_dkv_body<DHP, ESZ, true, true>(p, smem, blockIdx.x, gridDim.x, key_lens, q_lens, key_idx);
 }
 template <int DHP, int ESZ>
 __global__ __launch_bounds__(256, (DHP > 96 ? 1 : 2)) void gta_bwd_dqkv_kernel(const GtaBwdParams p, const int n_dq) {
@@ -2064,7 +2110,45 @@ int run_bwd_varlen(const GtaBwdParams& p, const int32_t* key_lens, const int32_t
     return hipGetLastError() == hipSuccess ? GTA_OK : GTA_E_LAUNCH;
 }
 
+// gta_attn_bwd_gather: run_bwd_varlen with the GATHER instance of the dK/dV walk -- three launches, never the generated streams.  The query side
+// has no lengths of its own here (q_lens = NULL: every query row is live)
+template <int DHP, int ESZ>
+int run_bwd_gather(const GtaBwdParams& p, const int32_t* key_idx, const int32_t* key_lens, hipStream_t stream) {
+    const int n_qt = (p.Tq + BN - 1) / BN;
+    const int32_t* q_lens = nullptr;
+    if (int rc = gta_lds_optin<&gta_bwd_prep_kernel<DHP, ESZ, false, true, const int32_t*>>(BPrepSmem<DHP, ESZ>::total(GTA_MAX_VIEWS))) return rc;
+    if (int rc = gta_lds_optin<&gta_bwd_dq_varlen_kernel<DHP, ESZ>>(DqSmem<DHP>::total(GTA_MAX_VIEWS))) return rc;
+    if (int rc = gta_lds_optin<&gta_bwd_dkv_gather_kernel<DHP, ESZ>>(DkvSmem<DHP>::total(GTA_MAX_VIEWS))) return rc;
+    const long prep_grid = ((long)p.B * n_qt + 7) / 8 * 8 * p.H;
+    const long n_dq = (long)p.B * p.H * ((p.Tq + 127) / 128), n_dkv = (long)p.B * p.H * ((p.Tk + 127) / 128);
+    if (prep_grid > 0x7fffffffL || n_dq > 0x7fffffffL || n_dkv > 0x7fffffffL) return GTA_E_UNSUPPORTED;
+    const int lds_prep = BPrepSmem<DHP, ESZ>::total(p.vrep_q ? p.Nq : 0);
+    const int lds_dq = DqSmem<DHP>::total(p.vrep_q ? p.Nq : 0), lds_dkv = DkvSmem<DHP>::total(p.vrep_k ? p.Nk : 0);
+    hipLaunchKernelGGL((gta_bwd_prep_kernel<DHP, ESZ, false, true, const int32_t*>), dim3((unsigned)prep_grid), dim3(256), lds_prep, stream, p, q_lens);
+    hipLaunchKernelGGL((gta_bwd_dq_varlen_kernel<DHP, ESZ>), dim3((unsigned)n_dq), dim3(256), lds_dq, stream, p, key_lens, q_lens);
+    hipLaunchKernelGGL((gta_bwd_dkv_gather_kernel<DHP, ESZ>), dim3((unsigned)n_dkv), dim3(256), lds_dkv, stream, p, key_lens, q_lens, key_idx);
+    if (p.dtrans_coeff)
+        hipLaunchKernelGGL(gta_reduce_kernel, dim3(1), dim3(1024), 0, stream, p.dc_partial, p.dc_total, p.dtrans_coeff, (const float*)nullptr);
+    if (p.dtau)
+        hipLaunchKernelGGL(gta_reduce_kernel, dim3(1), dim3(1024), 0, stream, p.dt_partial, (int)n_dq, p.dtau, p.tau);
+    return hipGetLastError() == hipSuccess ? GTA_OK : GTA_E_LAUNCH;
+}
+
 }  // namespace
+
+int gta_bwd_gather_dispatch(const GtaBwdParams& p, const int32_t* key_idx, const int32_t* key_lens, int dhp, int esz, hipStream_t stream) {
+    if (!key_idx || !key_lens) return GTA_E_BADARG;
+    if (p.flags & GTA_FLAG_FP32_PRODUCTS) return GTA_E_UNSUPPORTED;
+#define GTA_CASEB(D) case D: return esz == 2 ? run_bwd_gather<D, 2>(p, key_idx, key_lens, stream) : run_bwd_gather<D, 4>(p, key_idx, key_lens, stream);
+    switch (dhp) {
+        GTA_CASEB(32)
+        GTA_CASEB(64)
+        GTA_CASEB(96)
+        GTA_CASEB(128)
+    }
+#undef GTA_CASEB
+    return GTA_E_UNSUPPORTED;
+}
 
 int gta_bwd_varlen_dispatch(const GtaBwdParams& p, const int32_t* key_lens, const int32_t* q_lens, int dhp, int esz, hipStream_t stream) {
     if (!key_lens || (p.flags & GTA_FLAG_FP32_PRODUCTS)) return GTA_E_UNSUPPORTED;

@@ -611,9 +611,10 @@ def key_lens_tensor(key_views: Tuple[int, ...], Pk: int, device) -> torch.Tensor
     return torch.tensor([n * Pk for n in key_views], dtype=torch.int32).to(device, non_blocking=True)
 
 
-def _key_mask_refusals(*, needs_grad=False, precise=False, pretransformed=False, kv_mode="auto"):
-    """what a call with ``key_mask`` cannot be combined with: said here, before anything is launched"""
-    if needs_grad:
+def _key_mask_refusals(*, needs_grad=False, precise=False, pretransformed=False, kv_mode="auto", key_mask_backward=False):
+    """what a call with ``key_mask`` cannot be combined with: said here, before anything is launched.  ``key_mask_backward`` opts in to the
+    backward (``gta_attn_bwd_gather``); without it a call under grad is refused as before."""
+    if needs_grad and not key_mask_backward:
         raise native.GtaError("key_mask is forward-only (no backward through the gathered keys yet): call under torch.no_grad()")
     if precise:
         raise native.GtaError("key_mask has no precise=True (fp32-faithful) instances")
@@ -734,6 +735,32 @@ def _gather_forward(q, k, v, cfg, tables, trans_coeff, tau, key_mask, kv_cache=N
     return c, ws
 
 
+class _GatherAttn(torch.autograd.Function):
+    """The fused layouts with a key mask under grad (``key_mask_backward=True``): the forward of ``_gather_forward``, whose workspace (the compacted
+    K'/V' tile images) and LSE serve ``gta_attn_bwd_gather`` under the same ``key_idx`` / ``key_lens`` (``key_index_tensors``: every row a
+    permutation, the valid tokens first).  Gradients: q, k, v, trans_coeff, tau -- as ``_GtaAttn``; dk / dv rows of masked tokens are zeros.  No
+    query-side mask, and no gradients of the tables (refused before the call gets here)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, trans_coeff, tau, cfg, key_idx, key_lens, vrep_q, vrep_k, cs_q, cs_k):
+        c, ws = _gather_forward(q, k, v, cfg, dict(vrep_q=vrep_q, vrep_k=vrep_k, cs_q=cs_q, cs_k=cs_k), trans_coeff, tau, None,
+                                key_idx=key_idx, key_lens=key_lens)
+        ctx.cfg = cfg
+        ctx.kv_images = ws
+        ctx.save_for_backward(c.q, c.k, c.v, c.out, c.lse, c.tc, c.ta, vrep_q, vrep_k, cs_q, cs_k, key_idx, key_lens)
+        ctx.tc_meta, ctx.tau_meta = _scalar_meta(trans_coeff), _scalar_meta(tau)
+        return c.out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from . import backward as _bw
+        q, k, v, out, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k, key_idx, key_lens = ctx.saved_tensors
+        want_dtau = ta is not None and ctx.needs_input_grad[4]
+        dq, dk, dv, dtc, dta = _bw.attn_bwd(ctx.cfg, q, k, v, out, dout, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k,
+                                            kv_images=ctx.kv_images, want_dtau=want_dtau, key_idx=key_idx, key_lens=key_lens)
+        return (dq, dk, dv, _restore_scalar(dtc, ctx.tc_meta), _restore_scalar(dta, ctx.tau_meta)) + (None,) * 7
+
+
 class _VarlenAttn(torch.autograd.Function):
     """The fused layouts with per-scene key prefixes under grad (``key_views_backward=True``): the forward of ``_varlen_forward``, whose workspace
     (the masked K'/V' tile images) and LSE serve ``gta_attn_bwd_varlen``.  ``q_lens`` (or None) masks padded query rows in the backward only.
@@ -801,7 +828,7 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
                   euclid: bool = False, pretransformed: bool = False, use_dma: bool = True,
                   kv_mode: str = "auto", kv_cache: Optional[dict] = None, precise: Optional[bool] = None,
                   key_views=None, key_lens: Optional[torch.Tensor] = None, key_views_backward: bool = False,
-                  query_views=None, return_lse: bool = False, key_mask: Optional[torch.Tensor] = None):
+                  query_views=None, return_lse: bool = False, key_mask: Optional[torch.Tensor] = None, key_mask_backward: bool = False):
     """Fused GTA attention on packed reps.  q [B,H,Tq,dh], k/v [B,H,Tk,dh] -> out [B,H,Tq,dh].
 
     kv_mode: 'prepass' = K/V rep pre-pass + lean attention kernel (two launches; at dh = 96 in the MSN layout the attention kernel is
@@ -849,10 +876,22 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
              masked tiles are skipped, not computed.  A CPU mask is validated (every scene needs a valid key); a CUDA mask is used without
              a sync, and a scene of it with no valid key attends its token 0.  In self-attention the output rows of masked tokens are
              computed like any other.  With ``kv_cache`` later calls must pass ``key_mask`` again (it is not looked at: they run on the
-             indices and lengths the first call stored).  Forward only, default arithmetic, two-stage plan, fused layouts; refused by name:
-             a call under grad, precise=True, pretransformed, kv_mode='fused', ``key_views`` beside it, and the staged and rho-apply
-             layouts (t2, euclid, so3 of degree 1, unaligned slabs), which have no gather pre-pass.
+             indices and lengths the first call stored).  Forward only unless ``key_mask_backward=True``; default arithmetic, two-stage plan,
+             fused layouts; refused by name: a call under grad without ``key_mask_backward``, precise=True, pretransformed, kv_mode='fused',
+             ``key_views`` beside it, and the staged and rho-apply layouts (t2, euclid, so3 of degree 1, unaligned slabs), which have no gather
+             pre-pass.
+    key_mask_backward: only with ``key_mask``.  False (default): a call with ``key_mask`` under grad raises "forward-only", as it always did.
+             True: the call is differentiable in q, k, v, trans_coeff and tau (``gta_attn_fwd_gather`` + ``gta_attn_bwd_gather``; the forward's
+             compacted images serve the backward).  dk / dv rows of masked tokens are exactly zero, and nothing of a masked KEY row -- k, v, cs_k,
+             the vrep_k record of a wholly masked view -- is read: it may hold anything, NaN and Inf included.  There is NO query-side mask: in
+             self-attention the masked tokens are query rows too, computed as in the forward, and they take part in the backward with whatever
+             ``dout`` they get -- so masked QUERY rows (q, cs_q, and the dout that reaches them) must hold finite values; a zero ``dout`` row then
+             adds exact zeros to dk / dv.  Still refused, by name: rep tables or poses that require grad (no pose / coordinate gradients under a
+             key mask yet), return_lse under grad, kv_cache under grad, precise=True, pretransformed, kv_mode='fused', and the staged and
+             rho-apply layouts.
     """
+    if key_mask_backward and key_mask is None:
+        raise native.GtaError("key_mask_backward=True comes with key_mask")
     if key_mask is not None and (key_views is not None or key_lens is not None or key_views_backward or query_views is not None):
         raise native.GtaError("key_mask with key_views (or its companions): a call takes one key mask -- a prefix of views is a mask too")
     if query_views is not None and not key_views_backward:
@@ -894,10 +933,20 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
                key_views_backward=bool(key_views_backward))
     if key_mask is not None:
         check_key_mask(key_mask, q.shape[0], k.shape[2])
+        if key_mask_backward and needs_grad:
+            if carriers:
+                raise native.GtaError("key_mask_backward: no pose / coordinate gradients under a key mask yet (gta_rep_grad_sums_varlen knows "
+                                      "prefixes only): detach the rep tables and poses")
+            if return_lse:
+                raise native.GtaError("return_lse under grad with key_mask_backward: gta_attn_bwd_gather takes no gradient of the log-sum-exp "
+                                      "(drop return_lse, or call under torch.no_grad())")
         flags = attention_route(tuple(q.shape), k.shape[2], q.dtype, f_dims, so3_degree, Nq, Nk, pretransformed=pretransformed, use_dma=use_dma,
                                 kv_mode=kv_mode, kv_cache=kv_cache is not None, v_transform=v_transform, euclid=euclid, precise=bool(precise),
-                                needs_grad=needs_grad, key_mask=True)
+                                needs_grad=needs_grad, key_mask=True, key_mask_backward=bool(key_mask_backward))
         cfg = ({k_: int(v_) for k_, v_ in f_dims.items()}, int(so3_degree), Nq, Nk, float(scale), flags)
+        if needs_grad:          # (key_mask_backward: anything else was refused above)
+            key_idx, key_lens_m = key_index_tensors(key_mask, q.device)
+            return _GatherAttn.apply(q, k, v, trans_coeff, tau, cfg, key_idx, key_lens_m, *(packed.get(t) for t in ("vrep_q", "vrep_k", "cs_q", "cs_k")))
         c = _gather_forward(q, k, v, cfg, packed, trans_coeff, tau, key_mask, kv_cache)[0]
         return (c.out, c.lse) if return_lse else c.out
     flags = attention_route(tuple(q.shape), k.shape[2], q.dtype, f_dims, so3_degree, Nq, Nk, pretransformed=pretransformed, use_dma=use_dma,
@@ -1043,7 +1092,7 @@ KV_MODES = {
 def attention_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree: int, Nq: int, Nk: int, *, v_transform: bool = True,
                     euclid: bool = False, pretransformed: bool = False, use_dma: bool = True, kv_mode: str = "auto",
                     kv_cache: bool = False, precise: bool = False, needs_grad: bool = False, key_views: bool = False,
-                    key_views_backward: bool = False, key_mask: bool = False) -> Optional[int]:
+                    key_views_backward: bool = False, key_mask: bool = False, key_mask_backward: bool = False) -> Optional[int]:
     """How ``gta_attention`` runs a call: the descriptor flags of the fused path, or None for the generic one (rho-apply kernels around the
     plain attention kernel).  q_shape = (B, H, Tq, dh); Tk keys; dtype of q.
 
@@ -1056,7 +1105,8 @@ def attention_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree:
     serve ``gta_attn_bwd_varlen``.
 
     key_mask=True (the call comes with a key mask): the flags of ``gta_attn_fwd_gather`` -- the two-stage plan --, never None: the layouts
-    without a fused kernel have no gather pre-pass and raise ``GtaError`` like every other combination without one."""
+    without a fused kernel have no gather pre-pass and raise ``GtaError`` like every other combination without one.  key_mask_backward=True
+    lets needs_grad through: the same flags serve ``gta_attn_bwd_gather``."""
     if kv_mode not in KV_MODES:
         raise ValueError(f"kv_mode {kv_mode!r}")
     flags = KV_MODES[kv_mode] | _layout_flags(v_transform, euclid) | (0 if use_dma else native.FLAG_NO_DMA)
@@ -1064,7 +1114,8 @@ def attention_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree:
     if key_mask:
         if key_views:
             raise native.GtaError("key_mask with key_views: a call takes one key mask")
-        _key_mask_refusals(needs_grad=needs_grad, precise=precise, pretransformed=pretransformed, kv_mode=kv_mode)
+        _key_mask_refusals(needs_grad=needs_grad, precise=precise, pretransformed=pretransformed, kv_mode=kv_mode,
+                           key_mask_backward=key_mask_backward)
         rc = native.attn_fwd_supported(probe(flags))
         if rc == native.E_UNSUPPORTED:
             raise native.GtaError("key_mask: the staged and rho-apply layouts (t2, euclid, so3 of degree 1, unaligned slabs) have no gather "

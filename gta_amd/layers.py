@@ -181,6 +181,7 @@ class Attention(nn.Module):
             raise _gta.native.GtaError("key_mask with return_attmap: the dense attention map has no key mask")
         # (training on such batches) the opt-in backward, and the valid query views of a self-attention layer -- both absent by default
         kvb = bool(extras.get("key_views_backward")) if extras is not None else False
+        kmb = bool(extras.get("key_mask_backward")) if extras is not None else False
         query_views = extras.get("query_views") if extras is not None else None
         packed = _gta.pack_reps(extras, self.f_dims)
         out = _gta.gta_attention(
@@ -190,7 +191,8 @@ class Attention(nn.Module):
             scale=self.scale, v_transform=self.method_args.get("v_transform", True), euclid=self.euclid,
             kv_cache=kv_cache, precise=self.precise and q.dtype == torch.float32 and kv_cache is None,
             **({"key_views": key_views} if key_views is not None else {}), **({"key_mask": key_mask} if key_mask is not None else {}),
-            **({"key_views_backward": True} if kvb else {}), **({"query_views": query_views} if query_views is not None else {}))
+            **({"key_views_backward": True} if kvb else {}), **({"query_views": query_views} if query_views is not None else {}),
+            **({"key_mask_backward": True} if kmb else {}))
         out = out.permute(0, 2, 1, 3).reshape(B, Tq, H * dh)              # free: out is [B,Tq,H,dh] in memory
         attn = None
         if return_attmap:                                                  # layers.py:441-442

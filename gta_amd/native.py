@@ -52,6 +52,7 @@ ABI_SYMBOLS = (
     "gta_attn_bwd_varlen", "gta_attn_bwd_varlen_supported",
     "gta_attn_bwd_dlse", "gta_attn_bwd_dlse_supported", "gta_attn_merge", "gta_attn_merge_bwd",
     "gta_attn_fwd_gather", "gta_attn_fwd_gather_supported",
+    "gta_attn_bwd_gather", "gta_attn_bwd_gather_supported",
 )
 MERGE_MAX = 8           # partial attentions per gta_attn_merge call
 
@@ -150,6 +151,10 @@ def lib():
         L.gta_attn_bwd_varlen.argtypes = ([ctypes.POINTER(GtaAttnDesc)] + [c_void_p] * 18
                                           + [ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_int64, c_void_p])
         L.gta_attn_bwd_varlen_supported.argtypes = [ctypes.POINTER(GtaAttnDesc)]
+        # gta_attn_bwd_varlen with key_idx ([B, Tk] int32, device) in front of key_lens and no q_lens
+        L.gta_attn_bwd_gather.argtypes = ([ctypes.POINTER(GtaAttnDesc)] + [c_void_p] * 18
+                                          + [ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_int64, c_void_p])
+        L.gta_attn_bwd_gather_supported.argtypes = [ctypes.POINTER(GtaAttnDesc)]
         # gta_attn_bwd with dlse ([B,H,Tq] fp32, device) behind lse
         L.gta_attn_bwd_dlse.argtypes = ([ctypes.POINTER(GtaAttnDesc)] + [c_void_p] * 17
                                         + [ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_int64, c_void_p])
@@ -444,10 +449,15 @@ def attn_bwd_workspace_bytes(desc: GtaAttnDesc) -> int:
 
 
 def _bwd_call(entry: str, desc: GtaAttnDesc, q, k, v, out, dout, lse, tables, lens, kv_images, dq, dk, dv, dtrans_coeff, workspace, dtau, dlse=()):
-    """The backward entries: ``lens`` is () or (key_lens, q_lens) -- [B] int32 on the device, q_lens may be None; ``dlse`` is () or (dlse,)."""
+    """The backward entries: ``lens`` is () or (key_lens, q_lens) -- [B] int32 on the device, q_lens may be None --, for gta_attn_bwd_gather
+    (key_idx, key_lens) -- key_idx [B, Tk] int32 on the device; ``dlse`` is () or (dlse,)."""
     _require_cuda(q, k, v, out, dout, dq, dk, dv, workspace, *lens, *dlse)
-    for t in lens[:1] + tuple(t for t in lens[1:] if t is not None):
-        _check_key_lens(t, desc.B, workspace.device)
+    if entry.endswith("_gather"):
+        _check_key_idx(lens[0], desc.B, desc.Tk, workspace.device)
+        _check_key_lens(lens[1], desc.B, workspace.device)
+    else:
+        for t in lens[:1] + tuple(t for t in lens[1:] if t is not None):
+            _check_key_lens(t, desc.B, workspace.device)
     check(getattr(lib(), entry)(ctypes.byref(desc), *map(_ptr, (q, k, v, out, dout, lse)), *map(_ptr, dlse), *map(_ptr, tables), *map(_ptr, lens),
                                 _ptr(kv_images), _ptr(dq), _ptr(dk), _ptr(dv), _strides(dq, dk, dv), _strides(dout),
                                 _ptr(dtrans_coeff), _ptr(dtau), _ptr(workspace), workspace.numel(), _stream()), entry)
@@ -525,6 +535,20 @@ def attn_bwd_varlen(desc: GtaAttnDesc, q, k, v, out, dout, lse, vrep_q, vrep_k, 
     """``attn_bwd`` with scene b's keys cut to key_lens[b] tokens and (q_lens, or None) its query rows to q_lens[b]: [B] int32 on the device.
     kv_images: the workspace of ``attn_fwd_varlen`` under the same key_lens, or None."""
     _bwd_call("gta_attn_bwd_varlen", desc, q, k, v, out, dout, lse, (vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau), (key_lens, q_lens),
+              kv_images, dq, dk, dv, dtrans_coeff, workspace, dtau)
+
+
+def attn_bwd_gather_supported(desc: GtaAttnDesc) -> int:
+    """0 when gta_attn_bwd_gather (the backward over any per-scene subset of the key tokens) serves desc, else a GTA_E_* code; needs no GPU"""
+    return lib().gta_attn_bwd_gather_supported(ctypes.byref(desc))
+
+
+def attn_bwd_gather(desc: GtaAttnDesc, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, key_idx, key_lens, kv_images,
+                    dq, dk, dv, dtrans_coeff, workspace, dtau=None):
+    """``attn_bwd_varlen`` (no q_lens) for the keys of ``attn_fwd_gather``: key_idx [B, Tk] int32 on the device, every row a permutation of
+    [0, Tk) with the key_lens[b] valid tokens first (``gta.key_index_tensors``) -- dk / dv of the valid tokens land in their rows, the rows of
+    the masked tokens are written as zeros.  kv_images: the workspace of ``attn_fwd_gather`` under the same key_idx / key_lens, or None."""
+    _bwd_call("gta_attn_bwd_gather", desc, q, k, v, out, dout, lse, (vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau), (key_idx, key_lens),
               kv_images, dq, dk, dv, dtrans_coeff, workspace, dtau)
 
 

@@ -173,7 +173,7 @@ class TransformingSRT(nn.Module):
         return self.decoder(z, x, rays, extras)
 
     def forward(self, input_images, input_camera_pos, input_rays, target_camera_pos, target_rays, extras=None, input_views=None,
-                input_views_backward=False, input_mask=None):
+                input_views_backward=False, input_mask=None, input_mask_backward=False):
         """``input_views``: per-scene numbers of valid input views (a host sequence of length B, each in 1..N) for batches that mix
         view counts: scene b's first ``input_views[b]`` views are its input, the rest of its [N, ...] slots is padding that no valid
         token ever attends to -- in the encoder's self-attention and in the decoder's cross-attention (``gta_attention``'s
@@ -186,13 +186,21 @@ class TransformingSRT(nn.Module):
         ``input_mask``: a bool [B, N, P] or [B, N * P] tensor over the scene tokens (N views of P patches; True: a valid token) -- any
         subset: smaller views padded inside their slots, a missing view that is not the last, patches to ignore.  No token attends to a
         masked one, in the encoder's self-attention and in the decoder's cross-attention (``gta_attention``'s ``key_mask``); the scene
-        tokens of masked positions are still computed and unspecified.  Inference only; not together with ``input_views``."""
+        tokens of masked positions are still computed and unspecified.  Not together with ``input_views``.  Inference only unless
+        ``input_mask_backward=True``: every layer then runs the differentiable route (``key_mask_backward``; fused layouts, no pose or
+        coordinate gradients).  There is no query-side mask: in the encoder's self-attention the masked tokens are query rows too and take
+        part in the backward, so the inputs at masked positions must be finite (zero-filled padding is); nothing of a masked token reaches
+        a valid one as a KEY."""
         extras = {} if extras is None else extras
+        if input_mask_backward and input_mask is None:
+            raise native.GtaError("input_mask_backward=True comes with input_mask")
         if input_mask is not None:
             if input_views is not None:
                 raise native.GtaError("input_mask with input_views: a call takes one key mask -- a prefix of views is a mask too")
             extras = dict(extras)
             extras["key_mask"] = _token_mask(input_mask)
+            if input_mask_backward:
+                extras["key_mask_backward"] = True
         if input_views is not None:
             extras = dict(extras)                      # the caller's dict never carries these counts into a later call (as render_image)
             extras["key_views"] = input_views

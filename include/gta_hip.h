@@ -214,6 +214,38 @@ int gta_attn_bwd_varlen(const GtaAttnDesc* desc,
                         float* dtrans_coeff, float* dtau,
                         void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Backward over any per-scene subset of the key tokens (gta_attention's key_mask with key_mask_backward): the backward of
+ * gta_attn_fwd_gather.  It is gta_attn_bwd_varlen without q_lens (there is no query-side mask: every query row is live and must hold finite
+ * values) whose dK/dV walk runs in GATHER instances: the walk over the compacted K'/V' images is the VARLEN walk, and the epilogue reads the
+ * token of a compacted row from key_idx -- that token gives the view record, the cs_k row, the raw K / V row of the dtrans_coeff term and the
+ * row of dk / dv that is written.  The dQ walk and the q-side pre-pass are the VARLEN kernels as they are.
+ *   key_idx:  [B, Tk] int32 on the device; NULL: GTA_E_BADARG, with kv_images too (the scatter reads it).  For THIS entry every row must be a
+ *       permutation of [0, Tk): the key_lens[b] valid tokens first, then the masked ones (what the Python layer's key_index_tensors builds).
+ *       Positions at or past key_lens[b] are read here: dk / dv rows of the tokens they name are written as zeros, and nothing of those
+ *       tokens (k, v, cs_k) is loaded.  Then every row of dk and dv is written exactly once.  A row that is not a permutation leaves the
+ *       gradient rows of the tokens it does not name unwritten; values are clamped into [0, Tk) as in the forward, so no value moves a load
+ *       or a store out of the scene's rows.  (The forward entry's contract -- entries at or past key_lens[b] are never read -- is unchanged.)
+ *   key_lens: as in gta_attn_fwd_gather; NULL: GTA_E_BADARG.
+ *   kv_images: the workspace of a gta_attn_fwd_gather call under the same key_idx / key_lens, or NULL -> rebuilt here by the GATHER pre-pass.
+ *   vrep_k records of views no valid token belongs to are loaded with the others and enter no result (they may hold NaN).
+ *   Kernels: three launches for bf16 and fp32 inputs at every head size; the generated 64-row streams are never selected, and
+ *       GTA_FLAG_FP32_PRODUCTS is refused.  Under a mask of whole leading views every output is bit for bit that of gta_attn_bwd_varlen
+ *       with the same key_lens and q_lens = NULL.
+ *   gta_attn_bwd_gather_supported: what gta_attn_bwd_varlen_supported answers.
+ *   workspace: >= gta_attn_bwd_workspace_bytes(desc).  Every other argument, check and error code: as in gta_attn_bwd_varlen.  No gradients of
+ *       the reps / poses under a mask yet. */
+int gta_attn_bwd_gather_supported(const GtaAttnDesc* desc);
+int gta_attn_bwd_gather(const GtaAttnDesc* desc,
+                        const void* q, const void* k, const void* v, const void* out, const void* dout,
+                        const float* lse,
+                        const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
+                        const float* trans_coeff, const float* tau,
+                        const int32_t* key_idx, const int32_t* key_lens,
+                        const void* kv_images,
+                        void* dq, void* dk, void* dv, const int64_t* dqkv_stride, const int64_t* dout_stride,
+                        float* dtrans_coeff, float* dtau,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Backward of the PAIR (out, lse) (gta_attention's return_lse under grad): gta_attn_bwd with the gradient of the log-sum-exp.
  *   dlse: [B,H,Tq] fp32, contiguous, non-NULL (GTA_E_BADARG) -- d loss / d lse per query row, lse as the forward wrote it (natural log).
  *   The exact gradient of the logits is dS_ij = P_ij (dP_ij - D_i + dlse_i): the q-side pre-pass runs in instances that store -(D - dlse)

@@ -119,6 +119,18 @@ def audit_others():
             twin = bwd_scratch.get((kern + "_kernel", dhp, esz))
             if twin is None or row["scratch"] > twin:
                 problems.append(f"{row['kernel']} has {row['scratch']} scratch accesses, its twin without VARLEN {twin}")
+    # the GATHER instances of the dK/dV walk (gta_attn_bwd_gather) by the same rule against their VARLEN twins: eight of them, one per twin
+    varlen_scratch = {r["kernel"]: r["scratch"] for r in report if r["kernel"].startswith("gta_bwd_dkv_varlen_kernel<")}
+    n_gather = 0
+    for name, (dhp, esz), body, vgpr in _kernels(text, r"gta_bwd_dkv_gather_kernelILi(\d+)ELi(\d+)E"):
+        row = {"kernel": f"gta_bwd_dkv_gather_kernel<{dhp},{esz}>", "vgpr": vgpr, "scratch": body.count("scratch_")}
+        report.append(row)
+        n_gather += 1
+        twin = varlen_scratch.get(f"gta_bwd_dkv_varlen_kernel<{dhp},{esz}>")
+        if twin is None or row["scratch"] > twin:
+            problems.append(f"{row['kernel']} has {row['scratch']} scratch accesses, its VARLEN twin {twin}")
+    if n_gather != len(varlen_scratch):
+        problems.append(f"{n_gather} GATHER instances of the dK/dV walk for {len(varlen_scratch)} VARLEN ones")
     # the DLSE instances of the pre-pass (gta_attn_bwd_dlse) by the same rule against the twin without dlse, X3 ones against the X3 twin
     prep = {}
     for name, (dhp, esz, x3), body, vgpr in _kernels(text, r"gta_bwd_prep_kernelILi(\d+)ELi(\d+)ELb(\d)ELb0EJ"):
