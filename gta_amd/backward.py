@@ -38,13 +38,17 @@ def _grad_buffers(q, k, v):
 
 
 def attn_bwd(cfg, q, k, v, out, dout, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k, kv_images=None, want_dtau=False, key_lens=None, q_lens=None,
-             dlse=None, key_idx=None):
+             dlse=None, key_idx=None, q_live=None):
     """Returns (dq, dk, dv, dtrans_coeff or None, dtau or None); dtau ([1] fp32) only with ``want_dtau``.
     key_lens (with q_lens or None): ``gta_attn_bwd_varlen`` -- per-scene prefixes, kv_images those of ``attn_fwd_varlen`` under the same key_lens.
     key_idx (with key_lens, without q_lens): ``gta_attn_bwd_gather`` -- the keys of ``attn_fwd_gather``, kv_images those of that call under the same
     key_idx / key_lens; dk / dv rows of masked tokens are zeros.
+    q_live (with key_idx and key_lens; q_lens allowed): ``gta_attn_bwd_qmask`` -- the query-side mask of ``attn_fwd_qmask``; dq rows of dead rows
+    are zeros and nothing of them (q, out, dout, lse) is used.
     dlse ([B,H,Tq], the gradient of the forward's lse; not with key_lens): ``gta_attn_bwd_dlse`` -- the backward of the pair (out, lse)."""
-    if key_idx is not None and (key_lens is None or q_lens is not None):
+    if q_live is not None and (key_idx is None or key_lens is None):
+        raise native.GtaError("q_live comes with key_idx and key_lens (gta_attn_bwd_qmask runs on the key_mask route)")
+    if key_idx is not None and (key_lens is None or (q_lens is not None and q_live is None)):
         raise native.GtaError("key_idx comes with key_lens and without q_lens (gta_attn_bwd_gather has no query-side mask)")
     f_dims, so3_degree, Nq, Nk, scale, flags = cfg
     flags = flags & ~(native.FLAG_FUSED_KV | native.FLAG_KV_READY | native.FLAG_PREP_ONLY | native.FLAG_PERSIST)      # (GTA_FLAG_FP32_PRODUCTS stays: the X3 walks)
@@ -66,6 +70,9 @@ def attn_bwd(cfg, q, k, v, out, dout, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k, k
             raise native.GtaError("return_lse: gta_attn_bwd_varlen takes no gradient of the log-sum-exp")
         native.attn_bwd_dlse(desc, q, k, v, out, dout, lse, dlse.to(torch.float32).contiguous(), vrep_q, vrep_k, cs_q, cs_k, tc, ta, kv_images,
                              dq, dk, dv, dtc, ws, dta)
+    elif q_live is not None:
+        native.attn_bwd_qmask(desc, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, tc, ta, key_idx, key_lens, q_live, q_lens, kv_images,
+                              dq, dk, dv, dtc, ws, dta)
     elif key_idx is not None:
         native.attn_bwd_gather(desc, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, tc, ta, key_idx, key_lens, kv_images, dq, dk, dv, dtc, ws, dta)
     elif key_lens is not None:

@@ -29,6 +29,8 @@ int gta_merge_dispatch(const GtaMergeParams& p, int esz, hipStream_t stream);
 int gta_merge_bwd_dispatch(const GtaMergeBwdParams& p, int esz, hipStream_t stream);
 int gta_bwd_varlen_dispatch(const GtaBwdParams& p, const int32_t* key_lens, const int32_t* q_lens, int dhp, int esz, hipStream_t stream);
 int gta_bwd_gather_dispatch(const GtaBwdParams& p, const int32_t* key_idx, const int32_t* key_lens, int dhp, int esz, hipStream_t stream);
+int gta_bwd_qmask_dispatch(const GtaBwdParams& p, const int32_t* key_idx, const int32_t* key_lens, const int32_t* q_lens, const uint8_t* q_live,
+                           int dhp, int esz, hipStream_t stream);
 
 namespace {
 
@@ -238,13 +240,15 @@ int varlen_flags(const GtaAttnDesc* d) {
 int fwd_call(const GtaAttnDesc* d, const void* q, const void* k, const void* v,
              const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
              const float* trans_coeff, const float* tau, bool varlen, const int32_t* key_lens, bool gather, const int32_t* key_idx,
-             void* out, float* lse, void* workspace, int64_t workspace_bytes, void* stream) {
+             bool qmask, const uint8_t* q_live, void* out, float* lse, void* workspace, int64_t workspace_bytes, void* stream) {
     int rc = check_common(d);
     if (rc) return rc;
     if (!k || !v || ((!q || !out) && !(d->flags & GTA_FLAG_PREP_ONLY))) return fail(GTA_E_BADARG, "null q/k/v/out");
+    if (qmask && !(varlen && gather)) return fail(GTA_E_BADARG, "the query mask comes with the gather");
     if (varlen) {
         if (!key_lens) return fail(GTA_E_BADARG, "null key_lens");
         if (gather && !key_idx && !(d->flags & GTA_FLAG_KV_READY)) return fail(GTA_E_BADARG, "null key_idx");
+        if (qmask && !q_live) return fail(GTA_E_BADARG, "null q_live");
         if (!workspace) return fail(GTA_E_BADARG, "per-scene key prefixes need the workspace of gta_attn_fwd_workspace_bytes()");
     }
     GtaFwdParams p;
@@ -263,6 +267,7 @@ int fwd_call(const GtaAttnDesc* d, const void* q, const void* k, const void* v,
         s.kind = GTA_FWD_FWD2; s.coal = false; s.qtiles = false; s.rows = 128; s.name = "gta_fwd2_kernel"; s.varlen = true;
         p.key_lens = key_lens;
         if (gather) { s.gather = true; s.key_idx = (d->flags & GTA_FLAG_KV_READY) ? nullptr : key_idx; }
+        if (qmask) { s.qmask = true; s.q_live = q_live; }      // (the QMASK twins of the VARLEN attention kernel)
     } else if (t_prof && !(d->flags & GTA_FLAG_PREP_ONLY)) {      // (start / end stamps of every work item: gta_debug_profile_next_attention_kernel)
         if ((int64_t)d->B * d->H * ((d->Tq + s.rows - 1) / s.rows) <= t_prof_items) p.prof = t_prof;
         t_prof = nullptr;
@@ -286,7 +291,7 @@ extern "C" int gta_attn_fwd(const GtaAttnDesc* d, const void* q, const void* k, 
                             const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
                             const float* trans_coeff, const float* tau, void* out, float* lse,
                             void* workspace, int64_t workspace_bytes, void* stream) {
-    return fwd_call(d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, false, nullptr, false, nullptr, out, lse, workspace, workspace_bytes, stream);
+    return fwd_call(d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, false, nullptr, false, nullptr, false, nullptr, out, lse, workspace, workspace_bytes, stream);
 }
 
 extern "C" int gta_attn_fwd_varlen_supported(const GtaAttnDesc* desc) {
@@ -298,7 +303,7 @@ extern "C" int gta_attn_fwd_varlen(const GtaAttnDesc* d, const void* q, const vo
                                    const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
                                    const float* trans_coeff, const float* tau, const int32_t* key_lens, void* out, float* lse,
                                    void* workspace, int64_t workspace_bytes, void* stream) {
-    return fwd_call(d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, true, key_lens, false, nullptr, out, lse, workspace, workspace_bytes, stream);
+    return fwd_call(d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, true, key_lens, false, nullptr, false, nullptr, out, lse, workspace, workspace_bytes, stream);
 }
 
 // Any per-scene subset of the key tokens: the rules and the workspace of gta_attn_fwd_varlen, the GATHER instances of the pre-pass
@@ -308,7 +313,19 @@ extern "C" int gta_attn_fwd_gather(const GtaAttnDesc* d, const void* q, const vo
                                    const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
                                    const float* trans_coeff, const float* tau, const int32_t* key_idx, const int32_t* key_lens, void* out, float* lse,
                                    void* workspace, int64_t workspace_bytes, void* stream) {
-    return fwd_call(d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, true, key_lens, true, key_idx, out, lse, workspace, workspace_bytes, stream);
+    return fwd_call(d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, true, key_lens, true, key_idx, false, nullptr, out, lse, workspace, workspace_bytes, stream);
+}
+
+// gta_attn_fwd_gather under a query-side mask: the QMASK twins of the VARLEN gta_fwd2_kernel (dead rows: never used, out and lse +0.0)
+extern "C" int gta_attn_fwd_qmask_supported(const GtaAttnDesc* desc) { return gta_attn_fwd_gather_supported(desc); }
+
+extern "C" int gta_attn_fwd_qmask(const GtaAttnDesc* d, const void* q, const void* k, const void* v,
+                                  const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
+                                  const float* trans_coeff, const float* tau, const int32_t* key_idx, const int32_t* key_lens,
+                                  const uint8_t* q_live, void* out, float* lse,
+                                  void* workspace, int64_t workspace_bytes, void* stream) {
+    if (d && (d->flags & GTA_FLAG_PREP_ONLY)) return fail(GTA_E_BADARG, "gta_attn_fwd_qmask runs the attention step: no GTA_FLAG_PREP_ONLY (gta_attn_fwd_gather builds the images)");
+    return fwd_call(d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, true, key_lens, true, key_idx, true, q_live, out, lse, workspace, workspace_bytes, stream);
 }
 
 
@@ -447,12 +464,13 @@ int bwd_flags(const GtaAttnDesc* d) {
 
 // the four backward entries.  varlen (gta_attn_bwd_varlen) is the explicit selector of the VARLEN instances -- never "key_lens is non-null";
 // gather (gta_attn_bwd_gather; with varlen, q_lens null) that of the GATHER dK/dV walk -- never "key_idx is non-null"; with_dlse
-// (gta_attn_bwd_dlse) likewise selects the instances that read dlse
+// (gta_attn_bwd_dlse) likewise selects the instances that read dlse; qmask (gta_attn_bwd_qmask; with gather, q_lens allowed) the QMASK instances
+// of the q-side pre-pass and of the dQ walk
 int bwd_call(const GtaAttnDesc* d, const void* q, const void* k, const void* v, const void* out,
              const void* dout, const float* lse, const float* vrep_q, const float* vrep_k,
              const float* cs_q, const float* cs_k, const float* trans_coeff, const float* tau,
-             bool varlen, const int32_t* key_lens, const int32_t* q_lens, bool gather, const int32_t* key_idx, bool with_dlse, const float* dlse,
-             const void* kv_images, void* dq, void* dk, void* dv, const int64_t* dqkv_stride,
+             bool varlen, const int32_t* key_lens, const int32_t* q_lens, bool gather, const int32_t* key_idx, bool qmask, const uint8_t* q_live,
+             bool with_dlse, const float* dlse, const void* kv_images, void* dq, void* dk, void* dv, const int64_t* dqkv_stride,
              const int64_t* dout_stride, float* dtrans_coeff, float* dtau, void* workspace,
              int64_t workspace_bytes, void* stream) {
     int rc = check_common(d);
@@ -460,8 +478,10 @@ int bwd_call(const GtaAttnDesc* d, const void* q, const void* k, const void* v, 
     if (varlen) {
         if (!key_lens) return fail(GTA_E_BADARG, "null key_lens");
         if (gather && !key_idx) return fail(GTA_E_BADARG, "null key_idx (the backward scatters dk / dv through it, with kv_images too)");
+        if (qmask && !gather) return fail(GTA_E_BADARG, "the query mask comes with the gather");
+        if (qmask && !q_live) return fail(GTA_E_BADARG, "null q_live");
         if ((rc = varlen_flags(d))) return rc;
-    } else if (gather) {
+    } else if (gather || qmask) {
         return fail(GTA_E_BADARG, "the gather comes with per-scene key counts");
     }
     if (!q || !k || !v || !out || !dout || !lse || !dq || !dk || !dv || !dqkv_stride || !dout_stride || !workspace)
@@ -512,7 +532,8 @@ int bwd_call(const GtaAttnDesc* d, const void* q, const void* k, const void* v, 
     p.Pq = d->Tq / d->Nq; p.Pk = d->Tk / d->Nk; p.invPq = 1.0f / (float)p.Pq; p.invPk = 1.0f / (float)p.Pk;
     p.dh = d->dh; p.nso2 = d->d_so2 / 2; p.flags = d->flags; p.scale = d->scale;
     if (d->H > 65535 || d->B > 65535) return fail(GTA_E_UNSUPPORTED, "B or H above 65535");
-    return launch_status(gather ? gta_bwd_gather_dispatch(p, key_idx, key_lens, dhp, esz, (hipStream_t)stream)
+    return launch_status(qmask ? gta_bwd_qmask_dispatch(p, key_idx, key_lens, q_lens, q_live, dhp, esz, (hipStream_t)stream)
+                         : gather ? gta_bwd_gather_dispatch(p, key_idx, key_lens, dhp, esz, (hipStream_t)stream)
                          : varlen ? gta_bwd_varlen_dispatch(p, key_lens, q_lens, dhp, esz, (hipStream_t)stream)
                                 : gta_bwd_dispatch(p, with_dlse ? dlse : nullptr, dhp, esz, (hipStream_t)stream), "no kernel instance");
 }
@@ -525,7 +546,7 @@ extern "C" int gta_attn_bwd(const GtaAttnDesc* d, const void* q, const void* k, 
                             const int64_t* dout_stride, float* dtrans_coeff, float* dtau, void* workspace,
                             int64_t workspace_bytes,
                             void* stream) {
-    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, false, nullptr, nullptr, false, nullptr, false, nullptr, kv_images, dq, dk, dv,
+    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, false, nullptr, nullptr, false, nullptr, false, nullptr, false, nullptr, kv_images, dq, dk, dv,
                     dqkv_stride, dout_stride, dtrans_coeff, dtau, workspace, workspace_bytes, stream);
 }
 
@@ -541,7 +562,7 @@ extern "C" int gta_attn_bwd_dlse(const GtaAttnDesc* d, const void* q, const void
                                  const void* kv_images, void* dq, void* dk, void* dv, const int64_t* dqkv_stride,
                                  const int64_t* dout_stride, float* dtrans_coeff, float* dtau, void* workspace,
                                  int64_t workspace_bytes, void* stream) {
-    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, false, nullptr, nullptr, false, nullptr, true, dlse, kv_images, dq, dk, dv,
+    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, false, nullptr, nullptr, false, nullptr, false, nullptr, true, dlse, kv_images, dq, dk, dv,
                     dqkv_stride, dout_stride, dtrans_coeff, dtau, workspace, workspace_bytes, stream);
 }
 
@@ -555,7 +576,7 @@ extern "C" int gta_attn_bwd_varlen(const GtaAttnDesc* d, const void* q, const vo
                                    const void* kv_images, void* dq, void* dk, void* dv, const int64_t* dqkv_stride,
                                    const int64_t* dout_stride, float* dtrans_coeff, float* dtau, void* workspace,
                                    int64_t workspace_bytes, void* stream) {
-    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, true, key_lens, q_lens, false, nullptr, false, nullptr, kv_images, dq, dk, dv,
+    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, true, key_lens, q_lens, false, nullptr, false, nullptr, false, nullptr, kv_images, dq, dk, dv,
                     dqkv_stride, dout_stride, dtrans_coeff, dtau, workspace, workspace_bytes, stream);
 }
 
@@ -570,8 +591,23 @@ extern "C" int gta_attn_bwd_gather(const GtaAttnDesc* d, const void* q, const vo
                                    const void* kv_images, void* dq, void* dk, void* dv, const int64_t* dqkv_stride,
                                    const int64_t* dout_stride, float* dtrans_coeff, float* dtau, void* workspace,
                                    int64_t workspace_bytes, void* stream) {
-    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, true, key_lens, nullptr, true, key_idx, false, nullptr, kv_images,
-                    dq, dk, dv, dqkv_stride, dout_stride, dtrans_coeff, dtau, workspace, workspace_bytes, stream);
+    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, true, key_lens, nullptr, true, key_idx, false, nullptr, false, nullptr,
+                    kv_images, dq, dk, dv, dqkv_stride, dout_stride, dtrans_coeff, dtau, workspace, workspace_bytes, stream);
+}
+
+// gta_attn_bwd_gather under a query-side mask: the backward of gta_attn_fwd_qmask (the QMASK instances of the q-side pre-pass and of the dQ
+// walk; the GATHER dK/dV walk under q_lens)
+extern "C" int gta_attn_bwd_qmask_supported(const GtaAttnDesc* desc) { return gta_attn_bwd_gather_supported(desc); }
+
+extern "C" int gta_attn_bwd_qmask(const GtaAttnDesc* d, const void* q, const void* k, const void* v, const void* out,
+                                  const void* dout, const float* lse, const float* vrep_q, const float* vrep_k,
+                                  const float* cs_q, const float* cs_k, const float* trans_coeff, const float* tau,
+                                  const int32_t* key_idx, const int32_t* key_lens, const uint8_t* q_live, const int32_t* q_lens,
+                                  const void* kv_images, void* dq, void* dk, void* dv, const int64_t* dqkv_stride,
+                                  const int64_t* dout_stride, float* dtrans_coeff, float* dtau, void* workspace,
+                                  int64_t workspace_bytes, void* stream) {
+    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, true, key_lens, q_lens, true, key_idx, true, q_live, false, nullptr,
+                    kv_images, dq, dk, dv, dqkv_stride, dout_stride, dtrans_coeff, dtau, workspace, workspace_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -241,9 +241,14 @@ struct BPrepSmem {
 // DLSE instances (gta_attn_bwd_dlse: the gradient of the pair (out, lse)): LENS = const float*, the row gradients dlse [B,H,Tq] of the
 // log-sum-exp.  dS_ij = P_ij (dP_ij - D_i + dlse_i), so these instances store -(D - dlse) where the others store -D and every walk stays as it
 // is; never combined with VARLEN.
+// QMASK instance (gta_attn_bwd_qmask): LENS = (const int32_t*, const uint8_t*), q_lens and q_live [B, Tq] (non-zero = a live row).  A row is
+// live iff t < q_lens[b] and q_live[b, t] is set; a dead row takes the path of the rows past the prefix -- zero image rows, statistics
+// (-1e30, 0), no term in the partials, and nothing of the row (q, dout, out, lse, cs_q, its view's record) enters arithmetic.
 GTA_DEV const int32_t* first_len() { return nullptr; }
 GTA_DEV const int32_t* first_len(const int32_t* a) { return a; }
 GTA_DEV const int32_t* first_len(const float*) { return nullptr; }
+GTA_DEV const int32_t* first_len(const int32_t* a, const uint8_t*) { return a; }
+GTA_DEV const uint8_t* second_live(const int32_t*, const uint8_t* m) { return m; }
 GTA_DEV const float* first_dlse() { return nullptr; }
 GTA_DEV const float* first_dlse(const int32_t*) { return nullptr; }
 GTA_DEV const float* first_dlse(const float* a) { return a; }
@@ -253,7 +258,9 @@ template <int DHP, int ESZ, bool X3 = false, bool VARLEN = false, class... LENS>
 __global__ __launch_bounds__(256) void gta_bwd_prep_kernel(const GtaBwdParams p, LENS... lens) {
     static_assert(!(X3 && VARLEN), "no fp32-faithful VARLEN instances");
     constexpr bool DLSE = LensIsDlse<LENS...>::value;
-    static_assert(sizeof...(LENS) == ((VARLEN || DLSE) ? 1 : 0) && !(VARLEN && DLSE), "q_lens comes with VARLEN, dlse without it");
+    constexpr bool QMASK = sizeof...(LENS) == 2;         // (q_lens, q_live)
+    static_assert(sizeof...(LENS) == (QMASK ? 2 : (VARLEN || DLSE) ? 1 : 0) && !(VARLEN && DLSE) && (!QMASK || VARLEN),
+                  "q_lens comes with VARLEN, dlse without it, q_live behind q_lens");
     using S = BPrepSmem<DHP, ESZ, X3>;
     constexpr int CHP = DHP / 8, U = S::U, IMG = S::IMG;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -293,8 +300,11 @@ __global__ __launch_bounds__(256) void gta_bwd_prep_kernel(const GtaBwdParams p,
     const float qscale = p.scale * LOG2E / (p.tau ? *p.tau : 1.0f);
     const int r = lane;
     const int t_raw = j * BN + r;
-    const bool valid = t_raw < GTA_TQB;
+    bool valid = t_raw < GTA_TQB;
     const int t = valid ? t_raw : GTA_TQB - 1;
+    // (QMASK) a row is live iff it is inside the prefix and its byte of q_live is set; a dead row inside the prefix takes the path of the rows
+    // past it -- the raw-tile DMA above brought it into LDS, where nothing reads it.  t stays the row's own: an address inside the scene
+    if constexpr (QMASK) valid = valid && second_live(lens...)[(long)b * p.Tq + t] != 0;
     const int n = view_of(t, p.Pq, p.invPq);
     const float* rc = rec + n * BREC;
     float dpart = 0.f, dcpart = 0.f;
@@ -410,12 +420,17 @@ __global__ __launch_bounds__(256) void gta_bwd_prep_kernel(const GtaBwdParams p,
     float* st = p.stats + tile * 128;
     if (tid < 64) {
         const int tt = j * BN + tid;
+        if constexpr (QMASK) {                // (tid < 64: tid is the row `valid` was worked out for -- a dead row's lse and D are not read)
+            st[tid] = valid ? -(p.lse[((long)b * p.H + h) * p.Tq + tt] * LOG2E) : -1e30f;
+            st[64 + tid] = valid ? -((dsum[tid] + dsum[64 + tid]) + (dsum[128 + tid] + dsum[192 + tid])) : 0.f;
+        } else {
         st[tid] = tt < GTA_TQB ? -(p.lse[((long)b * p.H + h) * p.Tq + tt] * LOG2E) : -1e30f;
         if constexpr (DLSE) {
             const float* dlse = first_dlse(lens...);
             st[64 + tid] = tt < p.Tq ? -(((dsum[tid] + dsum[64 + tid]) + (dsum[128 + tid] + dsum[192 + tid])) - dlse[((long)b * p.H + h) * p.Tq + tt]) : 0.f;
         } else {
             st[64 + tid] = tt < GTA_TQB ? -((dsum[tid] + dsum[64 + tid]) + (dsum[128 + tid] + dsum[192 + tid])) : 0.f;
+        }
         }
     }
     if (tid == 0) p.dc_partial[p.dc_off_prep + tile] = dc_wg;
@@ -465,9 +480,14 @@ GTA_DEV void dma_stats(float* dst, const float* src, int wave, int lane) {
 
 // VARLEN: the walk runs over the ceil(Tk_b / 64) key tiles of the scene's prefix and masks the last one against Tk_b (the image rows past the
 // prefix are zero, which alone would leave P = exp2(-lse2) there); query rows at or past Tq_b store zeros and read nothing of their own.
-template <int DHP, int ESZ, bool VARLEN = false>
+// QMASK (with VARLEN; q_live [B, Tq] uint8): "a row past the query prefix" becomes "a dead row" -- past the prefix or with its byte of q_live
+// clear: its dq row is +0.0 and nothing of it is read (q, cs_q, its view's record); its image rows are zero and its statistics (-1e30, 0), so
+// it adds exact zeros to the walk.  A 128-row block without a live row stores zeros and returns before any DMA or barrier.
+template <int DHP, int ESZ, bool VARLEN = false, bool QMASK = false>
 // (body: workgroup L of nwg of this kernel's grid -- its own launch, or its share of the joint launch gta_bwd_dqkv_kernel)
-GTA_DEV void bwd_dq_body(const GtaBwdParams& p, char* smem, const int L, const int nwg, const int32_t* key_lens = nullptr, const int32_t* q_lens = nullptr) {
+GTA_DEV void bwd_dq_body(const GtaBwdParams& p, char* smem, const int L, const int nwg, const int32_t* key_lens = nullptr, const int32_t* q_lens = nullptr,
+                         const uint8_t* q_live = nullptr) {
+    static_assert(!QMASK || VARLEN, "q_live comes with the per-scene lengths");
     using S = DqSmem<DHP>;
     constexpr int CHP = S::CHP, KS = DHP / 16, DB = DHP / 32, BM = 128;
     constexpr int DMA_PER_WAVE = S::STAGE / 1024 / 4;
@@ -492,6 +512,19 @@ GTA_DEV void bwd_dq_body(const GtaBwdParams& p, char* smem, const int L, const i
     if constexpr (VARLEN) {
         tk_b = len_of(key_lens, b, p.Tk);
         tq_b = len_of(q_lens, b, p.Tq);
+        if constexpr (QMASK) {                            // a block without a live row: every wave reads the block's 128 bytes and votes
+            const int r0 = q0 + lane, r1 = r0 + 64;
+            const uint8_t* ql = q_live + (long)b * p.Tq;
+            const bool any = (r0 < tq_b && ql[r0] != 0) || (r1 < tq_b && ql[r1] != 0);
+            if (__builtin_amdgcn_ballot_w64(any) == 0) {  // (workgroup-uniform, the case below included): zeros, before any DMA or barrier
+                store_zero_rows<ESZ>((char*)p.dq + ((long)b * p.dq_sb + (long)h * p.dq_sh) * ESZ, p.dq_st * ESZ, q0, q0 + BM < p.Tq ? q0 + BM : p.Tq, ch_real, tid);
+                if (tid == 0) {
+                    p.dc_partial[p.dc_off_dq + w] = 0.f;
+                    if (p.dt_partial) p.dt_partial[w] = 0.f;
+                }
+                return;
+            }
+        } else
         if (q0 >= tq_b) {                                 // a block wholly past the query prefix (workgroup-uniform): zeros, before any DMA or barrier
             store_zero_rows<ESZ>((char*)p.dq + ((long)b * p.dq_sb + (long)h * p.dq_sh) * ESZ, p.dq_st * ESZ, q0, q0 + BM < p.Tq ? q0 + BM : p.Tq, ch_real, tid);
             if (tid == 0) {
@@ -681,13 +714,20 @@ GTA_DEV void bwd_dq_body(const GtaBwdParams& p, char* smem, const int L, const i
     char* dqg = (char*)p.dq + ((long)b * p.dq_sb + (long)h * p.dq_sh) * ESZ;
     float dcpart = 0.f, dtpart = 0.f;
     const bool want_dtau = p.dt_partial != nullptr;
+    // (QMASK) item = wave + 4 it: every item of a thread is row lane + 64 (wave & 1) -- its liveness is read once
+    bool dead_q = false;
+    if constexpr (QMASK) {
+        const int t = q0 + lane + 64 * (wave & 1);
+        dead_q = t < p.Tq && (t >= tq_b || q_live[(long)b * p.Tq + t] == 0);
+    }
 #pragma unroll
     for (int it = 0; it < ITEMS; ++it) {
         const int item = wave + 4 * it;
         const int c = item >> 1;
         const int r = lane + 64 * (item & 1);
         const int t = q0 + r;
-        if (VARLEN && c < ch_real && t >= tq_b && t < p.Tq) {       // a row past the query prefix: zeros, nothing of the row is read
+        if (QMASK ? (c < ch_real && dead_q)                         // a dead row: zeros, nothing of the row is read
+            : (VARLEN && c < ch_real && t >= tq_b && t < p.Tq)) {   // a row past the query prefix: zeros, nothing of the row is read
             const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
             g_store_chunk<ESZ>(dqg + (long)t * p.dq_st * ESZ, c, z);
         } else if (c < ch_real && t < GTA_TQ) {
@@ -1090,6 +1130,14 @@ __global__ __launch_bounds__(256, (DHP > 96 ? 1 : 2)) void gta_bwd_dkv_gather_ke
                                                                                       const int32_t* key_idx) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     bwd_dkv_body<DHP, ESZ, true, true>(p, smem, blockIdx.x, gridDim.x, key_lens, q_lens, key_idx);
+}
+// the QMASK instances of the dQ walk (gta_attn_bwd_qmask): q_live [B, Tq] beside the lengths.  That entry's dK/dV walk is the GATHER one above
+// under q_lens = 1 + the last live row (dead rows reach it as zero image rows), its q-side pre-pass the QMASK instance of gta_bwd_prep_kernel
+template <int DHP, int ESZ>
+__global__ __launch_bounds__(256, (DHP > 96 ? 1 : 2)) void gta_bwd_dq_qmask_kernel(const GtaBwdParams p, const int32_t* key_lens, const int32_t* q_lens,
+                                                                                    const uint8_t* q_live) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    bwd_dq_body<DHP, ESZ, true, true>(p, smem, blockIdx.x, gridDim.x, key_lens, q_lens, q_live);
 }
 template <int DHP, int ESZ>
 __global__ __launch_bounds__(256, (DHP > 96 ? 1 : 2)) void gta_bwd_dqkv_kernel(const GtaBwdParams p, const int n_dq) {
@@ -2134,7 +2182,47 @@ int run_bwd_gather(const GtaBwdParams& p, const int32_t* key_idx, const int32_t*
     return hipGetLastError() == hipSuccess ? GTA_OK : GTA_E_LAUNCH;
 }
 
+// gta_attn_bwd_qmask: run_bwd_gather with the QMASK instances of the q-side pre-pass and of the dQ walk.  q_lens may be null (Tq: the dK/dV walk
+// then runs over every query tile, the dead ones adding exact zeros)
+template <int DHP, int ESZ>
+int run_bwd_qmask(const GtaBwdParams& p, const int32_t* key_idx, const int32_t* key_lens, const int32_t* q_lens, const uint8_t* q_live, hipStream_t stream) {
+    const int n_qt = (p.Tq + BN - 1) / BN;
+    if (int rc = gta_lds_optin<&gta_bwd_prep_kernel<DHP, ESZ, false, true, const int32_t*, const uint8_t*>>(BPrepSmem<DHP, ESZ>::total(GTA_MAX_VIEWS))) return rc;
+    if (int rc = gta_lds_optin<&gta_bwd_dq_qmask_kernel<DHP, ESZ>>(DqSmem<DHP>::total(GTA_MAX_VIEWS))) return rc;
+    if (int rc = gta_lds_optin<&gta_bwd_dkv_gather_kernel<DHP, ESZ>>(DkvSmem<DHP>::total(GTA_MAX_VIEWS))) return rc;
+    const long prep_grid = ((long)p.B * n_qt + 7) / 8 * 8 * p.H;
+    const long n_dq = (long)p.B * p.H * ((p.Tq + 127) / 128), n_dkv = (long)p.B * p.H * ((p.Tk + 127) / 128);
+    if (prep_grid > 0x7fffffffL || n_dq > 0x7fffffffL || n_dkv > 0x7fffffffL) return GTA_E_UNSUPPORTED;
+    const int lds_prep = BPrepSmem<DHP, ESZ>::total(p.vrep_q ? p.Nq : 0);
+    const int lds_dq = DqSmem<DHP>::total(p.vrep_q ? p.Nq : 0), lds_dkv = DkvSmem<DHP>::total(p.vrep_k ? p.Nk : 0);
+    hipLaunchKernelGGL((gta_bwd_prep_kernel<DHP, ESZ, false, true, const int32_t*, const uint8_t*>), dim3((unsigned)prep_grid), dim3(256), lds_prep, stream,
+                       p, q_lens, q_live);
+    hipLaunchKernelGGL((gta_bwd_dq_qmask_kernel<DHP, ESZ>), dim3((unsigned)n_dq), dim3(256), lds_dq, stream, p, key_lens, q_lens, q_live);
+    hipLaunchKernelGGL((gta_bwd_dkv_gather_kernel<DHP, ESZ>), dim3((unsigned)n_dkv), dim3(256), lds_dkv, stream, p, key_lens, q_lens, key_idx);
+    if (p.dtrans_coeff)
+        hipLaunchKernelGGL(gta_reduce_kernel, dim3(1), dim3(1024), 0, stream, p.dc_partial, p.dc_total, p.dtrans_coeff, (const float*)nullptr);
+    if (p.dtau)
+        hipLaunchKernelGGL(gta_reduce_kernel, dim3(1), dim3(1024), 0, stream, p.dt_partial, (int)n_dq, p.dtau, p.tau);
+    return hipGetLastError() == hipSuccess ? GTA_OK : GTA_E_LAUNCH;
+}
+
 }  // namespace
+
+int gta_bwd_qmask_dispatch(const GtaBwdParams& p, const int32_t* key_idx, const int32_t* key_lens, const int32_t* q_lens, const uint8_t* q_live,
+                           int dhp, int esz, hipStream_t stream) {
+    if (!key_idx || !key_lens || !q_live) return GTA_E_BADARG;
+    if (p.flags & GTA_FLAG_FP32_PRODUCTS) return GTA_E_UNSUPPORTED;
+#define GTA_CASEB(D) case D: return esz == 2 ? run_bwd_qmask<D, 2>(p, key_idx, key_lens, q_lens, q_live, stream) \
+                                              : run_bwd_qmask<D, 4>(p, key_idx, key_lens, q_lens, q_live, stream);
+    switch (dhp) {
+        GTA_CASEB(32)
+        GTA_CASEB(64)
+        GTA_CASEB(96)
+        GTA_CASEB(128)
+    }
+#undef GTA_CASEB
+    return GTA_E_UNSUPPORTED;
+}
 
 int gta_bwd_gather_dispatch(const GtaBwdParams& p, const int32_t* key_idx, const int32_t* key_lens, int dhp, int esz, hipStream_t stream) {
     if (!key_idx || !key_lens) return GTA_E_BADARG;

@@ -73,10 +73,31 @@ GTA_DEV KArgs kargs() {
 // VARLEN: the key side of scene b is the prefix of p.key_lens[b] tokens of its Tk (gta_attention's key_views).  A work item belongs to one
 // (b,h), so the prefix is wave-uniform: it replaces Tk in the tile count, the tail mask, the one-tile rule and the lazy-tail rule, and the
 // DMA stream carries the tile count of the item whose tiles it is requesting.  The workspace keeps the strides of the full Tk.
-template <int DHP, int ESZ, int LAYOUT, bool X3 = false, bool VARLEN = false>
-__global__ __launch_bounds__(256, (X3 ? 2 : DHP <= 64 ? 3 : 2)) void gta_fwd2_kernel(const GtaFwdParams p_kernarg) {
+//
+// QMASK (gta_attn_fwd_qmask; VARLEN plus a query-side mask): q_live [B, Tq] uint8, non-zero = the row is live.  The QMASK instances alone take
+// the trailing argument (QM = const uint8_t*); without it QM is empty and the kernel's signature and argument block are what they were.  The
+// mask is read through the kernarg segment where it is needed (item prologue, epilogue), like every other argument: nothing of it lives
+// through the tile loop.
+//   * an item without a live row (every wave reads the item's 128 bytes and votes: the answer is workgroup-uniform without a barrier) stores
+//     +0.0 to its out and lse rows below Tq and returns -- before its first dma_next and Q load, so no LDS DMA is in flight when it ends.
+//     This needs one workgroup per item (a persistent grid's stream would have to skip the item's tiles): launch_fwd2 checks it.
+//   * in a live item a dead row is loaded like any other (its q / cs_q row and its view's record must be readable and may hold anything)
+//     and zeroed BEHIND rho_q (0 * NaN is not 0): it walks the tiles as q' = 0 with |q'| = 0 -- to every wave-wide decision of the lazy
+//     softmax it is the row a zero q row gives -- and the epilogue stores +0.0 to its out and lse.  Rows past Tq follow row Tq - 1, whose
+//     copies they are.
+typedef const uint8_t* const __attribute__((address_space(4)))* QLiveArg;
+GTA_DEV const uint8_t* q_live_arg() {
+    static_assert(sizeof(GtaFwdParams) % 8 == 0, "the trailing pointer sits right behind the block");
+    const __attribute__((address_space(4))) char* a = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(a));
+    return *(QLiveArg)(a + sizeof(GtaFwdParams));
+}
+template <int DHP, int ESZ, int LAYOUT, bool X3 = false, bool VARLEN = false, class... QM>
+__global__ __launch_bounds__(256, (X3 ? 2 : DHP <= 64 ? 3 : 2)) void gta_fwd2_kernel(const GtaFwdParams p_kernarg, QM... qm) {
     static_assert(!X3 || (ESZ == 4 && DHP <= 64), "the fp32-faithful two-stage instances: fp32 inputs, dh <= 64");
     static_assert(!(X3 && VARLEN), "no fp32-faithful VARLEN instances");
+    constexpr bool QMASK = sizeof...(QM) == 1;
+    static_assert(sizeof...(QM) <= 1 && (!QMASK || VARLEN), "q_live comes with the VARLEN instances");
     using S = Smem2<DHP, X3>;
     // chunk descriptor: a compile-time constant for the shipped layouts (c is constant per unrolled item)
 #define GTA_DESC(c) (LAYOUT == GTA_LAYOUT_GENERIC ? pp->ctab[c] : gta_layout_desc(LAYOUT, c))
@@ -95,6 +116,30 @@ __global__ __launch_bounds__(256, (X3 ? 2 : DHP <= 64 ? 3 : 2)) void gta_fwd2_ke
     const int n_tiles = (pp->Tk + BN - 1) / BN;
     const int ch_real = pp->dh >> 3;
     char* ring = smem + S::OFF_RING;
+    if constexpr (QMASK) {
+        // (QMASK) the item's vote, in front of everything: one workgroup per item (launch_fwd2 checks it), so this workgroup's only item is
+        // blockIdx.x.  Every wave reads the item's 128 mask bytes -- the answer is workgroup-uniform without a barrier.  A dead item stores
+        // +0.0 to its out and lse rows below Tq and ends here: no DMA was requested, no Q row loaded
+        const int w = item_of(blockIdx.x, n_items);
+        const int bh = w / pp->n_qtiles, q0 = (w - bh * pp->n_qtiles) * BM;
+        const int b = bh / pp->H, h = bh - b * pp->H;
+        const uint8_t* ql = q_live_arg() + (long)b * pp->Tq;
+        const int r0 = q0 + (tid & 63), r1 = r0 + 64;
+        const bool any = (r0 < pp->Tq && ql[r0] != 0) || (r1 < pp->Tq && ql[r1] != 0);
+        if (__builtin_amdgcn_ballot_w64(any) == 0) {
+            const int t_end = q0 + BM < pp->Tq ? q0 + BM : pp->Tq;
+            char* og = (char*)pp->o + ((long)b * pp->o_sb + (long)h * pp->o_sh) * ESZ;
+            const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            const int r = q0 + (tid & (BM - 1));            // two threads per row: the even and the odd chunks
+            if (r < t_end) {
+                char* orow = og + (long)r * pp->o_st * ESZ;
+#pragma unroll 1
+                for (int c = tid >> 7; c < ch_real; c += 2) gstore_chunk2<ESZ>(orow, c, z);
+                if (pp->lse && tid < BM) pp->lse[((long)b * pp->H + h) * pp->Tq + r] = 0.f;
+            }
+            return;
+        }
+    }
 
     // per work item, when a profile buffer is set (gta_debug_profile_next_attention_kernel): [0] start, [4] end (s_memtime: shader cycles),
     // [5] / [6] start / end by s_memrealtime (100 MHz) -- what bench.py turns into kernel cycles and the granted clock.
@@ -182,6 +227,7 @@ __global__ __launch_bounds__(256, (X3 ? 2 : DHP <= 64 ? 3 : 2)) void gta_fwd2_ke
     QrecItem rb0;
     rb0.val = 0.f; rb0.kind = 1; rb0.rr = 0; rb0.cc = 0; rb0.dst = -1;
     int b, h, q0, n_first, n_cnt, my_t;
+    bool my_live = true;                  // (QMASK) this lane's MFMA row is live; used up by rho_q below
     {
         const int w = item_of(V, n_items);
         const int bh = w / pp->n_qtiles, qt = w - bh * pp->n_qtiles;
@@ -196,6 +242,7 @@ __global__ __launch_bounds__(256, (X3 ? 2 : DHP <= 64 ? 3 : 2)) void gta_fwd2_ke
         // (the select folds); a mixed pair runs both kinds under exec masks.
         my_t = q0 + wave * 32 + l31;
         my_t = my_t < pp->Tq ? my_t : pp->Tq - 1;
+        if constexpr (QMASK) my_live = q_live_arg()[(long)b * pp->Tq + my_t] != 0;
         const char* qrow = (const char*)pp->q + ((long)b * pp->q_sb + (long)h * pp->q_sh + (long)my_t * pp->q_st) * ESZ + lh * 8 * ESZ;
         const float* csrow = pp->cs_q ? pp->cs_q + ((long)b * pp->Tq + my_t) * 2 * pp->nso2 : nullptr;
         auto q_loads = [&](auto FULLC) {
@@ -275,6 +322,10 @@ __global__ __launch_bounds__(256, (X3 ? 2 : DHP <= 64 ? 3 : 2)) void gta_fwd2_ke
                 } else {
 #pragma unroll
                     for (int i = 0; i < 8; ++i) x[0][i] = 0.f;
+                }
+                if constexpr (QMASK) {                     // a dead row: q' = 0 behind rho_q, whatever the row, its (cos, sin) and its record hold
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) x[0][i] = my_live ? x[0][i] : 0.f;
                 }
                 const u32x4_t qw = pack8(x[0]);
                 qf[ks] = __builtin_bit_cast(bf16x8_t, qw);
@@ -688,6 +739,30 @@ __global__ __launch_bounds__(256, (X3 ? 2 : DHP <= 64 ? 3 : 2)) void gta_fwd2_ke
         if (fast) o_items(std::true_type{}); else o_items(std::false_type{});
     }
     }
+    if constexpr (QMASK) {
+        // (QMASK) the epilogue above is the VARLEN one as it is -- it has no register to spare -- and stored whatever a dead row's accumulators
+        // held.  Now that they are dead: the row's mask byte, read again (nothing of it lived through the tile loop), and +0.0 over the out
+        // and lse of a dead row below Tq, by the lane that stored them (stores of one lane to one address keep their order)
+        KArgs pp = kargs();
+        int tid_z = threadIdx.x;            // (everything re-derived: nothing is kept alive across the epilogue for this)
+        asm volatile("" : "+v"(tid_z));
+        const int l31 = tid_z & 31, lh = (tid_z >> 5) & 1;
+        const int wz = item_of(V, pp->n_items), bhz = wz / pp->n_qtiles;
+        const int b = bhz / pp->H, h = bhz - b * pp->H, q0 = (wz - bhz * pp->n_qtiles) * BM;
+        const int tZ = q0 + wave * 32 + l31;
+        if (tZ < pp->Tq && q_live_arg()[(long)b * pp->Tq + tZ] == 0) {
+            char* orow = (char*)pp->o + ((long)b * pp->o_sb + (long)h * pp->o_sh + (long)tZ * pp->o_st) * ESZ;
+            uint32_t zu = 0u;               // (made HERE: as a constant the zero vector is hoisted out of the item loop, and spilled there)
+            asm volatile("" : "+v"(zu));
+            const u32x4_t zv = {zu, zu, zu, zu};
+#pragma unroll 1
+            for (int c = lh; c < ch_real; c += 2) {
+                *reinterpret_cast<u32x4_t*>(orow + c * 8 * ESZ) = zv;
+                if (ESZ == 4) *reinterpret_cast<u32x4_t*>(orow + c * 8 * ESZ + 16) = zv;
+            }
+            if (pp->lse && lh == 0) pp->lse[((long)b * pp->H + h) * pp->Tq + tZ] = 0.f;
+        }
+    }
 #undef GTA_CE
 #undef GTA_DLE
     GTA_STAMP(V, 4); GTA_STAMPR(V, 6); GTA_STAMP_HW(V);
@@ -704,11 +779,12 @@ __global__ __launch_bounds__(256, (X3 ? 2 : DHP <= 64 ? 3 : 2)) void gta_fwd2_ke
 #undef GTA_DESC
 }
 
-template <int DHP, int ESZ, int LAYOUT, bool X3 = false, bool VARLEN = false>
-int launch_fwd2(const GtaFwdParams& p, hipStream_t stream) {
+// (QM: the QMASK instances' trailing argument -- q_live, [B, Tq] uint8 on the device -- or nothing)
+template <int DHP, int ESZ, int LAYOUT, bool X3 = false, bool VARLEN = false, class... QM>
+int launch_fwd2(const GtaFwdParams& p, hipStream_t stream, QM... qm) {
     using S = Smem2<DHP, X3>;
-    const void* kfn = reinterpret_cast<const void*>(&gta_fwd2_kernel<DHP, ESZ, LAYOUT, X3, VARLEN>);
-    if (int rc = gta_lds_optin<&gta_fwd2_kernel<DHP, ESZ, LAYOUT, X3, VARLEN>>(S::total(GTA_MAX_VIEWS))) return rc;
+    const void* kfn = reinterpret_cast<const void*>(&gta_fwd2_kernel<DHP, ESZ, LAYOUT, X3, VARLEN, QM...>);
+    if (int rc = gta_lds_optin<&gta_fwd2_kernel<DHP, ESZ, LAYOUT, X3, VARLEN, QM...>>(S::total(GTA_MAX_VIEWS))) return rc;
     int lds = S::total(p.vrep_q ? p.nrec : 0);
     // One workgroup per item, or (GTA_FLAG_PERSIST / the few-rounds rule below) a persistent grid of as many workgroups as are resident at once
     // (registers and LDS: two per CU at dh = 96, three at dh = 64), a multiple of 8 so that the virtual ids of a workgroup
@@ -750,14 +826,17 @@ int launch_fwd2(const GtaFwdParams& p, hipStream_t stream) {
     }
     if (const char* e = getenv("GTA_GRID")) { const long g = atol(e); if (g > 0) grid = g < p.n_items ? g : p.n_items; }
 #endif
+    // (QMASK) a dead item returns from the kernel: one workgroup per item, or the items behind it would never run.  VARLEN never takes the
+    // persistent grid above, so this cannot fire in a product build (an instrumented build's GTA_GRID can ask for it: refused, not run)
+    if (sizeof...(QM) > 0 && grid != p.n_items) return GTA_E_UNSUPPORTED;
     if (g_fwd2_ev_start && g_fwd2_ev_stop) {
         // profiling hook (bench.py): start / stop events taken from the dispatch itself -- no marker packets, so the
         // kernel's neighbours in the stream are not pushed apart the way two hipEventRecord calls push them (~3 us each)
-        hipExtLaunchKernelGGL((gta_fwd2_kernel<DHP, ESZ, LAYOUT, X3, VARLEN>), dim3((unsigned)grid), dim3(256), lds, stream,
-                              (hipEvent_t)g_fwd2_ev_start, (hipEvent_t)g_fwd2_ev_stop, 0, pl);
+        hipExtLaunchKernelGGL((gta_fwd2_kernel<DHP, ESZ, LAYOUT, X3, VARLEN, QM...>), dim3((unsigned)grid), dim3(256), lds, stream,
+                              (hipEvent_t)g_fwd2_ev_start, (hipEvent_t)g_fwd2_ev_stop, 0, pl, qm...);
         g_fwd2_ev_start = g_fwd2_ev_stop = nullptr;
     } else {
-        hipLaunchKernelGGL((gta_fwd2_kernel<DHP, ESZ, LAYOUT, X3, VARLEN>), dim3((unsigned)grid), dim3(256), lds, stream, pl);
+        hipLaunchKernelGGL((gta_fwd2_kernel<DHP, ESZ, LAYOUT, X3, VARLEN, QM...>), dim3((unsigned)grid), dim3(256), lds, stream, pl, qm...);
     }
     return hipGetLastError() == hipSuccess ? GTA_OK : GTA_E_LAUNCH;
 }
@@ -818,15 +897,16 @@ static int launch_flash(const GtaFwdParams& p, const GtaFwdSel& s, hipStream_t s
 }
 
 // the VARLEN instances (s.varlen; they read p.key_lens): gta_fwd2_kernel only, default arithmetic, every layout launch_flash gives that kernel
-template <int DHP, int ESZ>
-static int launch_flash_varlen(const GtaFwdParams& p, const GtaFwdSel& s, hipStream_t stream) {
+// (QM: s.q_live for the QMASK twins -- gta_attn_fwd_qmask --, one per VARLEN instance)
+template <int DHP, int ESZ, class... QM>
+static int launch_flash_varlen(const GtaFwdParams& p, const GtaFwdSel& s, hipStream_t stream, QM... qm) {
     if (s.kind != GTA_FWD_FWD2) return GTA_E_UNSUPPORTED;
     switch (s.layout) {
-        case GTA_LAYOUT_MS:  if (DHP == 96) return launch_fwd2<DHP, ESZ, (DHP == 96 ? GTA_LAYOUT_MS : GTA_LAYOUT_GENERIC), false, true>(p, stream); break;
-        case GTA_LAYOUT_CL:  if (DHP == 64) return launch_fwd2<DHP, ESZ, (DHP == 64 ? GTA_LAYOUT_CL : GTA_LAYOUT_GENERIC), false, true>(p, stream); break;
-        case GTA_LAYOUT_SO2: return launch_fwd2<DHP, ESZ, GTA_LAYOUT_SO2, false, true>(p, stream);
+        case GTA_LAYOUT_MS:  if (DHP == 96) return launch_fwd2<DHP, ESZ, (DHP == 96 ? GTA_LAYOUT_MS : GTA_LAYOUT_GENERIC), false, true>(p, stream, qm...); break;
+        case GTA_LAYOUT_CL:  if (DHP == 64) return launch_fwd2<DHP, ESZ, (DHP == 64 ? GTA_LAYOUT_CL : GTA_LAYOUT_GENERIC), false, true>(p, stream, qm...); break;
+        case GTA_LAYOUT_SO2: return launch_fwd2<DHP, ESZ, GTA_LAYOUT_SO2, false, true>(p, stream, qm...);
     }
-    return launch_fwd2<DHP, ESZ, GTA_LAYOUT_GENERIC, false, true>(p, stream);
+    return launch_fwd2<DHP, ESZ, GTA_LAYOUT_GENERIC, false, true>(p, stream, qm...);
 }
 
 // prep (unless the caller says K'/V' images are already in the workspace) + attention kernel.
@@ -840,9 +920,19 @@ int gta_fwd2_dispatch(GtaFwdParams& p, const GtaFwdSel& s, int dhp, int esz, boo
     if (!run_flash || !s.qtiles) p.qtiles = nullptr;
     if (s.varlen && !p.key_lens) return GTA_E_BADARG;
     if (s.gather && (!s.varlen || (run_prep && !s.key_idx))) return GTA_E_BADARG;
+    if (s.qmask && (!s.varlen || !s.q_live)) return GTA_E_BADARG;          // (before the pre-pass: nothing is enqueued for a refused call)
     if (run_prep) rc = s.gather ? gta_prep_gather_dispatch(p, s.key_idx, dhp, esz, stream) : gta_prep_dispatch(p, dhp, esz, s.varlen, stream);
     else if (p.qtiles) rc = gta_qtiles_dispatch(p, stream);
     if (rc != GTA_OK || !run_flash) return rc;
+    if (s.qmask) {                          // the QMASK twins of the VARLEN instances (gta_attn_fwd_qmask)
+        switch (dhp) {
+            case 32: return esz == 2 ? launch_flash_varlen<32, 2>(p, s, stream, s.q_live) : launch_flash_varlen<32, 4>(p, s, stream, s.q_live);
+            case 64: return esz == 2 ? launch_flash_varlen<64, 2>(p, s, stream, s.q_live) : launch_flash_varlen<64, 4>(p, s, stream, s.q_live);
+            case 96: return esz == 2 ? launch_flash_varlen<96, 2>(p, s, stream, s.q_live) : launch_flash_varlen<96, 4>(p, s, stream, s.q_live);
+            case 128: return esz == 2 ? launch_flash_varlen<128, 2>(p, s, stream, s.q_live) : launch_flash_varlen<128, 4>(p, s, stream, s.q_live);
+        }
+        return GTA_E_UNSUPPORTED;
+    }
     if (s.varlen) {
         switch (dhp) {
             case 32: return esz == 2 ? launch_flash_varlen<32, 2>(p, s, stream) : launch_flash_varlen<32, 4>(p, s, stream);

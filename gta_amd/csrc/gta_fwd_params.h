@@ -51,6 +51,10 @@ struct GtaFwdSel {
     // int32 on the device, compacted into the prefix p.key_lens counts.  The attention kernel is the VARLEN one and never sees the indices.
     bool gather = false;
     const int32_t* key_idx = nullptr;
+    // the QMASK instances of gta_fwd2_kernel (gta_attn_fwd_qmask sets both, with varlen and gather): q_live [B, Tq] uint8 on the device, non-zero =
+    // a live query row.  A trailing kernel argument of those instances alone, so it rides here and not in GtaFwdParams
+    bool qmask = false;
+    const uint8_t* q_live = nullptr;
 };
 // p: the argument block with the operands of the call (p.kp = the workspace or null; p.kn, p.qtiles inside it)
 GtaFwdSel gta_fwd_select(const GtaFwdParams& p, int dhp, int esz);

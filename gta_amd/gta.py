@@ -653,6 +653,35 @@ def key_index_tensors(key_mask: torch.Tensor, device) -> Tuple[torch.Tensor, tor
     return idx.contiguous().to(device, non_blocking=True), lens.to(device, non_blocking=True)
 
 
+def check_query_mask(query_mask, B: Optional[int] = None, Tq: Optional[int] = None):
+    """Validation of a query mask: a bool [B, Tq] tensor (the shape is held against B and Tq where given).  Its values are not looked at: a
+    scene may have no live query row at all."""
+    if not torch.is_tensor(query_mask) or query_mask.dtype != torch.bool or query_mask.dim() != 2:
+        raise native.GtaError("query_mask must be a bool tensor of shape [B, Tq] (True: the query row is live)")
+    if B is not None and tuple(query_mask.shape) != (B, Tq):
+        raise native.GtaError(f"query_mask has shape {tuple(query_mask.shape)} for {B} scenes of {Tq} query tokens")
+
+
+def query_mask_tensors(query_mask: torch.Tensor, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """query_mask (bool [B, Tq], True = the row is live) -> (q_live [B, Tq] bool, q_lens [B] int32) on ``device``: what ``gta_attn_fwd_qmask``
+    and ``gta_attn_bwd_qmask`` read.  q_live is the mask itself (its storage: one byte per row); q_lens[b] is 1 + the index of scene b's last
+    live row, 0 for a scene without one (legal: the kernels clamp it to 1 and find row 0 dead) -- the backward's dK/dV walk skips the query
+    tiles behind it.  A CUDA mask is converted on the device without a sync, a CPU mask on the host and uploaded."""
+    check_query_mask(query_mask)
+    if query_mask.is_cuda and query_mask.device != torch.device(device):
+        raise native.GtaError(f"query_mask lives on {query_mask.device}, the call on {device}")
+    pos = torch.arange(1, query_mask.shape[1] + 1, dtype=torch.int32, device=query_mask.device)
+    lens = (query_mask.to(torch.int32) * pos).amax(1) if query_mask.shape[1] else torch.zeros(query_mask.shape[0], dtype=torch.int32)
+    return query_mask.contiguous().to(device, non_blocking=True), lens.to(torch.int32).to(device, non_blocking=True)
+
+
+def _all_keys_tensors(B: int, Tk: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(key_idx, key_lens) of an all-True key mask -- a query mask without a key mask runs the key_mask route under it: the identity index
+    (an arange, no sort) and the full count"""
+    return (torch.arange(Tk, dtype=torch.int32, device=device).expand(B, Tk).contiguous(),
+            torch.full((B,), Tk, dtype=torch.int32, device=device))
+
+
 def _plan_key(family: str, flags, dt, B, H, Tk, dh, f_dims, so3_degree, Nk, scale, key_views):
     """what the images of a cache depend on besides the keys, reps and trans_coeff (the caller's contract, see gta_attention): the family
     ('fused' / 'staged': different tile images), the key side's shape and layout, the dtype (bf16 / fp32 inputs pick different instances), the
@@ -716,11 +745,12 @@ def _varlen_forward(q, k, v, cfg, tables, trans_coeff, tau, key_lens, key_views=
     return c, ws
 
 
-def _gather_forward(q, k, v, cfg, tables, trans_coeff, tau, key_mask, kv_cache=None, key_idx=None, key_lens=None):
+def _gather_forward(q, k, v, cfg, tables, trans_coeff, tau, key_mask, kv_cache=None, key_idx=None, key_lens=None, q_live=None):
     """The fused layouts with a key mask: ``gta_attn_fwd_gather`` -- the GATHER instances of the pre-pass compact the valid keys, the VARLEN
     gta_fwd2_kernel attends over them.  ``key_idx`` / ``key_lens``: the ready-made tensors of ``key_index_tensors`` (``ForwardPlan``), built
     here when None.  With ``kv_cache`` the first call stores both beside the images (plan key: "key_mask"); later calls run on the stored
-    lengths under GTA_FLAG_KV_READY and build nothing from their mask.  -> (the call, its workspace)"""
+    lengths under GTA_FLAG_KV_READY and build nothing from their mask.  ``q_live`` (``query_mask_tensors``; never with ``kv_cache``): the
+    attention step runs in its QMASK instances (``gta_attn_fwd_qmask``).  -> (the call, its workspace)"""
     c = _setup_call(q, k, v, *cfg, tables, trans_coeff, tau)
     ws = _fused_workspace(c, cfg, kv_cache, "key_mask")
     if c.desc.flags & native.FLAG_KV_READY:
@@ -730,6 +760,10 @@ def _gather_forward(q, k, v, cfg, tables, trans_coeff, tau, key_mask, kv_cache=N
             key_idx, key_lens = key_index_tensors(key_mask, c.q.device)
         if kv_cache is not None:
             kv_cache["key_idx"], kv_cache["key_lens"] = key_idx, key_lens
+    if q_live is not None:
+        native.attn_fwd_qmask(c.desc, c.q, c.k, c.v, tables.get("vrep_q"), tables.get("vrep_k"), tables.get("cs_q"), tables.get("cs_k"),
+                              c.tc, c.ta, key_idx, key_lens, q_live, c.out, c.lse, ws)
+        return c, ws
     native.attn_fwd_gather(c.desc, c.q, c.k, c.v, tables.get("vrep_q"), tables.get("vrep_k"), tables.get("cs_q"), tables.get("cs_k"),
                            c.tc, c.ta, key_idx, key_lens, c.out, c.lse, ws)
     return c, ws
@@ -739,14 +773,17 @@ class _GatherAttn(torch.autograd.Function):
     """The fused layouts with a key mask under grad (``key_mask_backward=True``): the forward of ``_gather_forward``, whose workspace (the compacted
     K'/V' tile images) and LSE serve ``gta_attn_bwd_gather`` under the same ``key_idx`` / ``key_lens`` (``key_index_tensors``: every row a
     permutation, the valid tokens first).  Gradients: q, k, v, trans_coeff, tau -- as ``_GtaAttn``; dk / dv rows of masked tokens are zeros.  No
-    query-side mask, and no gradients of the tables (refused before the call gets here)."""
+    gradients of the tables (refused before the call gets here).  ``q_live`` / ``q_lens`` (``query_mask_tensors``; both or neither): the same
+    two tensors go to ``gta_attn_fwd_qmask`` and ``gta_attn_bwd_qmask`` -- dq rows of dead rows are zeros; without them the two gather
+    entries run as before."""
 
     @staticmethod
-    def forward(ctx, q, k, v, trans_coeff, tau, cfg, key_idx, key_lens, vrep_q, vrep_k, cs_q, cs_k):
+    def forward(ctx, q, k, v, trans_coeff, tau, cfg, key_idx, key_lens, vrep_q, vrep_k, cs_q, cs_k, q_live=None, q_lens=None):
         c, ws = _gather_forward(q, k, v, cfg, dict(vrep_q=vrep_q, vrep_k=vrep_k, cs_q=cs_q, cs_k=cs_k), trans_coeff, tau, None,
-                                key_idx=key_idx, key_lens=key_lens)
+                                key_idx=key_idx, key_lens=key_lens, q_live=q_live)
         ctx.cfg = cfg
         ctx.kv_images = ws
+        ctx.q_mask = (q_live, q_lens)          # (the objects themselves: they need no gradient and the backward hands them on as they are)
         ctx.save_for_backward(c.q, c.k, c.v, c.out, c.lse, c.tc, c.ta, vrep_q, vrep_k, cs_q, cs_k, key_idx, key_lens)
         ctx.tc_meta, ctx.tau_meta = _scalar_meta(trans_coeff), _scalar_meta(tau)
         return c.out
@@ -756,9 +793,11 @@ class _GatherAttn(torch.autograd.Function):
         from . import backward as _bw
         q, k, v, out, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k, key_idx, key_lens = ctx.saved_tensors
         want_dtau = ta is not None and ctx.needs_input_grad[4]
+        q_live, q_lens = ctx.q_mask
         dq, dk, dv, dtc, dta = _bw.attn_bwd(ctx.cfg, q, k, v, out, dout, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k,
-                                            kv_images=ctx.kv_images, want_dtau=want_dtau, key_idx=key_idx, key_lens=key_lens)
-        return (dq, dk, dv, _restore_scalar(dtc, ctx.tc_meta), _restore_scalar(dta, ctx.tau_meta)) + (None,) * 7
+                                            kv_images=ctx.kv_images, want_dtau=want_dtau, key_idx=key_idx, key_lens=key_lens,
+                                            **({} if q_live is None else {"q_live": q_live, "q_lens": q_lens}))
+        return (dq, dk, dv, _restore_scalar(dtc, ctx.tc_meta), _restore_scalar(dta, ctx.tau_meta)) + (None,) * 9
 
 
 class _VarlenAttn(torch.autograd.Function):
@@ -828,7 +867,8 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
                   euclid: bool = False, pretransformed: bool = False, use_dma: bool = True,
                   kv_mode: str = "auto", kv_cache: Optional[dict] = None, precise: Optional[bool] = None,
                   key_views=None, key_lens: Optional[torch.Tensor] = None, key_views_backward: bool = False,
-                  query_views=None, return_lse: bool = False, key_mask: Optional[torch.Tensor] = None, key_mask_backward: bool = False):
+                  query_views=None, return_lse: bool = False, key_mask: Optional[torch.Tensor] = None, key_mask_backward: bool = False,
+                  query_mask: Optional[torch.Tensor] = None):
     """Fused GTA attention on packed reps.  q [B,H,Tq,dh], k/v [B,H,Tk,dh] -> out [B,H,Tq,dh].
 
     kv_mode: 'prepass' = K/V rep pre-pass + lean attention kernel (two launches; at dh = 96 in the MSN layout the attention kernel is
@@ -883,15 +923,32 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
     key_mask_backward: only with ``key_mask``.  False (default): a call with ``key_mask`` under grad raises "forward-only", as it always did.
              True: the call is differentiable in q, k, v, trans_coeff and tau (``gta_attn_fwd_gather`` + ``gta_attn_bwd_gather``; the forward's
              compacted images serve the backward).  dk / dv rows of masked tokens are exactly zero, and nothing of a masked KEY row -- k, v, cs_k,
-             the vrep_k record of a wholly masked view -- is read: it may hold anything, NaN and Inf included.  There is NO query-side mask: in
+             the vrep_k record of a wholly masked view -- is read: it may hold anything, NaN and Inf included.  Without ``query_mask`` (below) there is no query-side mask: in
              self-attention the masked tokens are query rows too, computed as in the forward, and they take part in the backward with whatever
              ``dout`` they get -- so masked QUERY rows (q, cs_q, and the dout that reaches them) must hold finite values; a zero ``dout`` row then
              adds exact zeros to dk / dv.  Still refused, by name: rep tables or poses that require grad (no pose / coordinate gradients under a
              key mask yet), return_lse under grad, kv_cache under grad, precise=True, pretransformed, kv_mode='fused', and the staged and
              rho-apply layouts.
+    query_mask: a bool [B, Tq] tensor (True: the query row is live; None: every row is) -- the query side of ``key_mask``: padded tokens of
+             a self-attention layer, scenes with different numbers of target rays.  A masked (dead) row is never used: its q row, its cs_q
+             row and the vrep_q record of a view without a live row may hold anything, NaN and Inf included, and so may its ``dout`` row in
+             the backward.  It receives exact zeros: out = +0.0 and lse = +0.0 (a later ``gta_attention_merge`` of such rows stays finite),
+             dq = +0.0, and it adds nothing to dk, dv, d trans_coeff or d tau.  A scene may have no live row.  Work items (128 rows)
+             without a live row cost a store of zeros; a dead row inside a live item is computed as a zero row.  The call runs the
+             ``key_mask`` route (``gta_attn_fwd_qmask`` / ``gta_attn_bwd_qmask``) -- without ``key_mask`` under an all-True one, whose index is
+             an arange (no sort) -- and with everything that route refuses: under grad it needs ``key_mask_backward=True``.  Refused by
+             name: ``key_views`` / ``query_views`` / ``key_lens`` / ``key_views_backward`` beside it, ``kv_cache``, and what ``key_mask``
+             refuses.  ``return_lse`` without grad is served.
     """
-    if key_mask_backward and key_mask is None:
+    if key_mask_backward and key_mask is None and query_mask is None:
         raise native.GtaError("key_mask_backward=True comes with key_mask")
+    if query_mask is not None:
+        if key_views is not None or key_lens is not None or key_views_backward or query_views is not None:
+            raise native.GtaError("query_mask with key_views / query_views / key_lens / key_views_backward: a query mask runs on the key_mask "
+                                  "route -- say the valid views as a key_mask (and the valid query rows as the query_mask)")
+        if kv_cache is not None:
+            raise native.GtaError("query_mask with kv_cache: a cache serves later query sets, a query mask belongs to one (no cached query-mask "
+                                  "calls yet)")
     if key_mask is not None and (key_views is not None or key_lens is not None or key_views_backward or query_views is not None):
         raise native.GtaError("key_mask with key_views (or its companions): a call takes one key mask -- a prefix of views is a mask too")
     if query_views is not None and not key_views_backward:
@@ -931,8 +988,11 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
                                   "tables and poses that require grad must be CUDA tensors")
     how = dict(v_transform=v_transform, euclid=euclid, precise=bool(precise), needs_grad=needs_grad, key_views=key_views is not None,
                key_views_backward=bool(key_views_backward))
-    if key_mask is not None:
-        check_key_mask(key_mask, q.shape[0], k.shape[2])
+    if key_mask is not None or query_mask is not None:
+        if key_mask is not None:
+            check_key_mask(key_mask, q.shape[0], k.shape[2])
+        if query_mask is not None:
+            check_query_mask(query_mask, q.shape[0], q.shape[2])
         if key_mask_backward and needs_grad:
             if carriers:
                 raise native.GtaError("key_mask_backward: no pose / coordinate gradients under a key mask yet (gta_rep_grad_sums_varlen knows "
@@ -944,6 +1004,15 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
                                 kv_mode=kv_mode, kv_cache=kv_cache is not None, v_transform=v_transform, euclid=euclid, precise=bool(precise),
                                 needs_grad=needs_grad, key_mask=True, key_mask_backward=bool(key_mask_backward))
         cfg = ({k_: int(v_) for k_, v_ in f_dims.items()}, int(so3_degree), Nq, Nk, float(scale), flags)
+        if query_mask is not None:
+            q_live, q_lens = query_mask_tensors(query_mask, q.device)
+            key_idx, key_lens_m = (_all_keys_tensors(q.shape[0], k.shape[2], q.device) if key_mask is None
+                                   else key_index_tensors(key_mask, q.device))
+            tables = [packed.get(t) for t in ("vrep_q", "vrep_k", "cs_q", "cs_k")]
+            if needs_grad:
+                return _GatherAttn.apply(q, k, v, trans_coeff, tau, cfg, key_idx, key_lens_m, *tables, q_live, q_lens)
+            c = _gather_forward(q, k, v, cfg, packed, trans_coeff, tau, None, None, key_idx=key_idx, key_lens=key_lens_m, q_live=q_live)[0]
+            return (c.out, c.lse) if return_lse else c.out
         if needs_grad:          # (key_mask_backward: anything else was refused above)
             key_idx, key_lens_m = key_index_tensors(key_mask, q.device)
             return _GatherAttn.apply(q, k, v, trans_coeff, tau, cfg, key_idx, key_lens_m, *(packed.get(t) for t in ("vrep_q", "vrep_k", "cs_q", "cs_k")))

@@ -162,6 +162,8 @@ class Attention(nn.Module):
                 raise _gta.native.GtaError("key_views: the elementwise_mul ablation has no per-scene key mask")
             if extras.get("key_mask") is not None:
                 raise _gta.native.GtaError("key_mask: the elementwise_mul ablation has no key mask")
+            if extras.get("query_mask") is not None:
+                raise _gta.native.GtaError("query_mask: the elementwise_mul ablation has no query mask")
             ex = dict(vecrep_q=self.rep_to_vec(extras["flattened_rep_q"]), vecrep_k=self.rep_to_vec(extras["flattened_rep_k"]),
                       vecinvrep_q=self.rep_to_vec(extras["flattened_invrep_q"]))
             out, _ = _gta.multihead_vecrep_attention(q, k, v, attn_fn=self, extras=ex, tau=tau)
@@ -183,6 +185,10 @@ class Attention(nn.Module):
         kvb = bool(extras.get("key_views_backward")) if extras is not None else False
         kmb = bool(extras.get("key_mask_backward")) if extras is not None else False
         query_views = extras.get("query_views") if extras is not None else None
+        # a bool [B, Tq] mask of the live query rows (srt.TransformingSRT's input_mask_queries, self-attention layers): absent by default
+        query_mask = extras.get("query_mask") if extras is not None else None
+        if query_mask is not None and return_attmap:
+            raise _gta.native.GtaError("query_mask with return_attmap: the dense attention map has no query mask")
         packed = _gta.pack_reps(extras, self.f_dims)
         out = _gta.gta_attention(
             q, k, v, self.f_dims, packed,
@@ -192,7 +198,7 @@ class Attention(nn.Module):
             kv_cache=kv_cache, precise=self.precise and q.dtype == torch.float32 and kv_cache is None,
             **({"key_views": key_views} if key_views is not None else {}), **({"key_mask": key_mask} if key_mask is not None else {}),
             **({"key_views_backward": True} if kvb else {}), **({"query_views": query_views} if query_views is not None else {}),
-            **({"key_mask_backward": True} if kmb else {}))
+            **({"key_mask_backward": True} if kmb else {}), **({"query_mask": query_mask} if query_mask is not None else {}))
         out = out.permute(0, 2, 1, 3).reshape(B, Tq, H * dh)              # free: out is [B,Tq,H,dh] in memory
         attn = None
         if return_attmap:                                                  # layers.py:441-442

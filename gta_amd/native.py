@@ -53,6 +53,7 @@ ABI_SYMBOLS = (
     "gta_attn_bwd_dlse", "gta_attn_bwd_dlse_supported", "gta_attn_merge", "gta_attn_merge_bwd",
     "gta_attn_fwd_gather", "gta_attn_fwd_gather_supported",
     "gta_attn_bwd_gather", "gta_attn_bwd_gather_supported",
+    "gta_attn_fwd_qmask", "gta_attn_fwd_qmask_supported", "gta_attn_bwd_qmask", "gta_attn_bwd_qmask_supported",
 )
 MERGE_MAX = 8           # partial attentions per gta_attn_merge call
 
@@ -145,6 +146,9 @@ def lib():
         # gta_attn_fwd_varlen with key_idx ([B, Tk] int32, device) in front of key_lens
         L.gta_attn_fwd_gather.argtypes = [ctypes.POINTER(GtaAttnDesc)] + [c_void_p] * 14 + [c_int64, c_void_p]
         L.gta_attn_fwd_gather_supported.argtypes = [ctypes.POINTER(GtaAttnDesc)]
+        # gta_attn_fwd_gather with q_live ([B, Tq] uint8, device) behind key_lens
+        L.gta_attn_fwd_qmask.argtypes = [ctypes.POINTER(GtaAttnDesc)] + [c_void_p] * 15 + [c_int64, c_void_p]
+        L.gta_attn_fwd_qmask_supported.argtypes = [ctypes.POINTER(GtaAttnDesc)]
         L.gta_attn_fwd_staged_varlen.argtypes = [ctypes.POINTER(GtaAttnDesc)] + [c_void_p] * 15 + [c_int64, c_void_p]
         L.gta_attn_fwd_staged_varlen_supported.argtypes = [ctypes.POINTER(GtaAttnDesc)]
         # gta_attn_bwd with key_lens, q_lens ([B] int32, device; q_lens may be NULL) in front of kv_images
@@ -155,6 +159,10 @@ def lib():
         L.gta_attn_bwd_gather.argtypes = ([ctypes.POINTER(GtaAttnDesc)] + [c_void_p] * 18
                                           + [ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_int64, c_void_p])
         L.gta_attn_bwd_gather_supported.argtypes = [ctypes.POINTER(GtaAttnDesc)]
+        # gta_attn_bwd_gather with q_live ([B, Tq] uint8, device) and q_lens ([B] int32, device; may be NULL) behind key_lens
+        L.gta_attn_bwd_qmask.argtypes = ([ctypes.POINTER(GtaAttnDesc)] + [c_void_p] * 20
+                                         + [ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_int64, c_void_p])
+        L.gta_attn_bwd_qmask_supported.argtypes = [ctypes.POINTER(GtaAttnDesc)]
         # gta_attn_bwd with dlse ([B,H,Tq] fp32, device) behind lse
         L.gta_attn_bwd_dlse.argtypes = ([ctypes.POINTER(GtaAttnDesc)] + [c_void_p] * 17
                                         + [ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_int64, c_void_p])
@@ -335,25 +343,35 @@ def _check_key_lens(key_lens, B: int, device):
         raise GtaError(f"key_lens must be a contiguous int32 tensor of shape ({B},) on {device}")
 
 
+def _check_q_live(q_live, B: int, Tq: int, device):
+    """the storage of a bool [B, Tq] query mask (bool or uint8: one byte per row, non-zero = live)"""
+    if (not torch.is_tensor(q_live) or q_live.dtype not in (torch.bool, torch.uint8) or q_live.device != device or tuple(q_live.shape) != (B, Tq)
+            or not q_live.is_contiguous()):
+        raise GtaError(f"q_live must be a contiguous bool (or uint8) tensor of shape ({B}, {Tq}) on {device}")
+
+
 def _check_key_idx(key_idx, B: int, Tk: int, device):
     if (not torch.is_tensor(key_idx) or key_idx.dtype != torch.int32 or key_idx.device != device or tuple(key_idx.shape) != (B, Tk)
             or not key_idx.is_contiguous()):
         raise GtaError(f"key_idx must be a contiguous int32 tensor of shape ({B}, {Tk}) on {device}")
 
 
-def _fwd_call(entry: str, desc: GtaAttnDesc, qkv, tables, out, lse, workspace, key_lens=None, key_idx=None):
+def _fwd_call(entry: str, desc: GtaAttnDesc, qkv, tables, out, lse, workspace, key_lens=None, key_idx=None, q_live=None):
     """The forward entries: ``tables`` are the float operands between v and out in the entry's order; the *_varlen entries take
     ``key_lens`` ([B] int32 on the device) in front of out, gta_attn_fwd_gather ``key_idx`` ([B, Tk] int32 on the device; None only under
-    FLAG_KV_READY) and ``key_lens``."""
-    _require_cuda(*qkv, out, workspace, key_lens, key_idx)
+    FLAG_KV_READY) and ``key_lens``, gta_attn_fwd_qmask those two and ``q_live`` ([B, Tq] bool / uint8 on the device)."""
+    _require_cuda(*qkv, out, workspace, key_lens, key_idx, q_live)
     lens = ()
-    if entry.endswith("_varlen") or entry.endswith("_gather"):
+    if entry.endswith("_varlen") or entry.endswith("_gather") or entry.endswith("_qmask"):
         _check_key_lens(key_lens, desc.B, workspace.device)
         lens = (_ptr(key_lens),)
-    if entry.endswith("_gather"):
+    if entry.endswith("_gather") or entry.endswith("_qmask"):
         if key_idx is not None or not desc.flags & FLAG_KV_READY:
             _check_key_idx(key_idx, desc.B, desc.Tk, workspace.device)
         lens = (_ptr(key_idx),) + lens
+    if entry.endswith("_qmask"):
+        _check_q_live(q_live, desc.B, desc.Tq, workspace.device)
+        lens = lens + (_ptr(q_live),)
     check(getattr(lib(), entry)(ctypes.byref(desc), *map(_ptr, qkv), *map(_ptr, tables), *lens, _ptr(out), _ptr(lse), _ptr(workspace),
                                 0 if workspace is None else workspace.numel(), _stream()), entry)
 
@@ -376,6 +394,13 @@ def attn_fwd_gather(desc: GtaAttnDesc, q, k, v, vrep_q, vrep_k, cs_q, cs_k, tran
     device, see ``gta.key_index_tensors``): the pre-pass compacts them into the prefix the attention kernel walks.  key_idx may be None
     under FLAG_KV_READY (it is not read)."""
     _fwd_call("gta_attn_fwd_gather", desc, (q, k, v), (vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau), out, lse, workspace, key_lens, key_idx)
+
+
+def attn_fwd_qmask(desc: GtaAttnDesc, q, k, v, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, key_idx, key_lens, q_live, out, lse,
+                   workspace: torch.Tensor):
+    """``attn_fwd_gather`` under a query-side mask: q_live [B, Tq] bool (or uint8) on the device, non-zero = the row is live
+    (``gta.query_mask_tensors``).  Nothing of a dead row is used; its out and lse are written as +0.0."""
+    _fwd_call("gta_attn_fwd_qmask", desc, (q, k, v), (vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau), out, lse, workspace, key_lens, key_idx, q_live)
 
 
 def attn_fwd_staged(desc: GtaAttnDesc, q, k, v, vrep_q, vrep_k, cs_q, cs_k, coord_q, coord_k, trans_coeff, tau, out, lse,
@@ -419,6 +444,11 @@ def attn_fwd_gather_supported(desc: GtaAttnDesc) -> int:
     return lib().gta_attn_fwd_gather_supported(ctypes.byref(desc))
 
 
+def attn_fwd_qmask_supported(desc: GtaAttnDesc) -> int:
+    """0 when gta_attn_fwd_qmask (a key mask and a query mask, fused layouts) serves desc, else a GTA_E_* code; needs no GPU"""
+    return lib().gta_attn_fwd_qmask_supported(ctypes.byref(desc))
+
+
 def attn_fwd_staged_varlen_supported(desc: GtaAttnDesc) -> int:
     return lib().gta_attn_fwd_staged_varlen_supported(ctypes.byref(desc))
 
@@ -450,11 +480,16 @@ def attn_bwd_workspace_bytes(desc: GtaAttnDesc) -> int:
 
 def _bwd_call(entry: str, desc: GtaAttnDesc, q, k, v, out, dout, lse, tables, lens, kv_images, dq, dk, dv, dtrans_coeff, workspace, dtau, dlse=()):
     """The backward entries: ``lens`` is () or (key_lens, q_lens) -- [B] int32 on the device, q_lens may be None --, for gta_attn_bwd_gather
-    (key_idx, key_lens) -- key_idx [B, Tk] int32 on the device; ``dlse`` is () or (dlse,)."""
+    (key_idx, key_lens) -- key_idx [B, Tk] int32 on the device --, for gta_attn_bwd_qmask (key_idx, key_lens, q_live, q_lens) -- q_live [B, Tq]
+    bool / uint8 on the device, q_lens may be None; ``dlse`` is () or (dlse,)."""
     _require_cuda(q, k, v, out, dout, dq, dk, dv, workspace, *lens, *dlse)
-    if entry.endswith("_gather"):
+    if entry.endswith("_gather") or entry.endswith("_qmask"):
         _check_key_idx(lens[0], desc.B, desc.Tk, workspace.device)
         _check_key_lens(lens[1], desc.B, workspace.device)
+        if entry.endswith("_qmask"):
+            _check_q_live(lens[2], desc.B, desc.Tq, workspace.device)
+            if lens[3] is not None:
+                _check_key_lens(lens[3], desc.B, workspace.device)
     else:
         for t in lens[:1] + tuple(t for t in lens[1:] if t is not None):
             _check_key_lens(t, desc.B, workspace.device)
@@ -549,6 +584,20 @@ def attn_bwd_gather(desc: GtaAttnDesc, q, k, v, out, dout, lse, vrep_q, vrep_k, 
     [0, Tk) with the key_lens[b] valid tokens first (``gta.key_index_tensors``) -- dk / dv of the valid tokens land in their rows, the rows of
     the masked tokens are written as zeros.  kv_images: the workspace of ``attn_fwd_gather`` under the same key_idx / key_lens, or None."""
     _bwd_call("gta_attn_bwd_gather", desc, q, k, v, out, dout, lse, (vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau), (key_idx, key_lens),
+              kv_images, dq, dk, dv, dtrans_coeff, workspace, dtau)
+
+
+def attn_bwd_qmask_supported(desc: GtaAttnDesc) -> int:
+    """0 when gta_attn_bwd_qmask (the backward under a key mask and a query mask) serves desc, else a GTA_E_* code; needs no GPU"""
+    return lib().gta_attn_bwd_qmask_supported(ctypes.byref(desc))
+
+
+def attn_bwd_qmask(desc: GtaAttnDesc, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, key_idx, key_lens, q_live, q_lens,
+                   kv_images, dq, dk, dv, dtrans_coeff, workspace, dtau=None):
+    """``attn_bwd_gather`` under the query-side mask of ``attn_fwd_qmask``: q_live [B, Tq] bool / uint8 on the device, q_lens [B] int32 (1 + the
+    last live row, 0 for none: ``gta.query_mask_tensors``) or None.  Nothing of a dead row is used -- q, cs_q, out, dout, lse --, its dq row
+    is written as +0.0 and it adds nothing to dk, dv, dtrans_coeff or dtau."""
+    _bwd_call("gta_attn_bwd_qmask", desc, q, k, v, out, dout, lse, (vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau), (key_idx, key_lens, q_live, q_lens),
               kv_images, dq, dk, dv, dtrans_coeff, workspace, dtau)
 
 

@@ -84,9 +84,22 @@ class ImprovedSRTEncoder(nn.Module):
         extras = {} if extras is None else extras
         B, N = images.shape[:2]
         pre_compute_reps_encoder(self.attn_args, extras)            # HIP: inverse, Wigner-D, SO(2) table
+        # (TransformingSRT's input_mask_queries) the masked tokens are dead query rows of every self-attention layer.  The attention is not
+        # the only sum over tokens: a weight gradient of a token-wise layer (LayerNorm, the projections, the MLP, the convolutions) is a sum
+        # over ALL rows, and 0 * NaN is not 0 -- so the images of a view without a live token and the masked tokens are SELECTED away here
+        query_mask = extras.get("query_mask")
+        if query_mask is not None:
+            if tuple(query_mask.shape[:1]) != (B,) or query_mask.shape[1] % N:
+                raise native.GtaError(f"query_mask has shape {tuple(query_mask.shape)} for {B} scenes of {N} views")
+            view_live = query_mask.view(B, N, -1).any(-1)
+            images = torch.where(view_live[:, :, None, None, None], images, torch.zeros((), dtype=images.dtype, device=images.device))
         x = self.per_patch_linear(self.conv_blocks(images.flatten(0, 1)))
         x = x.flatten(2, 3).permute(0, 2, 1)                        # [B*N, h*w, attdim]
         x = x.reshape(B, N * x.shape[1], x.shape[2])                # view-major tokens
+        if query_mask is not None:
+            if query_mask.shape[1] != x.shape[1]:
+                raise native.GtaError(f"query_mask has {query_mask.shape[1]} tokens per scene, the encoder {x.shape[1]}")
+            x = torch.where(query_mask[:, :, None], x, torch.zeros((), dtype=x.dtype, device=x.device))
         x = self.lin_out(self.transformer(x, None, extras))
         if self.output_scaler:
             extras["scaler"] = self.scaler
@@ -173,7 +186,7 @@ class TransformingSRT(nn.Module):
         return self.decoder(z, x, rays, extras)
 
     def forward(self, input_images, input_camera_pos, input_rays, target_camera_pos, target_rays, extras=None, input_views=None,
-                input_views_backward=False, input_mask=None, input_mask_backward=False):
+                input_views_backward=False, input_mask=None, input_mask_backward=False, input_mask_queries=False):
         """``input_views``: per-scene numbers of valid input views (a host sequence of length B, each in 1..N) for batches that mix
         view counts: scene b's first ``input_views[b]`` views are its input, the rest of its [N, ...] slots is padding that no valid
         token ever attends to -- in the encoder's self-attention and in the decoder's cross-attention (``gta_attention``'s
@@ -188,12 +201,22 @@ class TransformingSRT(nn.Module):
         masked one, in the encoder's self-attention and in the decoder's cross-attention (``gta_attention``'s ``key_mask``); the scene
         tokens of masked positions are still computed and unspecified.  Not together with ``input_views``.  Inference only unless
         ``input_mask_backward=True``: every layer then runs the differentiable route (``key_mask_backward``; fused layouts, no pose or
-        coordinate gradients).  There is no query-side mask: in the encoder's self-attention the masked tokens are query rows too and take
-        part in the backward, so the inputs at masked positions must be finite (zero-filled padding is); nothing of a masked token reaches
-        a valid one as a KEY."""
+        coordinate gradients).  Without ``input_mask_queries`` there is no query-side mask: in the encoder's self-attention the masked
+        tokens are query rows too and take part in the backward, so the inputs at masked positions must be finite (zero-filled padding is);
+        nothing of a masked token reaches a valid one as a KEY.
+
+        ``input_mask_queries``: only with ``input_mask``.  False (default): the behaviour above, bit for bit.  True: the encoder's
+        self-attention layers also get ``query_mask`` = the key mask (``gta_attention``'s ``query_mask``): a masked token is a dead query row
+        -- never read, its attention output and gradient exact zeros, work items without a live row skipped --, and the encoder selects
+        the masked tokens (and the images of a view without a live token) away before its token-wise layers, whose weight gradients sum
+        over all rows.  The inputs of wholly masked views may then hold anything, NaN and Inf included; the pixels of a partly masked view
+        still pass the convolutions and must be finite.  The scene tokens of masked positions are unspecified but finite.  The decoder's
+        queries are the target rays, all live: the mask is taken out of the copy of ``extras`` before it."""
         extras = {} if extras is None else extras
         if input_mask_backward and input_mask is None:
             raise native.GtaError("input_mask_backward=True comes with input_mask")
+        if input_mask_queries and input_mask is None:
+            raise native.GtaError("input_mask_queries=True comes with input_mask")
         if input_mask is not None:
             if input_views is not None:
                 raise native.GtaError("input_mask with input_views: a call takes one key mask -- a prefix of views is a mask too")
@@ -201,6 +224,8 @@ class TransformingSRT(nn.Module):
             extras["key_mask"] = _token_mask(input_mask)
             if input_mask_backward:
                 extras["key_mask_backward"] = True
+            if input_mask_queries:
+                extras["query_mask"] = extras["key_mask"]      # (the encoder's layers: Tq = Tk, the same tokens on both sides)
         if input_views is not None:
             extras = dict(extras)                      # the caller's dict never carries these counts into a later call (as render_image)
             extras["key_views"] = input_views
@@ -210,6 +235,8 @@ class TransformingSRT(nn.Module):
         z, extras = self.encoder(input_images, input_camera_pos, input_rays, extras)
         if input_views is not None and input_views_backward:
             extras = {k_: v_ for k_, v_ in extras.items() if k_ != "query_views"}      # the decoder's queries are the target rays: all live
+        if input_mask_queries:
+            extras = {k_: v_ for k_, v_ in extras.items() if k_ != "query_mask"}       # (likewise)
         return self.decode(z, target_camera_pos, target_rays, extras=extras)
 
 

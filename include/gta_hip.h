@@ -215,7 +215,7 @@ int gta_attn_bwd_varlen(const GtaAttnDesc* desc,
                         void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Backward over any per-scene subset of the key tokens (gta_attention's key_mask with key_mask_backward): the backward of
- * gta_attn_fwd_gather.  It is gta_attn_bwd_varlen without q_lens (there is no query-side mask: every query row is live and must hold finite
+ * gta_attn_fwd_gather.  It is gta_attn_bwd_varlen without q_lens (this entry has no query-side mask -- gta_attn_bwd_qmask has --: every query row is live and must hold finite
  * values) whose dK/dV walk runs in GATHER instances: the walk over the compacted K'/V' images is the VARLEN walk, and the epilogue reads the
  * token of a compacted row from key_idx -- that token gives the view record, the cs_k row, the raw K / V row of the dtrans_coeff term and the
  * row of dk / dv that is written.  The dQ walk and the q-side pre-pass are the VARLEN kernels as they are.
@@ -380,6 +380,52 @@ int gta_attn_fwd_gather(const GtaAttnDesc* desc, const void* q, const void* k, c
                         const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
                         const float* trans_coeff, const float* tau, const int32_t* key_idx, const int32_t* key_lens, void* out, float* lse,
                         void* workspace, int64_t workspace_bytes, void* stream);
+
+/* A query-side mask beside the key mask (gta_attention's query_mask): gta_attn_fwd_gather whose attention step runs in the QMASK twins of the
+ * VARLEN gta_fwd2_kernel instances (every layout, head size and input type those exist for; one workgroup per work item).
+ *   q_live: [B, Tq] uint8 on the device (the storage of a bool tensor), non-zero = the query row is live.  NULL: GTA_E_BADARG.
+ *   A row (b, t) is live iff q_live[b, t] is set.  A dead row is never used: its q row, its cs_q row and the vrep_q record of a view without a
+ *       live row may hold anything, NaN and Inf included (the rows are loaded -- they must be readable memory -- and struck behind rho_q;
+ *       vrep_q records are loaded with the others and must be readable memory too).  A dead row is written as zeros: out = +0.0 in every
+ *       channel and lse = +0.0, so a later gta_attn_merge of such rows stays finite.  A scene may have no live row.
+ *   A 128-row work item without a live row stores those zeros and ends before it requests a key tile or loads a query row; in a live item
+ *       a dead row is computed as the row q' = 0 (to the wave-wide decisions of the lazy softmax it is the row a zero q row gives: the live
+ *       rows' out and lse are bit for bit those of gta_attn_fwd_gather on the same data with the dead q rows set to zero).
+ *   GTA_FLAG_PREP_ONLY: GTA_E_BADARG (the pre-pass knows no query mask: gta_attn_fwd_gather builds the images).  GTA_FLAG_KV_READY: as in
+ *       gta_attn_fwd_gather.
+ *   gta_attn_fwd_qmask_supported: what gta_attn_fwd_gather_supported answers.
+ *   Every other argument, check and error code: as in gta_attn_fwd_gather. */
+int gta_attn_fwd_qmask_supported(const GtaAttnDesc* desc);
+int gta_attn_fwd_qmask(const GtaAttnDesc* desc, const void* q, const void* k, const void* v,
+                       const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
+                       const float* trans_coeff, const float* tau, const int32_t* key_idx, const int32_t* key_lens,
+                       const uint8_t* q_live, void* out, float* lse,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+
+/* The backward of gta_attn_fwd_qmask (gta_attention's query_mask with key_mask_backward): gta_attn_bwd_gather with a query-side mask.  The
+ * q-side pre-pass and the dQ walk run in QMASK instances; the dK/dV walk is the GATHER one as it is, under q_lens.
+ *   q_live: as in gta_attn_fwd_qmask; NULL: GTA_E_BADARG.
+ *   q_lens: [B] int32 on the device, 1 + the index of scene b's last live row (0 for a scene without one; the kernels clamp it to 1), or
+ *       NULL = Tq.  It lets the dK/dV walk skip the query tiles behind the last live row; a larger value costs time, not correctness.
+ *   A row (b, t) is live iff t < q_lens[b] and q_live[b, t] is set.  A dead row is never used: its q, cs_q, out, dout and lse entries may hold
+ *       anything, NaN and Inf included, and so may the vrep_q record of a view without a live row (records are loaded with the others and
+ *       must be readable memory).  Its dq row is written as +0.0 in every channel, and it adds nothing to dk, dv, dtrans_coeff or dtau: its
+ *       rows of the Q'' / dO~ images are zero and its statistics (-1e30, 0), so P = 0 and dS = 0 for it in both walks.  A 128-row block of
+ *       the dQ walk without a live row stores zeros and ends.  Every output is bit for bit that of gta_attn_bwd_gather on the same data with
+ *       the dead rows of q and dout set to zero (dq at the live rows).
+ *   gta_attn_bwd_qmask_supported: what gta_attn_bwd_gather_supported answers.
+ *   Every other argument, check and error code: as in gta_attn_bwd_gather. */
+int gta_attn_bwd_qmask_supported(const GtaAttnDesc* desc);
+int gta_attn_bwd_qmask(const GtaAttnDesc* desc,
+                       const void* q, const void* k, const void* v, const void* out, const void* dout,
+                       const float* lse,
+                       const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
+                       const float* trans_coeff, const float* tau,
+                       const int32_t* key_idx, const int32_t* key_lens, const uint8_t* q_live, const int32_t* q_lens,
+                       const void* kv_images,
+                       void* dq, void* dk, void* dv, const int64_t* dqkv_stride, const int64_t* dout_stride,
+                       float* dtrans_coeff, float* dtau,
+                       void* workspace, int64_t workspace_bytes, void* stream);
 
 /* -------------------------------------------------------------------------------------------
  * Gradients of the reps: camera poses and patch coordinates (what autograd over gta.py:134-279 gives the reference's

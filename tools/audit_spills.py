@@ -29,7 +29,9 @@ def audit():
     for m in re.finditer(r"^(_ZN\w*gta_fwd2_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)ELb(\d)E\w+):", text, re.M):
         x3 = m.group(5) == "1"          # the fp32-faithful instances (split-bf16 operands): two workgroups per CU, 256 registers
         varlen = m.group(6) == "1"      # the instances with per-scene key prefixes (gta_attn_fwd_varlen): held to the rules of their twins
-        name, key = m.group(1), (int(m.group(2)), int(m.group(3)), int(m.group(4))) + (("x3",) if x3 else ()) + (("varlen",) if varlen else ())
+        qmask = "ELb1EJPKhEE" in m.group(1)    # the VARLEN instances with the trailing q_live argument (gta_attn_fwd_qmask): held to their VARLEN twins
+        name, key = m.group(1), ((int(m.group(2)), int(m.group(3)), int(m.group(4))) + (("x3",) if x3 else ()) + (("varlen",) if varlen else ())
+                                 + (("qmask",) if qmask else ()))
         body = text[m.start():text.index(".Lfunc_end", m.start())]
         meta = text[text.index(".amdhsa_kernel " + name):][:4000]
         vgpr = int(re.search(r"\.amdhsa_next_free_vgpr\s+(\d+)", meta).group(1))
@@ -48,6 +50,20 @@ def audit():
     for key, n in scratch.items():
         if key[-1] == "varlen" and key[:-1] in scratch and n > scratch[key[:-1]]:
             problems.append(f"gta_fwd2_kernel<{key}> has {n} scratch accesses, its twin without VARLEN {scratch[key[:-1]]}")
+    # a QMASK instance by the same rule against its VARLEN twin, and it keeps the twin's occupancy (waves per SIMD the registers allow: the mask
+    # must not live through the tile loop); one QMASK instance per VARLEN one
+    vgprs = {r["instance"]: r["vgpr"] for r in report}
+    waves = lambda v: min(8, 512 // ((v + 7) // 8 * 8))
+    for key, n in scratch.items():
+        if key[-1] == "qmask":
+            twin = key[:-1]
+            if twin not in scratch or n > scratch[twin]:
+                problems.append(f"gta_fwd2_kernel<{key}> has {n} scratch accesses, its VARLEN twin {scratch.get(twin)}")
+            elif waves(vgprs[key]) < waves(vgprs[twin]):
+                problems.append(f"gta_fwd2_kernel<{key}> needs {vgprs[key]} VGPRs, its VARLEN twin {vgprs[twin]}: fewer waves per SIMD")
+    n_qmask, n_varlen = sum(1 for k in scratch if k[-1] == "qmask"), sum(1 for k in scratch if k[-1] == "varlen")
+    if n_qmask != n_varlen:
+        problems.append(f"{n_qmask} QMASK instances of gta_fwd2_kernel for {n_varlen} VARLEN ones")
     # the dh = 64 bf16 instance (gta_fwd_cl.hip, r06): three workgroups per CU, no scratch anywhere
     text = _asm("gta_fwd_cl.hip", ("-fno-slp-vectorize",))
     for name, (layout,), body, vgpr in _kernels(text, r"gta_fwdc_kernelILi(\d+)E"):
@@ -114,6 +130,8 @@ def audit_others():
     for kern in ("gta_bwd_prep", "gta_bwd_dq", "gta_bwd_dkv"):
         pattern = r"_kernelILi(\d+)ELi(\d+)ELb0ELb1E" if kern == "gta_bwd_prep" else r"_varlen_kernelILi(\d+)ELi(\d+)E"
         for name, (dhp, esz), body, vgpr in _kernels(text, kern + pattern):
+            if "JPKiPKhEE" in name:                     # the pre-pass's QMASK instances <dhp, esz, false, true, q_lens, q_live>: below
+                continue
             row = {"kernel": f"{kern}_varlen_kernel<{dhp},{esz}>", "vgpr": vgpr, "scratch": body.count("scratch_")}
             report.append(row)
             twin = bwd_scratch.get((kern + "_kernel", dhp, esz))
@@ -131,6 +149,19 @@ def audit_others():
             problems.append(f"{row['kernel']} has {row['scratch']} scratch accesses, its VARLEN twin {twin}")
     if n_gather != len(varlen_scratch):
         problems.append(f"{n_gather} GATHER instances of the dK/dV walk for {len(varlen_scratch)} VARLEN ones")
+    # the QMASK instances of the pre-pass and of the dQ walk (gta_attn_bwd_qmask) by the same rule against their VARLEN twins, one per twin
+    for kern, pattern in (("gta_bwd_prep", r"gta_bwd_prep_kernelILi(\d+)ELi(\d+)ELb0ELb1EJPKiPKhEE"), ("gta_bwd_dq", r"gta_bwd_dq_qmask_kernelILi(\d+)ELi(\d+)E")):
+        twins = {r["kernel"]: r["scratch"] for r in report if r["kernel"].startswith(kern + "_varlen_kernel<")}
+        n_qmask = 0
+        for name, (dhp, esz), body, vgpr in _kernels(text, pattern):
+            row = {"kernel": f"{kern}_qmask_kernel<{dhp},{esz}>", "vgpr": vgpr, "scratch": body.count("scratch_")}
+            report.append(row)
+            n_qmask += 1
+            twin = twins.get(f"{kern}_varlen_kernel<{dhp},{esz}>")
+            if twin is None or row["scratch"] > twin:
+                problems.append(f"{row['kernel']} has {row['scratch']} scratch accesses, its VARLEN twin {twin}")
+        if n_qmask != len(twins):
+            problems.append(f"{n_qmask} QMASK instances of {kern} for {len(twins)} VARLEN ones")
     # the DLSE instances of the pre-pass (gta_attn_bwd_dlse) by the same rule against the twin without dlse, X3 ones against the X3 twin
     prep = {}
     for name, (dhp, esz, x3), body, vgpr in _kernels(text, r"gta_bwd_prep_kernelILi(\d+)ELi(\d+)ELb(\d)ELb0EJ"):
