@@ -739,16 +739,19 @@ extern "C" int64_t gta_rep_grad_workspace_bytes(const GtaAttnDesc* d, int32_t si
     return (int64_t)d->B * N * chunks * 16 * (int64_t)sizeof(float);
 }
 
-// both sums entries.  varlen (gta_rep_grad_sums_varlen) is the explicit selector of the VARLEN instances -- never "lens is non-null"
+// the three sums entries.  varlen (gta_rep_grad_sums_varlen) and masked (gta_rep_grad_sums_masked) are the explicit selectors of the
+// VARLEN / MASKED instances -- never "lens (live) is non-null"
 static int rep_grad_call(const GtaAttnDesc* d, int32_t side, int32_t n_pairs,
                          const void* a0, const int64_t* a0_stride, const void* b0, const int64_t* b0_stride,
                          const void* a1, const int64_t* a1_stride, const void* b1, const int64_t* b1_stride,
-                         bool varlen, const int32_t* lens, float* view_sums, float* so2_sums, float* t2_sums,
+                         bool varlen, const int32_t* lens, bool masked, const uint8_t* live,
+                         float* view_sums, float* so2_sums, float* t2_sums,
                          void* workspace, int64_t workspace_bytes, void* stream) {
     int T, N, tpb;
     long chunks;
     if (int rc = repgrad_geometry(d, side, T, N, tpb, chunks)) return rc;
     if (varlen && !lens) return fail(GTA_E_BADARG, "null lens");
+    if (masked && !live) return fail(GTA_E_BADARG, "null live");
     if (d->dtype != GTA_DTYPE_F32 && d->dtype != GTA_DTYPE_BF16) return fail(GTA_E_BADARG, "dtype must be GTA_DTYPE_F32 or GTA_DTYPE_BF16");
     if (n_pairs != 1 && n_pairs != 2) return fail(GTA_E_BADARG, "n_pairs must be 1 or 2");
     if (!view_sums && !so2_sums && !t2_sums) return fail(GTA_E_BADARG, "no output requested");
@@ -784,6 +787,7 @@ static int rep_grad_call(const GtaAttnDesc* d, int32_t side, int32_t n_pairs,
     p.n_t2 = t2_sums ? d->d_t2 / 3 : 0;
     p.part = (float*)workspace; p.view_out = view_sums; p.so2_out = so2_sums; p.t2_out = t2_sums;
     p.lens = varlen ? lens : nullptr;
+    p.live = masked ? live : nullptr;
     return launch_status(gta_repgrad_dispatch(p, esz, euclid, (hipStream_t)stream), "grid too large");
 }
 
@@ -792,7 +796,7 @@ extern "C" int gta_rep_grad_sums(const GtaAttnDesc* d, int32_t side, int32_t n_p
                                  const void* a1, const int64_t* a1_stride, const void* b1, const int64_t* b1_stride,
                                  float* view_sums, float* so2_sums, float* t2_sums,
                                  void* workspace, int64_t workspace_bytes, void* stream) {
-    return rep_grad_call(d, side, n_pairs, a0, a0_stride, b0, b0_stride, a1, a1_stride, b1, b1_stride, false, nullptr,
+    return rep_grad_call(d, side, n_pairs, a0, a0_stride, b0, b0_stride, a1, a1_stride, b1, b1_stride, false, nullptr, false, nullptr,
                          view_sums, so2_sums, t2_sums, workspace, workspace_bytes, stream);
 }
 
@@ -801,6 +805,15 @@ extern "C" int gta_rep_grad_sums_varlen(const GtaAttnDesc* d, int32_t side, int3
                                         const void* a1, const int64_t* a1_stride, const void* b1, const int64_t* b1_stride,
                                         const int32_t* lens, float* view_sums, float* so2_sums, float* t2_sums,
                                         void* workspace, int64_t workspace_bytes, void* stream) {
-    return rep_grad_call(d, side, n_pairs, a0, a0_stride, b0, b0_stride, a1, a1_stride, b1, b1_stride, true, lens,
+    return rep_grad_call(d, side, n_pairs, a0, a0_stride, b0, b0_stride, a1, a1_stride, b1, b1_stride, true, lens, false, nullptr,
+                         view_sums, so2_sums, t2_sums, workspace, workspace_bytes, stream);
+}
+
+extern "C" int gta_rep_grad_sums_masked(const GtaAttnDesc* d, int32_t side, int32_t n_pairs,
+                                        const void* a0, const int64_t* a0_stride, const void* b0, const int64_t* b0_stride,
+                                        const void* a1, const int64_t* a1_stride, const void* b1, const int64_t* b1_stride,
+                                        const uint8_t* live, float* view_sums, float* so2_sums, float* t2_sums,
+                                        void* workspace, int64_t workspace_bytes, void* stream) {
+    return rep_grad_call(d, side, n_pairs, a0, a0_stride, b0, b0_stride, a1, a1_stride, b1, b1_stride, false, nullptr, true, live,
                          view_sums, so2_sums, t2_sums, workspace, workspace_bytes, stream);
 }

@@ -8,6 +8,7 @@
 // Only the channels of the requested slabs are read.  No float atomics: per-token sums are finished inside the workgroup in head order,
 // per-view sums leave one partial per workgroup and gta_repgrad_finish_kernel adds them in workgroup order -- two runs, same bits.
 // With per-scene prefixes (gta_rep_grad_sums_varlen, batches that mix view counts) the VARLEN twins skip what lies past a scene's prefix.
+// With a per-token liveness byte (gta_rep_grad_sums_masked, key / query masks) the MASKED twins skip every dead row, wherever it lies.
 #include "gta_common.h"
 #include "gta_repgrad_params.h"
 #include "../../include/gta_hip.h"
@@ -42,8 +43,13 @@ GTA_DEV float head_sum(const float* red, int k, int tl, int H) {
 // VARLEN (gta_rep_grad_sums_varlen): a row at or past its scene's prefix p.lens[b] is dead -- never loaded, exact zero in every sum; a
 // workgroup wholly past the prefix writes +0.0 to its partial and to its per-token outputs and returns (uniform over the workgroup).
 // What is live runs the statements of the instance without VARLEN in the same order: the same bits.
-template <int ESZ, bool EUCLID, bool VEC, bool VARLEN = false>
+// MASKED (gta_rep_grad_sums_masked; the instances with the trailing `const uint8_t*`): a row is live when its token's byte of p.live
+// [B, T] is non-zero -- the same never-read / exact-zero rule per row.  A workgroup is dead when NONE of its ntok tokens is live, decided
+// by one OR over the workgroup (a ballot per wave, the four words through the LDS): its first token says nothing about the others.
+template <int ESZ, bool EUCLID, bool VEC, bool VARLEN = false, typename... LIVE>
 __global__ __launch_bounds__(NT) void gta_repgrad_kernel(const GtaRepGradParams p) {
+    constexpr bool MASKED = sizeof...(LIVE) == 1;
+    static_assert(sizeof...(LIVE) <= 1 && !(MASKED && VARLEN), "a launch has prefixes or a mask, not both");
     __shared__ float red[SO2_PASS * 4 * NT];
     const int tid = threadIdx.x;
     const int wg = blockIdx.x;
@@ -64,7 +70,25 @@ __global__ __launch_bounds__(NT) void gta_repgrad_kernel(const GtaRepGradParams 
         }
         nlive = min(ntok, len - t0);                           // a workgroup that straddles the prefix: its tail adds zeros
     }
-    const bool live = tl < nlive;
+    bool live = tl < nlive;
+    if (MASKED) {
+        live = tl < ntok && p.live[(long)b * p.T + t0 + tl] != 0;
+        uint32_t* any = reinterpret_cast<uint32_t*>(red);
+        const unsigned long long wave_live = __ballot(live);
+        if (tid % 64 == 0) any[tid / 64] = wave_live != 0ull;
+        __syncthreads();
+        uint32_t wg_live = 0;
+#pragma unroll
+        for (int w = 0; w < NT / 64; ++w) wg_live |= any[w];
+        if (!wg_live) {                                        // a dead workgroup (uniform): nothing loaded, every word it owns is +0.0
+            if (p.n_se3 > 0 && tid < 16) p.part[(long)wg * 16 + tid] = 0.f;
+            for (int e = tid; e < ntok * p.n_so2 * 4; e += NT) p.so2_out[(long)(b * p.T + t0) * p.n_so2 * 4 + e] = 0.f;
+            if (p.n_t2 > 0)
+                for (int e = tid; e < ntok * 9; e += NT) p.t2_out[(long)(b * p.T + t0) * 9 + e] = 0.f;
+            return;
+        }
+        __syncthreads();                                       // (red is the reduction array from here on)
+    }
     const int t = t0 + (live ? tl : 0);
     const char* ar[2];
     const char* br[2];
@@ -259,14 +283,32 @@ void launch_varlen(const GtaRepGradParams& p, int esz, bool euclid, dim3 grid, d
     }
 }
 
+// the MASKED twin of each instance, selected the same way
+void launch_masked(const GtaRepGradParams& p, int esz, bool euclid, dim3 grid, dim3 block, hipStream_t stream) {
+    using M = const uint8_t*;
+    if (vec_ok(p, esz, euclid)) {
+        if (esz == 2) hipLaunchKernelGGL((gta_repgrad_kernel<2, false, true, false, M>), grid, block, 0, stream, p);
+        else          hipLaunchKernelGGL((gta_repgrad_kernel<4, false, true, false, M>), grid, block, 0, stream, p);
+    } else if (esz == 2) {
+        if (euclid) hipLaunchKernelGGL((gta_repgrad_kernel<2, true, false, false, M>), grid, block, 0, stream, p);
+        else        hipLaunchKernelGGL((gta_repgrad_kernel<2, false, false, false, M>), grid, block, 0, stream, p);
+    } else {
+        if (euclid) hipLaunchKernelGGL((gta_repgrad_kernel<4, true, false, false, M>), grid, block, 0, stream, p);
+        else        hipLaunchKernelGGL((gta_repgrad_kernel<4, false, false, false, M>), grid, block, 0, stream, p);
+    }
+}
+
 }  // namespace
 
+// p.live != nullptr selects the MASKED instances (gta_rep_grad_sums_masked refuses a NULL live before it comes here), else
 // p.lens != nullptr selects the VARLEN instances (gta_rep_grad_sums_varlen refuses a NULL lens before it comes here)
 int gta_repgrad_dispatch(const GtaRepGradParams& p, int esz, bool euclid, hipStream_t stream) {
     const long nwg = (long)p.B * p.N * p.chunks;
     if (nwg <= 0 || nwg > 0x7fffffffL) return GTA_E_UNSUPPORTED;
     const dim3 grid((unsigned)nwg), block(NT);
-    if (p.lens) {
+    if (p.live) {
+        launch_masked(p, esz, euclid, grid, block, stream);
+    } else if (p.lens) {
         launch_varlen(p, esz, euclid, grid, block, stream);
     } else if (vec_ok(p, esz, euclid)) {
         if (esz == 2) hipLaunchKernelGGL((gta_repgrad_kernel<2, false, true>), grid, block, 0, stream, p);

@@ -19,6 +19,7 @@ struct GtaRepGradParams {
     float* so2_out;                   // [B*T][n_so2][4]
     float* t2_out;                    // [B*T][9]
     const int32_t* lens;              // [B] valid tokens of this side per scene (clamped to 1..T): the VARLEN instances; nullptr: every row is live
+    const uint8_t* live;              // [B, T] one byte per token of this side, non-zero = live: the MASKED instances; nullptr: not masked
 };
 
 constexpr int GTA_REPGRAD_THREADS = 256;

@@ -653,6 +653,18 @@ def key_index_tensors(key_mask: torch.Tensor, device) -> Tuple[torch.Tensor, tor
     return idx.contiguous().to(device, non_blocking=True), lens.to(device, non_blocking=True)
 
 
+def effective_key_mask(key_mask: torch.Tensor, device, unvalidated: Optional[bool] = None) -> torch.Tensor:
+    """The key mask the kernels act on, bool [B, Tk] on ``device``: what the rep-gradient pass (``gta_rep_grad_sums_masked``) must see.
+    Under a CUDA mask a scene with NO valid key attends its token 0 (``key_index_tensors``: the count is clamped to 1 and the first index of
+    an all-false row is 0), so token 0 of such a scene is live here too -- set on the device, without a sync.  A CPU mask was validated to
+    have a valid key in every scene: it is uploaded as it is.  ``unvalidated``: whether the mask's values were not looked at (None: a CUDA
+    mask)."""
+    live = key_mask.to(device, non_blocking=True).clone()
+    if key_mask.is_cuda if unvalidated is None else unvalidated:
+        live[:, 0] |= ~live.any(1)
+    return live.contiguous()
+
+
 def check_query_mask(query_mask, B: Optional[int] = None, Tq: Optional[int] = None):
     """Validation of a query mask: a bool [B, Tq] tensor (the shape is held against B and Tq where given).  Its values are not looked at: a
     scene may have no live query row at all."""
@@ -772,18 +784,23 @@ def _gather_forward(q, k, v, cfg, tables, trans_coeff, tau, key_mask, kv_cache=N
 class _GatherAttn(torch.autograd.Function):
     """The fused layouts with a key mask under grad (``key_mask_backward=True``): the forward of ``_gather_forward``, whose workspace (the compacted
     K'/V' tile images) and LSE serve ``gta_attn_bwd_gather`` under the same ``key_idx`` / ``key_lens`` (``key_index_tensors``: every row a
-    permutation, the valid tokens first).  Gradients: q, k, v, trans_coeff, tau -- as ``_GtaAttn``; dk / dv rows of masked tokens are zeros.  No
-    gradients of the tables (refused before the call gets here).  ``q_live`` / ``q_lens`` (``query_mask_tensors``; both or neither): the same
-    two tensors go to ``gta_attn_fwd_qmask`` and ``gta_attn_bwd_qmask`` -- dq rows of dead rows are zeros; without them the two gather
-    entries run as before."""
+    permutation, the valid tokens first).  Gradients: q, k, v, trans_coeff, tau -- as ``_GtaAttn``; dk / dv rows of masked tokens are zeros.
+    ``q_live`` / ``q_lens`` (``query_mask_tensors``; both or neither): the same two tensors go to ``gta_attn_fwd_qmask`` and
+    ``gta_attn_bwd_qmask`` -- dq rows of dead rows are zeros; without them the two gather entries run as before.
+    With ``carriers`` (``key_mask_rep_grad=True``; as in ``_VarlenAttn``) the tables' gradients too: the pass of gta_amd/repgrad.py over the
+    live tokens alone (``gta_rep_grad_sums_masked``) under ``k_live`` (the effective key mask, bool [B, Tk] on the device; None: every key
+    is live) and ``q_live`` (None: every query row is) -- exact zeros for views without a live token and for dead tokens."""
 
     @staticmethod
-    def forward(ctx, q, k, v, trans_coeff, tau, cfg, key_idx, key_lens, vrep_q, vrep_k, cs_q, cs_k, q_live=None, q_lens=None):
+    def forward(ctx, q, k, v, trans_coeff, tau, cfg, key_idx, key_lens, vrep_q, vrep_k, cs_q, cs_k, q_live=None, q_lens=None, k_live=None,
+                *carriers):
         c, ws = _gather_forward(q, k, v, cfg, dict(vrep_q=vrep_q, vrep_k=vrep_k, cs_q=cs_q, cs_k=cs_k), trans_coeff, tau, None,
                                 key_idx=key_idx, key_lens=key_lens, q_live=q_live)
         ctx.cfg = cfg
         ctx.kv_images = ws
         ctx.q_mask = (q_live, q_lens)          # (the objects themselves: they need no gradient and the backward hands them on as they are)
+        ctx.k_live = k_live
+        ctx.carriers = _repgrad.carrier_meta(carriers)
         ctx.save_for_backward(c.q, c.k, c.v, c.out, c.lse, c.tc, c.ta, vrep_q, vrep_k, cs_q, cs_k, key_idx, key_lens)
         ctx.tc_meta, ctx.tau_meta = _scalar_meta(trans_coeff), _scalar_meta(tau)
         return c.out
@@ -797,7 +814,18 @@ class _GatherAttn(torch.autograd.Function):
         dq, dk, dv, dtc, dta = _bw.attn_bwd(ctx.cfg, q, k, v, out, dout, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k,
                                             kv_images=ctx.kv_images, want_dtau=want_dtau, key_idx=key_idx, key_lens=key_lens,
                                             **({} if q_live is None else {"q_live": q_live, "q_lens": q_lens}))
-        return (dq, dk, dv, _restore_scalar(dtc, ctx.tc_meta), _restore_scalar(dta, ctx.tau_meta)) + (None,) * 9
+        grads = ()
+        if ctx.carriers:
+            # gradients of the tables over the live tokens: (q, dq), (dout, out) under q_live (every row without it), (dk, k), (dv, v) under k_live
+            meta = tuple(m if need else None for m, need in zip(ctx.carriers, ctx.needs_input_grad[15:]))
+            f_dims, so3_degree, Nq, Nk, scale, flags = ctx.cfg
+            desc = native.make_desc(q, k, v, out, f_dims, so3_degree, Nq, Nk, scale, flags)
+            do = _as_kernel_layout(dout.to(q.dtype))
+            vt = bool(flags & native.FLAG_V_TRANSFORM)
+            tables = dict(vrep_q=vrep_q, vrep_k=vrep_k, cs_q=cs_q, cs_k=cs_k)
+            grads = tuple(_repgrad.table_grads(desc, tables, meta, tc, ((q, dq), (do, out))[:1 + vt], ((dk, k), (dv, v))[:1 + vt],
+                                               direct=False, masks=(q_live, ctx.k_live)))
+        return (dq, dk, dv, _restore_scalar(dtc, ctx.tc_meta), _restore_scalar(dta, ctx.tau_meta)) + (None,) * 10 + grads
 
 
 class _VarlenAttn(torch.autograd.Function):
@@ -868,7 +896,7 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
                   kv_mode: str = "auto", kv_cache: Optional[dict] = None, precise: Optional[bool] = None,
                   key_views=None, key_lens: Optional[torch.Tensor] = None, key_views_backward: bool = False,
                   query_views=None, return_lse: bool = False, key_mask: Optional[torch.Tensor] = None, key_mask_backward: bool = False,
-                  query_mask: Optional[torch.Tensor] = None):
+                  query_mask: Optional[torch.Tensor] = None, key_mask_rep_grad: bool = False):
     """Fused GTA attention on packed reps.  q [B,H,Tq,dh], k/v [B,H,Tk,dh] -> out [B,H,Tq,dh].
 
     kv_mode: 'prepass' = K/V rep pre-pass + lean attention kernel (two launches; at dh = 96 in the MSN layout the attention kernel is
@@ -926,9 +954,15 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
              the vrep_k record of a wholly masked view -- is read: it may hold anything, NaN and Inf included.  Without ``query_mask`` (below) there is no query-side mask: in
              self-attention the masked tokens are query rows too, computed as in the forward, and they take part in the backward with whatever
              ``dout`` they get -- so masked QUERY rows (q, cs_q, and the dout that reaches them) must hold finite values; a zero ``dout`` row then
-             adds exact zeros to dk / dv.  Still refused, by name: rep tables or poses that require grad (no pose / coordinate gradients under a
-             key mask yet), return_lse under grad, kv_cache under grad, precise=True, pretransformed, kv_mode='fused', and the staged and
-             rho-apply layouts.
+             adds exact zeros to dk / dv.  Still refused, by name: rep tables or poses that require grad without ``key_mask_rep_grad`` (below),
+             return_lse under grad, kv_cache under grad, precise=True, pretransformed, kv_mode='fused', and the staged and rho-apply layouts.
+    key_mask_rep_grad: only with ``key_mask_backward=True``.  False (default): rep tables or poses that require grad are refused under a mask,
+             as they always were.  True: they get their gradients (gta_amd/repgrad.py over the live tokens, ``gta_rep_grad_sums_masked``): the
+             key side under the key mask, the query side under ``query_mask`` (without one every query row is live, in self-attention too).
+             A view without a live token gets exact zeros in its record (its matrix is never inverted) and a masked token exact zeros in
+             its so2 / coordinate entries, whatever those hold.  Under a CUDA key mask a scene without a valid key attends its token 0, and
+             that token counts as live here too.  Such tables must be CUDA tensors (the pass has no CPU path; a CPU one is refused by name
+             before anything is launched), and the masked sides' tokens must split evenly into views.
     query_mask: a bool [B, Tq] tensor (True: the query row is live; None: every row is) -- the query side of ``key_mask``: padded tokens of
              a self-attention layer, scenes with different numbers of target rays.  A masked (dead) row is never used: its q row, its cs_q
              row and the vrep_q record of a view without a live row may hold anything, NaN and Inf included, and so may its ``dout`` row in
@@ -942,6 +976,9 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
     """
     if key_mask_backward and key_mask is None and query_mask is None:
         raise native.GtaError("key_mask_backward=True comes with key_mask")
+    if key_mask_rep_grad and not key_mask_backward:
+        raise native.GtaError("key_mask_rep_grad=True comes with key_mask_backward=True (the pose / coordinate gradients are a pass after "
+                              "the masked backward)")
     if query_mask is not None:
         if key_views is not None or key_lens is not None or key_views_backward or query_views is not None:
             raise native.GtaError("query_mask with key_views / query_views / key_lens / key_views_backward: a query mask runs on the key_mask "
@@ -994,7 +1031,16 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
         if query_mask is not None:
             check_query_mask(query_mask, q.shape[0], q.shape[2])
         if key_mask_backward and needs_grad:
-            if carriers:
+            if carriers and key_mask_rep_grad:
+                if key_mask is not None and k.shape[2] % Nk:
+                    raise native.GtaError(f"key_mask_rep_grad: {k.shape[2]} key tokens do not split evenly into {Nk} views")
+                if query_mask is not None and q.shape[2] % Nq:
+                    raise native.GtaError(f"key_mask_rep_grad: {q.shape[2]} query tokens do not split evenly into {Nq} views")
+                if any(c is not None and not c.is_cuda for c in carriers):
+                    # said here, by name, before the forward is launched: the pass that serves them has no CPU path
+                    raise native.GtaError("key_mask_rep_grad: the gradients of rep tables or poses come from a GPU pass (gta_rep_grad_sums_masked): "
+                                          "tables and poses that require grad must be CUDA tensors")
+            elif carriers:
                 raise native.GtaError("key_mask_backward: no pose / coordinate gradients under a key mask yet (gta_rep_grad_sums_varlen knows "
                                       "prefixes only): detach the rep tables and poses")
             if return_lse:
@@ -1010,12 +1056,17 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
                                    else key_index_tensors(key_mask, q.device))
             tables = [packed.get(t) for t in ("vrep_q", "vrep_k", "cs_q", "cs_k")]
             if needs_grad:
-                return _GatherAttn.apply(q, k, v, trans_coeff, tau, cfg, key_idx, key_lens_m, *tables, q_live, q_lens)
+                k_live = effective_key_mask(key_mask, q.device) if carriers and key_mask is not None else None
+                return _GatherAttn.apply(q, k, v, trans_coeff, tau, cfg, key_idx, key_lens_m, *tables, q_live, q_lens, k_live, *carriers)
             c = _gather_forward(q, k, v, cfg, packed, trans_coeff, tau, None, None, key_idx=key_idx, key_lens=key_lens_m, q_live=q_live)[0]
             return (c.out, c.lse) if return_lse else c.out
         if needs_grad:          # (key_mask_backward: anything else was refused above)
             key_idx, key_lens_m = key_index_tensors(key_mask, q.device)
-            return _GatherAttn.apply(q, k, v, trans_coeff, tau, cfg, key_idx, key_lens_m, *(packed.get(t) for t in ("vrep_q", "vrep_k", "cs_q", "cs_k")))
+            tables = [packed.get(t) for t in ("vrep_q", "vrep_k", "cs_q", "cs_k")]
+            if carriers:        # (key_mask_rep_grad: refused above without it)
+                return _GatherAttn.apply(q, k, v, trans_coeff, tau, cfg, key_idx, key_lens_m, *tables, None, None,
+                                         effective_key_mask(key_mask, q.device), *carriers)
+            return _GatherAttn.apply(q, k, v, trans_coeff, tau, cfg, key_idx, key_lens_m, *tables)
         c = _gather_forward(q, k, v, cfg, packed, trans_coeff, tau, key_mask, kv_cache)[0]
         return (c.out, c.lse) if return_lse else c.out
     flags = attention_route(tuple(q.shape), k.shape[2], q.dtype, f_dims, so3_degree, Nq, Nk, pretransformed=pretransformed, use_dma=use_dma,

@@ -184,6 +184,8 @@ class Attention(nn.Module):
         # (training on such batches) the opt-in backward, and the valid query views of a self-attention layer -- both absent by default
         kvb = bool(extras.get("key_views_backward")) if extras is not None else False
         kmb = bool(extras.get("key_mask_backward")) if extras is not None else False
+        # (refining poses through such batches) pose / coordinate gradients under the masks: srt.TransformingSRT's input_mask_rep_grad
+        kmr = bool(extras.get("key_mask_rep_grad")) if extras is not None else False
         query_views = extras.get("query_views") if extras is not None else None
         # a bool [B, Tq] mask of the live query rows (srt.TransformingSRT's input_mask_queries, self-attention layers): absent by default
         query_mask = extras.get("query_mask") if extras is not None else None
@@ -198,7 +200,8 @@ class Attention(nn.Module):
             kv_cache=kv_cache, precise=self.precise and q.dtype == torch.float32 and kv_cache is None,
             **({"key_views": key_views} if key_views is not None else {}), **({"key_mask": key_mask} if key_mask is not None else {}),
             **({"key_views_backward": True} if kvb else {}), **({"query_views": query_views} if query_views is not None else {}),
-            **({"key_mask_backward": True} if kmb else {}), **({"query_mask": query_mask} if query_mask is not None else {}))
+            **({"key_mask_backward": True} if kmb else {}), **({"query_mask": query_mask} if query_mask is not None else {}),
+            **({"key_mask_rep_grad": True} if kmr else {}))
         out = out.permute(0, 2, 1, 3).reshape(B, Tq, H * dh)              # free: out is [B,Tq,H,dh] in memory
         attn = None
         if return_attmap:                                                  # layers.py:441-442

@@ -46,7 +46,7 @@ ABI_SYMBOLS = (
     "gta_strerror", "gta_abi_version", "gta_sizeof_attn_desc",
     "gta_debug_time_next_attention_kernel", "gta_debug_event_create", "gta_debug_event_destroy", "gta_debug_event_elapsed_ms",
     "gta_debug_profile_next_attention_kernel", "gta_debug_attention_kernel",
-    "gta_rep_grad_workspace_bytes", "gta_rep_grad_sums", "gta_rep_grad_sums_varlen",
+    "gta_rep_grad_workspace_bytes", "gta_rep_grad_sums", "gta_rep_grad_sums_varlen", "gta_rep_grad_sums_masked",
     "gta_attn_fwd_staged", "gta_attn_fwd_staged_supported", "gta_attn_fwd_staged_workspace_bytes",
     "gta_attn_fwd_varlen", "gta_attn_fwd_varlen_supported", "gta_attn_fwd_staged_varlen", "gta_attn_fwd_staged_varlen_supported",
     "gta_attn_bwd_varlen", "gta_attn_bwd_varlen_supported",
@@ -135,6 +135,9 @@ def lib():
                                         + [c_void_p] * 4 + [c_int64, c_void_p])
         # gta_rep_grad_sums with lens ([B] int32, device) in front of the outputs
         L.gta_rep_grad_sums_varlen.argtypes = ([ctypes.POINTER(GtaAttnDesc), c_int32, c_int32] + [c_void_p, ctypes.POINTER(c_int64)] * 4
+                                               + [c_void_p] * 5 + [c_int64, c_void_p])
+        # gta_rep_grad_sums with live ([B, T] uint8, device) in front of the outputs
+        L.gta_rep_grad_sums_masked.argtypes = ([ctypes.POINTER(GtaAttnDesc), c_int32, c_int32] + [c_void_p, ctypes.POINTER(c_int64)] * 4
                                                + [c_void_p] * 5 + [c_int64, c_void_p])
         L.gta_attn_fwd_staged.argtypes = [ctypes.POINTER(GtaAttnDesc)] + [c_void_p] * 14 + [c_int64, c_void_p]
         L.gta_attn_fwd_staged_supported.argtypes = [ctypes.POINTER(GtaAttnDesc)]
@@ -640,13 +643,22 @@ def rep_grad_workspace_bytes(desc: GtaAttnDesc, side: int) -> int:
     return n
 
 
-def rep_grad_sums(desc: GtaAttnDesc, side: int, pairs, view: bool = False, so2: bool = False, t2: bool = False, lens=None):
+def rep_grad_sums(desc: GtaAttnDesc, side: int, pairs, view: bool = False, so2: bool = False, t2: bool = False, lens=None, live=None):
     """Segmented sums of a b^T over the (a, b) pairs (one or two [B,H,T,dh] views of desc's dtype) -> fp32
     (view [B,N,4,4], so2 [B,T,d_so2/2,2,2], t2 [B,T,3,3]), None where not asked (include/gta_hip.h: gta_rep_grad_sums).
     ``lens`` ([B] int32 on the device, valid tokens of this side per scene): ``gta_rep_grad_sums_varlen`` -- rows at or past the prefix
-    are never read, their sums are exact zeros."""
+    are never read, their sums are exact zeros.
+    ``live`` (contiguous bool or uint8 [B, T] on the device, non-zero = a live token of this side): ``gta_rep_grad_sums_masked`` -- the
+    rows of dead tokens are never read, their sums and those of views without a live token are exact zeros.  Not together with ``lens``."""
     flat = [t for ab in pairs for t in ab]
     _require_cuda(*flat)
+    if live is not None:
+        if lens is not None:
+            raise GtaError("gta_rep_grad_sums: lens and live together (a side has prefixes or a mask, not both)")
+        T_side = desc.Tk if side else desc.Tq
+        if (not torch.is_tensor(live) or not live.is_cuda or live.dtype not in (torch.bool, torch.uint8)
+                or tuple(live.shape) != (desc.B, T_side) or not live.is_contiguous()):
+            raise GtaError(f"gta_rep_grad_sums_masked: live is a contiguous bool or uint8 [B, T] = [{desc.B}, {T_side}] CUDA tensor")
     if lens is not None:
         _require_cuda(lens)
         if lens.dtype != torch.int32 or lens.dim() != 1 or lens.numel() != desc.B or not lens.is_contiguous():
@@ -667,7 +679,9 @@ def rep_grad_sums(desc: GtaAttnDesc, side: int, pairs, view: bool = False, so2: 
         for t in (pairs[i] if i < len(pairs) else (None, None)):
             args += [_ptr(t), None if t is None else _strides(t)]
     outs = (_ptr(vo), _ptr(so), _ptr(to), _ptr(ws), 0 if ws is None else ws.numel(), _stream())
-    if lens is None:
+    if live is not None:
+        check(lib().gta_rep_grad_sums_masked(ctypes.byref(desc), int(side), len(pairs), *args, _ptr(live), *outs), "gta_rep_grad_sums_masked")
+    elif lens is None:
         check(lib().gta_rep_grad_sums(ctypes.byref(desc), int(side), len(pairs), *args, *outs), "gta_rep_grad_sums")
     else:
         check(lib().gta_rep_grad_sums_varlen(ctypes.byref(desc), int(side), len(pairs), *args, _ptr(lens), *outs), "gta_rep_grad_sums_varlen")

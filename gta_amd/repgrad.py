@@ -15,6 +15,10 @@ of the matrices as applied; the fused path's sums are in the input space and go 
 Batches that mix view counts (``key_views_backward=True``): the sums come from ``gta_rep_grad_sums_varlen`` over each scene's prefix, and
 the algebra runs under masks built from the host view counts -- a padded view's matrix is never inverted, padded entries are selected to
 exact zero.
+
+Key and query masks (``key_mask_rep_grad=True``): the sums come from ``gta_rep_grad_sums_masked`` over the live tokens alone, and the
+algebra runs under the device masks themselves -- a token is live when its byte is set, a view when one of its tokens is; nothing is
+read back.
 """
 from __future__ import annotations
 
@@ -140,14 +144,32 @@ def t2_packed(side: int, dM, live=None) -> torch.Tensor:
 
 
 def table_grads(desc, tables: dict, meta, tc, q_pairs, k_pairs, direct: bool, euclid: bool = False, q_view_pairs=None,
-                views=(None, None), lens=(None, None)):
+                views=(None, None), lens=(None, None), masks=(None, None)):
     """The carriers' gradients (list of six, None where no gradient is asked): the sums of both sides through ``gta_rep_grad_sums``
     (one launch per side; under euclid two more for the query side's view sums), then the algebra above.
     views, lens: per side (query, key) the validated host tuple of per-scene view counts (``query_views`` / ``key_views``) with the device
     tensor of valid tokens built from it (``q_lens`` / ``key_lens``), or None for a side without padding.  A side that has them takes its
     sums through ``gta_rep_grad_sums_varlen`` -- nothing of a padded view is read -- and the algebra works under masks built from the
-    host tuple: padded views' matrices are never inverted, and padded entries get exact zeros."""
+    host tuple: padded views' matrices are never inverted, and padded entries get exact zeros.
+    masks: per side (query, key) a device bool [B, T] (True = a live token of that side), or None for a side without a mask.  A side that
+    has one takes its sums through ``gta_rep_grad_sums_masked`` -- nothing of a dead token is read -- and the algebra works under
+    live_t = mask, live_v = "the view has a live token", both built on the device without a sync: a view without a live token never has
+    its matrix inverted and gets exact zeros, and so do a dead token's so2 / coordinate entries.  Not with ``views`` on the same side."""
     out = [None] * 6
+    for side, mask in enumerate(masks):          # said by name, for either side, before anything is launched
+        if mask is None:
+            continue
+        T, N = (desc.Tk, desc.Nk) if side else (desc.Tq, desc.Nq)
+        if views[side] is not None:
+            raise native.GtaError("table_grads: views= and masks= on the same side (a side has per-scene view counts or a mask, not both)")
+        if euclid:
+            raise native.GtaError("table_grads: masks= does not serve euclid layouts")
+        if direct:
+            raise native.GtaError("table_grads: masks= does not serve direct sums (the generic path): the fused layouts only")
+        if T % N != 0:
+            raise native.GtaError(f"table_grads: masks= needs tokens that split evenly into views: T % N != 0 (T = {T}, N = {N})")
+        if not torch.is_tensor(mask) or mask.dtype != torch.bool or tuple(mask.shape) != (desc.B, T):
+            raise native.GtaError(f"table_grads: masks[{side}] is a bool [B, T] = [{desc.B}, {T}] tensor")
     for side, pairs in ((0, q_pairs), (1, k_pairs)):
         mv, mc, mo = meta[side], meta[2 + side], meta[4 + side]
         if mv is None and mc is None and mo is None:
@@ -160,10 +182,15 @@ def table_grads(desc, tables: dict, meta, tc, q_pairs, k_pairs, direct: bool, eu
             T, N = (desc.Tk, desc.Nk) if side else (desc.Tq, desc.Nq)
             dev = pairs[0][0].device
             live_v, live_t = live_mask(views[side], N, 1, dev), live_mask(views[side], N, T // N, dev)
+        mask = masks[side]
+        if mask is not None:
+            T, N = (desc.Tk, desc.Nk) if side else (desc.Tq, desc.Nq)
+            live_t, live_v = mask, mask.view(desc.B, N, T // N).any(-1)
         view_here = want_view and not (euclid and side == 0)
         if view_here or want_so2 or want_t2:
             S, T2, T3 = native.rep_grad_sums(desc, side, pairs, view=view_here, so2=want_so2, t2=want_t2,
-                                             lens=lens[side] if views[side] is not None else None)
+                                             lens=lens[side] if views[side] is not None else None,
+                                             **({} if mask is None else {"live": mask}))
         if want_view and not view_here:
             S = native.rep_grad_sums(desc, 0, q_view_pairs[:1], view=True)[0]
             if len(q_view_pairs) > 1:

@@ -186,7 +186,8 @@ class TransformingSRT(nn.Module):
         return self.decoder(z, x, rays, extras)
 
     def forward(self, input_images, input_camera_pos, input_rays, target_camera_pos, target_rays, extras=None, input_views=None,
-                input_views_backward=False, input_mask=None, input_mask_backward=False, input_mask_queries=False):
+                input_views_backward=False, input_mask=None, input_mask_backward=False, input_mask_queries=False,
+                input_mask_rep_grad=False):
         """``input_views``: per-scene numbers of valid input views (a host sequence of length B, each in 1..N) for batches that mix
         view counts: scene b's first ``input_views[b]`` views are its input, the rest of its [N, ...] slots is padding that no valid
         token ever attends to -- in the encoder's self-attention and in the decoder's cross-attention (``gta_attention``'s
@@ -200,8 +201,8 @@ class TransformingSRT(nn.Module):
         subset: smaller views padded inside their slots, a missing view that is not the last, patches to ignore.  No token attends to a
         masked one, in the encoder's self-attention and in the decoder's cross-attention (``gta_attention``'s ``key_mask``); the scene
         tokens of masked positions are still computed and unspecified.  Not together with ``input_views``.  Inference only unless
-        ``input_mask_backward=True``: every layer then runs the differentiable route (``key_mask_backward``; fused layouts, no pose or
-        coordinate gradients).  Without ``input_mask_queries`` there is no query-side mask: in the encoder's self-attention the masked
+        ``input_mask_backward=True``: every layer then runs the differentiable route (``key_mask_backward``; fused layouts; pose and
+        coordinate gradients only with ``input_mask_rep_grad``, below).  Without ``input_mask_queries`` there is no query-side mask: in the encoder's self-attention the masked
         tokens are query rows too and take part in the backward, so the inputs at masked positions must be finite (zero-filled padding is);
         nothing of a masked token reaches a valid one as a KEY.
 
@@ -211,12 +212,20 @@ class TransformingSRT(nn.Module):
         the masked tokens (and the images of a view without a live token) away before its token-wise layers, whose weight gradients sum
         over all rows.  The inputs of wholly masked views may then hold anything, NaN and Inf included; the pixels of a partly masked view
         still pass the convolutions and must be finite.  The scene tokens of masked positions are unspecified but finite.  The decoder's
-        queries are the target rays, all live: the mask is taken out of the copy of ``extras`` before it."""
+        queries are the target rays, all live: the mask is taken out of the copy of ``extras`` before it.
+
+        ``input_mask_rep_grad``: only with ``input_mask_backward=True``.  False (default): poses and coordinates that require grad are refused
+        under a mask, as before.  True: ``extras['input_transforms']``, ``['input_coord']`` and ``['target_*']`` may require grad
+        (``gta_attention``'s ``key_mask_rep_grad``): the extrinsics of a view without a valid token and the coordinates of a masked token
+        get exact zeros on every side that carries the mask -- the key side always, the encoder's query side with ``input_mask_queries``.
+        Without ``input_mask_queries`` the encoder's masked tokens are live query rows and send their (finite) share."""
         extras = {} if extras is None else extras
         if input_mask_backward and input_mask is None:
             raise native.GtaError("input_mask_backward=True comes with input_mask")
         if input_mask_queries and input_mask is None:
             raise native.GtaError("input_mask_queries=True comes with input_mask")
+        if input_mask_rep_grad and not input_mask_backward:
+            raise native.GtaError("input_mask_rep_grad=True comes with input_mask_backward=True")
         if input_mask is not None:
             if input_views is not None:
                 raise native.GtaError("input_mask with input_views: a call takes one key mask -- a prefix of views is a mask too")
@@ -224,6 +233,8 @@ class TransformingSRT(nn.Module):
             extras["key_mask"] = _token_mask(input_mask)
             if input_mask_backward:
                 extras["key_mask_backward"] = True
+            if input_mask_rep_grad:
+                extras["key_mask_rep_grad"] = True
             if input_mask_queries:
                 extras["query_mask"] = extras["key_mask"]      # (the encoder's layers: Tq = Tk, the same tokens on both sides)
         if input_views is not None:

@@ -466,6 +466,26 @@ int gta_rep_grad_sums_varlen(const GtaAttnDesc* desc, int32_t side, int32_t n_pa
                              const int32_t* lens, float* view_sums, float* so2_sums, float* t2_sums,
                              void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The sums under a per-token mask (the pass after gta_attn_bwd_gather / gta_attn_bwd_qmask): gta_rep_grad_sums over the live rows alone.
+ *   live: [B, T] uint8 on the device, one byte per token of this side, non-zero = live; NULL: GTA_E_BADARG.
+ *   Never-read: a row (b, h, t) with live[b * T + t] == 0 is dead: none of its operands is loaded, in either pair (it may hold anything,
+ *       NaN and Inf included), and it adds exact zero to every sum.
+ *   Dead-zero: every requested output is written whole: per-token sums of dead tokens and the view sums of views without a live token
+ *       are +0.0 (all bits zero).  A scene without a live token is legal: everything it owns is +0.0.
+ *   Live-equal: every output word is bit for bit that of gta_rep_grad_sums on the same operands with the dead rows set to zero (the MASKED
+ *       twin of the instance it selects: the same thread-to-row map, pair and group order, tree, head order and finish order); under
+ *       a mask that is a prefix of every scene it is the word of gta_rep_grad_sums_varlen with those counts.
+ *   Dead workgroups: a workgroup (256 / H tokens of one view) none of whose tokens is live loads nothing, writes +0.0 to what it owns and
+ *       returns.  That is decided uniformly, by one OR over the whole workgroup -- never from its first token: a workgroup whose first
+ *       token is dead and a later one live is a live workgroup.
+ *   Workspace (gta_rep_grad_workspace_bytes serves all three entries), every other argument, check and error code: as in
+ *       gta_rep_grad_sums. */
+int gta_rep_grad_sums_masked(const GtaAttnDesc* desc, int32_t side, int32_t n_pairs,
+                             const void* a0, const int64_t* a0_stride, const void* b0, const int64_t* b0_stride,
+                             const void* a1, const int64_t* a1_stride, const void* b1, const int64_t* b1_stride,
+                             const uint8_t* live, float* view_sums, float* so2_sums, float* t2_sums,
+                             void* workspace, int64_t workspace_bytes, void* stream);
+
 /* softmax((scale * q k^T + key_bias) / tau) v with no rep at all (the fused kernel on an identity layout).
  * key_bias: [B,H,bias_pitch] fp32, added to scale*q.k BEFORE the division by tau; bias_pitch a multiple of 64 >= Tk; or NULL.
  * Only desc->{dtype,B,H,Tq,Tk,dh,scale,*_stride} are read. */

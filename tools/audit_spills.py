@@ -351,9 +351,13 @@ def audit_gen():
 
 
 def audit_repgrad():
-    """The rep-gradient sums (gta_repgrad.hip): the six <ESZ, EUCLID, VEC> instances and their VARLEN twins (gta_rep_grad_sums_varlen).
-    Registers as the code object's metadata counts them (.vgpr_count), the static LDS and scratch; DESIGN.md 4.8 / 4.8c: no scratch, the
-    32 KiB reduction array, 44-64 VGPRs.  Hard: twelve instances, no scratch, and a VARLEN twin with the LDS of its instance."""
+    """The rep-gradient sums (gta_repgrad.hip): the six <ESZ, EUCLID, VEC> instances, their VARLEN twins (gta_rep_grad_sums_varlen) and
+    their MASKED twins (gta_rep_grad_sums_masked: the trailing `const uint8_t*`).  Registers as the code object's metadata counts them
+    (.vgpr_count), the static LDS and scratch; DESIGN.md 4.8 / 4.8c / 4.8d: no scratch, the 32 KiB reduction array, 44-64 VGPRs.  Hard:
+    eighteen instances, no scratch, a VARLEN or MASKED twin with the LDS of its instance, and a MASKED twin with no more VGPRs than its
+    VARLEN twin (the mask byte and the workgroup-wide OR die before the sums begin).  A MASKED twin above its unmasked instance's count is
+    reported ("perf:"): hipcc gives every instance with a run-time row predicate 4 more than the one whose predicate is `tl < ntok`, the
+    VARLEN twins included, and the LDS bounds the occupancy (five workgroups per CU) well below either count."""
     text = _asm("gta_repgrad.hip")
     report, problems, seen = [], [], {}
     for name, (esz, euclid, vec, varlen), body, _ in _kernels(text, r"gta_repgrad_kernelILi(\d)ELb(\d)ELb(\d)ELb(\d)E"):
@@ -361,8 +365,9 @@ def audit_repgrad():
         lds = int(re.search(r"\.amdhsa_group_segment_fixed_size\s+(\d+)", meta).group(1))
         private = int(re.search(r"\.amdhsa_private_segment_fixed_size\s+(\d+)", meta).group(1))
         vgpr = int(re.search(r"\.name:\s+" + re.escape(name) + r"\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)", text).group(1))
-        key = (int(esz), euclid == "1", vec == "1", varlen == "1")
-        row = {"kernel": f"gta_repgrad_kernel<{esz}, {'euclid' if key[1] else 'se3'}, {'vec' if key[2] else 'scalar'}{', varlen' if key[3] else ''}>",
+        masked = "JPKhEE" in name
+        key = (int(esz), euclid == "1", vec == "1", "masked" if masked else varlen == "1")
+        row = {"kernel": f"gta_repgrad_kernel<{esz}, {'euclid' if key[1] else 'se3'}, {'vec' if key[2] else 'scalar'}{', masked' if masked else ', varlen' if key[3] else ''}>",
                "vgpr": vgpr, "lds_bytes": lds, "scratch": body.count("scratch_") + private}
         seen[key] = row
         report.append(row)
@@ -370,10 +375,19 @@ def audit_repgrad():
             problems.append(f"{row['kernel']}: scratch in use ({row['scratch']})")
         if vgpr > 64:
             problems.append(f"perf: {row['kernel']}: {vgpr} VGPRs (DESIGN.md 4.8: 44-64)")
-    if len(seen) != 12:
-        problems.append(f"gta_repgrad.hip: {len(seen)} kernel instances found (expected 12)")
+    if len(seen) != 18:
+        problems.append(f"gta_repgrad.hip: {len(seen)} kernel instances found (expected 18)")
     for key, row in seen.items():
-        if key[3] and (key[:3] + (False,) not in seen or row["lds_bytes"] != seen[key[:3] + (False,)]["lds_bytes"]):
+        if key[3] == "masked":
+            twin = seen.get(key[:3] + (False,))
+            if twin is None or row["lds_bytes"] != twin["lds_bytes"]:
+                problems.append(f"{row['kernel']}: no unmasked twin, or another LDS size")
+            elif row["vgpr"] > twin["vgpr"]:
+                problems.append(f"perf: {row['kernel']}: {row['vgpr']} VGPRs, its unmasked twin {twin['vgpr']}")
+            varlen_twin = seen.get(key[:3] + (True,))
+            if varlen_twin is None or row["vgpr"] > varlen_twin["vgpr"]:
+                problems.append(f"{row['kernel']}: {row['vgpr']} VGPRs, its VARLEN twin {varlen_twin and varlen_twin['vgpr']}")
+        elif key[3] and (key[:3] + (False,) not in seen or row["lds_bytes"] != seen[key[:3] + (False,)]["lds_bytes"]):
             problems.append(f"{row['kernel']}: no twin without VARLEN, or another LDS size")
     return report, problems
 
