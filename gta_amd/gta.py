@@ -283,73 +283,6 @@ def _none_to_zero(dout, like):
     return torch.zeros_like(like) if dout is None else dout
 
 
-class _GtaAttn(torch.autograd.Function):
-    """forward -> out.  ``_GtaAttnLse`` below is the same call with the pair (out, lse) as differentiable outputs (``return_lse``); both
-    share ``_run`` and ``_grads``."""
-
-    @staticmethod
-    def forward(ctx, *args):
-        return _GtaAttn._run(ctx, *args).out
-
-    @staticmethod
-    def backward(ctx, dout):
-        return _GtaAttn._grads(ctx, dout)
-
-    @staticmethod
-    def _run(ctx, q, k, v, trans_coeff, tau, kv_cache, cfg, vrep_q, vrep_k, cs_q, cs_k, *carriers):
-        # carriers: () or six tensors / None (gta_amd.repgrad.split_tables) whose gradients the backward returns
-        flags = cfg[5]
-        c = _setup_call(q, k, v, *cfg, dict(vrep_q=vrep_q, vrep_k=vrep_k, cs_q=cs_q, cs_k=cs_k), trans_coeff, tau,
-                        k_side=not (flags & native.FLAG_PRETRANSFORMED))
-        ws = None
-        if not (flags & (native.FLAG_FUSED_KV | native.FLAG_PRETRANSFORMED)):
-            ws = _fused_workspace(c, cfg, kv_cache)
-        native.attn_fwd(c.desc, c.q, c.k, c.v, vrep_q, vrep_k, cs_q, cs_k, c.tc, c.ta, c.out, c.lse, ws)
-        ctx.cfg = cfg
-        # K'/V' tile images of the two-stage plan: reused by the backward (fp32-faithful plan: its hi / lo images by the X3 walks, r06)
-        ctx.kv_images = ws
-        ctx.save_for_backward(c.q, c.k, c.v, c.out, c.lse, c.tc, c.ta, vrep_q, vrep_k, cs_q, cs_k)
-        ctx.tc_meta, ctx.tau_meta = _scalar_meta(trans_coeff), _scalar_meta(tau)
-        ctx.carriers = _repgrad.carrier_meta(carriers)
-        return c
-
-    @staticmethod
-    def _grads(ctx, dout, dlse=None):
-        from . import backward as _bw
-        q, k, v, out, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k = ctx.saved_tensors
-        want_dtau = ta is not None and ctx.needs_input_grad[4]
-        dq, dk, dv, dtc, dta = _bw.attn_bwd(ctx.cfg, q, k, v, out, dout, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k,
-                                            kv_images=ctx.kv_images, want_dtau=want_dtau, dlse=dlse)
-        dtc, dta = _restore_scalar(dtc, ctx.tc_meta), _restore_scalar(dta, ctx.tau_meta)
-        grads = ()
-        if ctx.carriers:
-            # gradients of the tables: a pass after the backward over (q, dq), (dout, out) and (dk, k), (dv, v) (gta_amd/repgrad.py)
-            meta = tuple(m if need else None for m, need in zip(ctx.carriers, ctx.needs_input_grad[11:]))
-            f_dims, so3_degree, Nq, Nk, scale, flags = ctx.cfg
-            desc = native.make_desc(q, k, v, out, f_dims, so3_degree, Nq, Nk, scale, flags)
-            do = _as_kernel_layout(dout.to(q.dtype))
-            vt = bool(flags & native.FLAG_V_TRANSFORM)
-            tables = dict(vrep_q=vrep_q, vrep_k=vrep_k, cs_q=cs_q, cs_k=cs_k)
-            grads = tuple(_repgrad.table_grads(desc, tables, meta, tc, ((q, dq), (do, out))[:1 + vt], ((dk, k), (dv, v))[:1 + vt],
-                                               direct=False))
-        return (dq, dk, dv, dtc, dta, None, None, None, None, None, None) + grads
-
-
-class _GtaAttnLse(torch.autograd.Function):
-    """``_GtaAttn`` -> (out, lse), both differentiable: the backward takes (dout, dlse), either of which may be None, through
-    ``gta_attn_bwd_dlse`` (dS = P (dP - D + dlse): the q-side pre-pass stores -(D - dlse), every walk is the one of ``gta_attn_bwd``)."""
-
-    @staticmethod
-    def forward(ctx, *args):
-        ctx.set_materialize_grads(False)
-        c = _GtaAttn._run(ctx, *args)
-        return c.out, c.lse
-
-    @staticmethod
-    def backward(ctx, dout, dlse):
-        return _GtaAttn._grads(ctx, _none_to_zero(dout, ctx.saved_tensors[3]), dlse)
-
-
 class _GenericAttn(torch.autograd.Function):
     """Ablation layouts the fused kernels refuse (t2 slab, so3 degree 1, unaligned slabs, euclid similarity):
     generic rho-apply kernels (gta_rep_apply) around the plain attention kernel, and for the backward their
@@ -505,7 +438,7 @@ class _GenericAttn(torch.autograd.Function):
 
 
 class _GenericAttnLse(torch.autograd.Function):
-    """``_GenericAttn`` -> (out, lse), both differentiable (``return_lse``; default arithmetic): see ``_GtaAttnLse``"""
+    """``_GenericAttn`` -> (out, lse), both differentiable (``return_lse``; default arithmetic): see ``_FusedAttnLse``"""
 
     @staticmethod
     def forward(ctx, *args):
@@ -548,7 +481,7 @@ def generic_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree: i
     call that would be 'apply' raises ``GtaError`` instead -- ``_GenericAttn`` has no key mask; that holds under ``key_views_backward`` too (the
     backward with per-scene prefixes serves the fused layouts alone)."""
     if key_views:
-        _key_views_refusals(needs_grad=needs_grad, precise=precise, key_views_backward=key_views_backward)
+        _mask_refusals("key_views", needs_grad=needs_grad, precise=precise, backward=key_views_backward)
         if needs_grad:
             raise native.GtaError("key_views_backward: the staged generic layouts (t2, euclid, so3 of degree 1, unaligned slabs) have no backward "
                                   "with a key mask")
@@ -566,17 +499,38 @@ def generic_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree: i
     return "staged" if native.attn_fwd_staged_supported(probe) == 0 else "apply"
 
 
-def _key_views_refusals(*, needs_grad=False, precise=False, pretransformed=False, kv_mode="auto", key_views_backward=False):
-    """what a call with ``key_views`` cannot be combined with: said here, before anything is launched, instead of running a route without the mask.
-    ``key_views_backward`` opts in to the backward (``gta_attn_bwd_varlen``); without it a call under grad is refused as before."""
-    if needs_grad and not key_views_backward:
-        raise native.GtaError("key_views is forward-only (no backward with per-scene key prefixes yet): call under torch.no_grad()")
+# what the refusals of a masked call say per keyword: why it is forward-only without its opt-in, what of it lives in the K/V pre-pass, and what
+# the single-kernel plan lacks
+_MASK_WORDS = {"key_views": ("no backward with per-scene key prefixes yet", "key mask", "per-scene key mask"),
+               "key_mask": ("no backward through the gathered keys yet", "gather", "gather")}
+
+
+def _mask_refusals(name, *, needs_grad=False, precise=False, pretransformed=False, kv_mode="auto", backward=False):
+    """what a call with ``name`` (``key_views`` or ``key_mask``) cannot be combined with: said here, before anything is launched, instead of
+    running a route without the mask.  ``backward``: the keyword's opt-in to its backward (``key_views_backward``: ``gta_attn_bwd_varlen``,
+    ``key_mask_backward``: ``gta_attn_bwd_gather``); without it a call under grad is refused as before."""
+    forward_only, prepass, fused = _MASK_WORDS[name]
+    if needs_grad and not backward:
+        raise native.GtaError(f"{name} is forward-only ({forward_only}): call under torch.no_grad()")
     if precise:
-        raise native.GtaError("key_views has no precise=True (fp32-faithful) instances")
+        raise native.GtaError(f"{name} has no precise=True (fp32-faithful) instances")
     if pretransformed:
-        raise native.GtaError("key_views with pretransformed=True: the key mask lives in the K/V pre-pass, which that mode skips")
+        raise native.GtaError(f"{name} with pretransformed=True: the {prepass} lives in the K/V pre-pass, which that mode skips")
     if kv_mode == "fused":
-        raise native.GtaError("key_views runs the two-stage plan: kv_mode='fused' has no per-scene key mask")
+        raise native.GtaError(f"{name} runs the two-stage plan: kv_mode='fused' has no {fused}")
+
+
+def _refuse_uneven(name, side, T, N):
+    """the masked rep-gradient passes and the per-scene view counts work per view: the tokens of a side split evenly into its views"""
+    if T % N:
+        raise native.GtaError(f"{name}: {T} {side} tokens do not split evenly into {N} views")
+
+
+def _refuse_cpu_carriers(name, gpu_pass, carriers):
+    """said by name, before the forward is launched: the pass that serves the carriers under a mask has no CPU path"""
+    if any(c is not None and not c.is_cuda for c in carriers):
+        raise native.GtaError(f"{name}: the gradients of rep tables or poses come from a GPU pass ({gpu_pass}): "
+                              "tables and poses that require grad must be CUDA tensors")
 
 
 def check_key_views(key_views, B: int, Nk: Optional[int], name: str = "key_views") -> Tuple[int, ...]:
@@ -609,19 +563,6 @@ def check_key_views(key_views, B: int, Nk: Optional[int], name: str = "key_views
 def key_lens_tensor(key_views: Tuple[int, ...], Pk: int, device) -> torch.Tensor:
     """[B] int32 on ``device``: the valid key TOKENS per scene (view-major tokens: a prefix), what the varlen entries read"""
     return torch.tensor([n * Pk for n in key_views], dtype=torch.int32).to(device, non_blocking=True)
-
-
-def _key_mask_refusals(*, needs_grad=False, precise=False, pretransformed=False, kv_mode="auto", key_mask_backward=False):
-    """what a call with ``key_mask`` cannot be combined with: said here, before anything is launched.  ``key_mask_backward`` opts in to the
-    backward (``gta_attn_bwd_gather``); without it a call under grad is refused as before."""
-    if needs_grad and not key_mask_backward:
-        raise native.GtaError("key_mask is forward-only (no backward through the gathered keys yet): call under torch.no_grad()")
-    if precise:
-        raise native.GtaError("key_mask has no precise=True (fp32-faithful) instances")
-    if pretransformed:
-        raise native.GtaError("key_mask with pretransformed=True: the gather lives in the K/V pre-pass, which that mode skips")
-    if kv_mode == "fused":
-        raise native.GtaError("key_mask runs the two-stage plan: kv_mode='fused' has no gather")
 
 
 def check_key_mask(key_mask, B: Optional[int] = None, Tk: Optional[int] = None):
@@ -729,7 +670,7 @@ def _two_stage_workspace(desc, flags, plan_key, kv_cache, device, need, cache_by
 
 
 def _fused_workspace(c: _Call, cfg, kv_cache, key_views=None):
-    """``_two_stage_workspace`` for the fused family (``_GtaAttn`` and the varlen forward alike)"""
+    """``_two_stage_workspace`` for the fused family (``_fused_forward``, masked or not)"""
     f_dims, so3_degree, _, Nk, scale, flags = cfg
     need = native.attn_fwd_workspace_bytes(c.desc)
     if kv_cache is None:
@@ -747,132 +688,159 @@ def _fused_workspace(c: _Call, cfg, kv_cache, key_views=None):
     return _two_stage_workspace(c.desc, flags, plan_key, kv_cache, c.q.device, need, cache_bytes)
 
 
-def _varlen_forward(q, k, v, cfg, tables, trans_coeff, tau, key_lens, key_views=None, kv_cache=None):
-    """The fused layouts with per-scene key prefixes: ``gta_attn_fwd_varlen`` -- the two-stage plan's pre-pass and gta_fwd2_kernel in their
-    VARLEN instances.  ``kv_cache`` as in ``_GtaAttn``; its plan key carries the view counts.  -> (the call, its workspace)"""
-    c = _setup_call(q, k, v, *cfg, tables, trans_coeff, tau)
-    ws = _fused_workspace(c, cfg, kv_cache, key_views)
-    native.attn_fwd_varlen(c.desc, c.q, c.k, c.v, tables.get("vrep_q"), tables.get("vrep_k"), tables.get("cs_q"), tables.get("cs_k"),
-                           c.tc, c.ta, key_lens, c.out, c.lse, ws)
-    return c, ws
+# How a call on the fused layouts is masked: what the forward launcher, ``_FusedAttn`` and its backward pass around.
+#   kind     None (every key, every query row), "views" (per-scene prefixes of views: the varlen entries) or "gather" (key and / or query mask)
+#   key_idx  gather: [B, Tk] int32, ``key_index_tensors`` (``_all_keys_tensors`` under a query mask alone)
+#   key_lens views / gather: [B] int32, the valid key tokens per scene
+#   q_live   gather under a query mask: the mask itself on the device (``query_mask_tensors``)
+#   q_lens   with q_live, or views with ``query_views`` (backward only): [B] int32
+#   k_live   gather with carriers: the effective key mask of the rep-gradient pass (None: every key is live)
+#   views    views: the validated host tuples (query_views or None, key_views) the device tensors were built from
+#   key_mask gather, forward only, no query mask: the caller's mask, from which the launcher builds key_idx / key_lens after its checks -- and a
+#            later call on a ``kv_cache`` builds nothing
+_Mask = namedtuple("_Mask", "kind key_idx key_lens q_live q_lens k_live views key_mask", defaults=(None,) * 8)
+_NO_MASK = _Mask()
 
 
-def _gather_forward(q, k, v, cfg, tables, trans_coeff, tau, key_mask, kv_cache=None, key_idx=None, key_lens=None, q_live=None):
-    """The fused layouts with a key mask: ``gta_attn_fwd_gather`` -- the GATHER instances of the pre-pass compact the valid keys, the VARLEN
-    gta_fwd2_kernel attends over them.  ``key_idx`` / ``key_lens``: the ready-made tensors of ``key_index_tensors`` (``ForwardPlan``), built
-    here when None.  With ``kv_cache`` the first call stores both beside the images (plan key: "key_mask"); later calls run on the stored
-    lengths under GTA_FLAG_KV_READY and build nothing from their mask.  ``q_live`` (``query_mask_tensors``; never with ``kv_cache``): the
-    attention step runs in its QMASK instances (``gta_attn_fwd_qmask``).  -> (the call, its workspace)"""
-    c = _setup_call(q, k, v, *cfg, tables, trans_coeff, tau)
-    ws = _fused_workspace(c, cfg, kv_cache, "key_mask")
-    if c.desc.flags & native.FLAG_KV_READY:
-        key_idx, key_lens = None, kv_cache["key_lens"]
+def _views_mask(key_views, key_lens, query_views, q, k, Nq, Nk) -> _Mask:
+    """``key_views`` (validated; ``key_lens``: its ready-made device tensor or None) and ``query_views`` (validated, or None: no query side)"""
+    if key_lens is None:
+        key_lens = key_lens_tensor(key_views, k.shape[2] // Nk, q.device)
+    q_lens = None if query_views is None else key_lens_tensor(query_views, q.shape[2] // Nq, q.device)
+    return _Mask("views", key_lens=key_lens, q_lens=q_lens, views=(query_views, key_views))
+
+
+def _gather_mask(key_mask, query_mask, q, k, needs_grad, carriers) -> _Mask:
+    """``key_mask`` and / or ``query_mask`` (both validated).  A query mask without a key mask runs under an all-True one; a forward-only call
+    without a query mask leaves the key tensors to the launcher."""
+    if query_mask is None and not needs_grad:
+        return _Mask("gather", key_mask=key_mask)
+    q_live, q_lens = (None, None) if query_mask is None else query_mask_tensors(query_mask, q.device)
+    key_idx, key_lens = _all_keys_tensors(q.shape[0], k.shape[2], q.device) if key_mask is None else key_index_tensors(key_mask, q.device)
+    k_live = effective_key_mask(key_mask, q.device) if needs_grad and carriers and key_mask is not None else None
+    return _Mask("gather", key_idx, key_lens, q_live, q_lens, k_live)
+
+
+def _fused_forward(q, k, v, cfg, kv_cache, mask: _Mask, tables, trans_coeff, tau):
+    """The forward of the fused layouts, one native entry by the mask's kind: ``gta_attn_fwd``; views: ``gta_attn_fwd_varlen`` (the two-stage
+    plan's pre-pass and gta_fwd2_kernel in their VARLEN instances); gather: ``gta_attn_fwd_gather`` (the GATHER instances of the pre-pass
+    compact the valid keys, the VARLEN gta_fwd2_kernel attends over them), under a query mask ``gta_attn_fwd_qmask`` (never with ``kv_cache``).
+    The masked entries always run the two-stage plan; the plan key of their ``kv_cache`` carries the view counts, or the word "key_mask" --
+    such a cache holds ``key_idx`` / ``key_lens`` beside the images, and later calls run on the stored lengths under GTA_FLAG_KV_READY.
+    -> (the call, its workspace: the K'/V' tile images, or None on the single-kernel plan)"""
+    flags = cfg[5]
+    c = _setup_call(q, k, v, *cfg, tables, trans_coeff, tau, k_side=not (flags & native.FLAG_PRETRANSFORMED))
+    kind = mask.kind
+    operands = (c.desc, c.q, c.k, c.v, tables.get("vrep_q"), tables.get("vrep_k"), tables.get("cs_q"), tables.get("cs_k"), c.tc, c.ta)
+    if kind is None:
+        # (the single-kernel plan and a pretransformed call have no K/V pre-pass: no workspace)
+        ws = None if flags & (native.FLAG_FUSED_KV | native.FLAG_PRETRANSFORMED) else _fused_workspace(c, cfg, kv_cache)
+        native.attn_fwd(*operands, c.out, c.lse, ws)
+    elif kind == "views":
+        ws = _fused_workspace(c, cfg, kv_cache, mask.views[1])
+        native.attn_fwd_varlen(*operands, mask.key_lens, c.out, c.lse, ws)
     else:
-        if key_lens is None:
-            key_idx, key_lens = key_index_tensors(key_mask, c.q.device)
-        if kv_cache is not None:
-            kv_cache["key_idx"], kv_cache["key_lens"] = key_idx, key_lens
-    if q_live is not None:
-        native.attn_fwd_qmask(c.desc, c.q, c.k, c.v, tables.get("vrep_q"), tables.get("vrep_k"), tables.get("cs_q"), tables.get("cs_k"),
-                              c.tc, c.ta, key_idx, key_lens, q_live, c.out, c.lse, ws)
-        return c, ws
-    native.attn_fwd_gather(c.desc, c.q, c.k, c.v, tables.get("vrep_q"), tables.get("vrep_k"), tables.get("cs_q"), tables.get("cs_k"),
-                           c.tc, c.ta, key_idx, key_lens, c.out, c.lse, ws)
+        ws = _fused_workspace(c, cfg, kv_cache, "key_mask")
+        key_idx, key_lens = mask.key_idx, mask.key_lens
+        if c.desc.flags & native.FLAG_KV_READY:
+            key_idx, key_lens = None, kv_cache["key_lens"]
+        else:
+            if key_lens is None:
+                key_idx, key_lens = key_index_tensors(mask.key_mask, c.q.device)
+            if kv_cache is not None:
+                kv_cache["key_idx"], kv_cache["key_lens"] = key_idx, key_lens
+        if mask.q_live is not None:
+            native.attn_fwd_qmask(*operands, key_idx, key_lens, mask.q_live, c.out, c.lse, ws)
+        else:
+            native.attn_fwd_gather(*operands, key_idx, key_lens, c.out, c.lse, ws)
     return c, ws
 
 
-class _GatherAttn(torch.autograd.Function):
-    """The fused layouts with a key mask under grad (``key_mask_backward=True``): the forward of ``_gather_forward``, whose workspace (the compacted
-    K'/V' tile images) and LSE serve ``gta_attn_bwd_gather`` under the same ``key_idx`` / ``key_lens`` (``key_index_tensors``: every row a
-    permutation, the valid tokens first).  Gradients: q, k, v, trans_coeff, tau -- as ``_GtaAttn``; dk / dv rows of masked tokens are zeros.
-    ``q_live`` / ``q_lens`` (``query_mask_tensors``; both or neither): the same two tensors go to ``gta_attn_fwd_qmask`` and
-    ``gta_attn_bwd_qmask`` -- dq rows of dead rows are zeros; without them the two gather entries run as before.
-    With ``carriers`` (``key_mask_rep_grad=True``; as in ``_VarlenAttn``) the tables' gradients too: the pass of gta_amd/repgrad.py over the
-    live tokens alone (``gta_rep_grad_sums_masked``) under ``k_live`` (the effective key mask, bool [B, Tk] on the device; None: every key
-    is live) and ``q_live`` (None: every query row is) -- exact zeros for views without a live token and for dead tokens."""
+class _FusedAttn(torch.autograd.Function):
+    """The fused layouts under autograd, masked or not: forward -> out through ``_fused_forward``, whose workspace (the K'/V' tile images, masked
+    or compacted like the call) and LSE serve the backward entry of the same kind (``backward.attn_bwd``).  ``_FusedAttnLse`` below is the same
+    call with the pair (out, lse) as differentiable outputs (``return_lse``); both share ``_run`` and ``_grads``.
+
+    Arguments: (q, k, v, trans_coeff, tau, call, vrep_q, vrep_k, cs_q, cs_k, *carriers) -- ``call`` = (cfg, kv_cache, mask), the one non-tensor
+    argument (kv_cache: the unmasked call's alone, None under a mask); carriers: () or six tensors / None (gta_amd.repgrad.split_tables) whose gradients the backward returns, from ``CARRIERS`` on.
+    Gradients: q, k, v, trans_coeff, tau; dk / dv rows of padded views and masked tokens and dq rows of dead query rows are exact zeros.  With
+    carriers the tables' too: the pass of gta_amd/repgrad.py over (q, dq), (dout, out) and (dk, k), (dv, v) -- views: over the prefixes alone
+    (``gta_rep_grad_sums_varlen``), gather: over the live tokens alone (``gta_rep_grad_sums_masked``) under ``mask.q_live`` (None: every row)
+    and ``mask.k_live`` --, exact zeros for padded or wholly masked views and for dead tokens.
+
+    The mask's tensors (``_Mask``) are integer or bool tensors that take no gradient: they stay on ``ctx`` inside the record, as the objects
+    themselves, never in ``save_for_backward`` -- the backward hands the native entries and ``table_grads`` the very objects the forward got."""
+
+    CARRIERS = 10          # where the carriers start in the argument list
 
     @staticmethod
-    def forward(ctx, q, k, v, trans_coeff, tau, cfg, key_idx, key_lens, vrep_q, vrep_k, cs_q, cs_k, q_live=None, q_lens=None, k_live=None,
-                *carriers):
-        c, ws = _gather_forward(q, k, v, cfg, dict(vrep_q=vrep_q, vrep_k=vrep_k, cs_q=cs_q, cs_k=cs_k), trans_coeff, tau, None,
-                                key_idx=key_idx, key_lens=key_lens, q_live=q_live)
-        ctx.cfg = cfg
-        ctx.kv_images = ws
-        ctx.q_mask = (q_live, q_lens)          # (the objects themselves: they need no gradient and the backward hands them on as they are)
-        ctx.k_live = k_live
-        ctx.carriers = _repgrad.carrier_meta(carriers)
-        ctx.save_for_backward(c.q, c.k, c.v, c.out, c.lse, c.tc, c.ta, vrep_q, vrep_k, cs_q, cs_k, key_idx, key_lens)
-        ctx.tc_meta, ctx.tau_meta = _scalar_meta(trans_coeff), _scalar_meta(tau)
-        return c.out
+    def forward(ctx, *args):
+        return _FusedAttn._run(ctx, *args).out
 
     @staticmethod
     def backward(ctx, dout):
+        return _FusedAttn._grads(ctx, dout)
+
+    @staticmethod
+    def _run(ctx, q, k, v, trans_coeff, tau, call, vrep_q, vrep_k, cs_q, cs_k, *carriers):
+        cfg, kv_cache, mask = call
+        c, ws = _fused_forward(q, k, v, cfg, kv_cache, mask, dict(vrep_q=vrep_q, vrep_k=vrep_k, cs_q=cs_q, cs_k=cs_k), trans_coeff, tau)
+        ctx.cfg, ctx.mask = cfg, mask
+        # K'/V' tile images of the two-stage plan: reused by the backward (fp32-faithful plan: its hi / lo images by the X3 walks, r06)
+        ctx.kv_images = ws
+        ctx.save_for_backward(c.q, c.k, c.v, c.out, c.lse, c.tc, c.ta, vrep_q, vrep_k, cs_q, cs_k)
+        ctx.tc_meta, ctx.tau_meta = _scalar_meta(trans_coeff), _scalar_meta(tau)
+        ctx.carriers = _repgrad.carrier_meta(carriers)
+        return c
+
+    @staticmethod
+    def _grads(ctx, dout, dlse=None):
         from . import backward as _bw
-        q, k, v, out, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k, key_idx, key_lens = ctx.saved_tensors
+        q, k, v, out, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k = ctx.saved_tensors
+        mask = ctx.mask
         want_dtau = ta is not None and ctx.needs_input_grad[4]
-        q_live, q_lens = ctx.q_mask
-        dq, dk, dv, dtc, dta = _bw.attn_bwd(ctx.cfg, q, k, v, out, dout, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k,
-                                            kv_images=ctx.kv_images, want_dtau=want_dtau, key_idx=key_idx, key_lens=key_lens,
-                                            **({} if q_live is None else {"q_live": q_live, "q_lens": q_lens}))
+        dq, dk, dv, dtc, dta = _bw.attn_bwd(ctx.cfg, q, k, v, out, dout, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k, kv_images=ctx.kv_images,
+                                            want_dtau=want_dtau, key_lens=mask.key_lens, q_lens=mask.q_lens, dlse=dlse, key_idx=mask.key_idx,
+                                            q_live=mask.q_live)
         grads = ()
         if ctx.carriers:
-            # gradients of the tables over the live tokens: (q, dq), (dout, out) under q_live (every row without it), (dk, k), (dv, v) under k_live
-            meta = tuple(m if need else None for m, need in zip(ctx.carriers, ctx.needs_input_grad[15:]))
+            # gradients of the tables: a pass after the backward over (q, dq), (dout, out) and (dk, k), (dv, v) (gta_amd/repgrad.py) -- under
+            # per-scene view counts over the prefixes, under masks over the live tokens
+            meta = tuple(m if need else None for m, need in zip(ctx.carriers, ctx.needs_input_grad[_FusedAttn.CARRIERS:]))
             f_dims, so3_degree, Nq, Nk, scale, flags = ctx.cfg
             desc = native.make_desc(q, k, v, out, f_dims, so3_degree, Nq, Nk, scale, flags)
             do = _as_kernel_layout(dout.to(q.dtype))
             vt = bool(flags & native.FLAG_V_TRANSFORM)
             tables = dict(vrep_q=vrep_q, vrep_k=vrep_k, cs_q=cs_q, cs_k=cs_k)
+            sides = {}
+            if mask.kind == "views":
+                sides = dict(views=mask.views, lens=(mask.q_lens, mask.key_lens))
+            elif mask.kind == "gather":
+                sides = dict(masks=(mask.q_live, mask.k_live))
             grads = tuple(_repgrad.table_grads(desc, tables, meta, tc, ((q, dq), (do, out))[:1 + vt], ((dk, k), (dv, v))[:1 + vt],
-                                               direct=False, masks=(q_live, ctx.k_live)))
-        return (dq, dk, dv, _restore_scalar(dtc, ctx.tc_meta), _restore_scalar(dta, ctx.tau_meta)) + (None,) * 10 + grads
+                                               direct=False, **sides))
+        return (dq, dk, dv, _restore_scalar(dtc, ctx.tc_meta), _restore_scalar(dta, ctx.tau_meta)) + (None,) * (_FusedAttn.CARRIERS - 5) + grads
 
 
-class _VarlenAttn(torch.autograd.Function):
-    """The fused layouts with per-scene key prefixes under grad (``key_views_backward=True``): the forward of ``_varlen_forward``, whose workspace
-    (the masked K'/V' tile images) and LSE serve ``gta_attn_bwd_varlen``.  ``q_lens`` (or None) masks padded query rows in the backward only.
-    ``views``: the validated host tuples (query_views or None, key_views) the two device tensors were built from.
-    Gradients: q, k, v, trans_coeff, tau -- as ``_GtaAttn``; and, with ``carriers`` (as in ``_GtaAttn``), the tables': the pass of
-    gta_amd/repgrad.py over the prefixes alone (``gta_rep_grad_sums_varlen``), exact zeros for padded views and tokens."""
+class _FusedAttnLse(torch.autograd.Function):
+    """``_FusedAttn`` -> (out, lse), both differentiable: the backward takes (dout, dlse), either of which may be None, through
+    ``gta_attn_bwd_dlse`` (dS = P (dP - D + dlse): the q-side pre-pass stores -(D - dlse), every walk is the one of ``gta_attn_bwd``)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, trans_coeff, tau, cfg, key_lens, q_lens, views, vrep_q, vrep_k, cs_q, cs_k, *carriers):
-        c, ws = _varlen_forward(q, k, v, cfg, dict(vrep_q=vrep_q, vrep_k=vrep_k, cs_q=cs_q, cs_k=cs_k), trans_coeff, tau, key_lens)
-        ctx.cfg = cfg
-        ctx.kv_images = ws
-        ctx.save_for_backward(c.q, c.k, c.v, c.out, c.lse, c.tc, c.ta, vrep_q, vrep_k, cs_q, cs_k, key_lens, q_lens)
-        ctx.tc_meta, ctx.tau_meta = _scalar_meta(trans_coeff), _scalar_meta(tau)
-        ctx.views = views
-        ctx.carriers = _repgrad.carrier_meta(carriers)
-        return c.out
+    def forward(ctx, *args):
+        ctx.set_materialize_grads(False)
+        c = _FusedAttn._run(ctx, *args)
+        return c.out, c.lse
 
     @staticmethod
-    def backward(ctx, dout):
-        from . import backward as _bw
-        q, k, v, out, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k, key_lens, q_lens = ctx.saved_tensors
-        want_dtau = ta is not None and ctx.needs_input_grad[4]
-        dq, dk, dv, dtc, dta = _bw.attn_bwd(ctx.cfg, q, k, v, out, dout, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k,
-                                            kv_images=ctx.kv_images, want_dtau=want_dtau, key_lens=key_lens, q_lens=q_lens)
-        grads = ()
-        if ctx.carriers:
-            # gradients of the tables over the prefixes: (q, dq), (dout, out) under q_lens (every row without it), (dk, k), (dv, v) under key_lens
-            meta = tuple(m if need else None for m, need in zip(ctx.carriers, ctx.needs_input_grad[13:]))
-            f_dims, so3_degree, Nq, Nk, scale, flags = ctx.cfg
-            desc = native.make_desc(q, k, v, out, f_dims, so3_degree, Nq, Nk, scale, flags)
-            do = _as_kernel_layout(dout.to(q.dtype))
-            vt = bool(flags & native.FLAG_V_TRANSFORM)
-            tables = dict(vrep_q=vrep_q, vrep_k=vrep_k, cs_q=cs_q, cs_k=cs_k)
-            query_views, key_views = ctx.views
-            grads = tuple(_repgrad.table_grads(desc, tables, meta, tc, ((q, dq), (do, out))[:1 + vt], ((dk, k), (dv, v))[:1 + vt],
-                                               direct=False, views=(query_views if q_lens is not None else None, key_views),
-                                               lens=(q_lens, key_lens)))
-        return (dq, dk, dv, _restore_scalar(dtc, ctx.tc_meta), _restore_scalar(dta, ctx.tau_meta)) + (None,) * 8 + grads
+    def backward(ctx, dout, dlse):
+        return _FusedAttn._grads(ctx, _none_to_zero(dout, ctx.saved_tensors[3]), dlse)
 
 
 def _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, kv_cache=None, key_views=None,
                     key_lens=None, return_lse=False):
     """The generic path without a gradient: one pre-pass launch + one attention launch (``gta_attn_fwd_staged``), and the attention
-    launch alone on a call that finds its K'/V' images in ``kv_cache`` -- the contract of ``_GtaAttn``: images and plan key are stored by
+    launch alone on a call that finds its K'/V' images in ``kv_cache`` -- the contract of ``_fused_forward``: images and plan key are stored by
     the first call, later calls against another key set / plan raise ``GtaError``.  ``key_views`` (validated) with ``key_lens`` (device):
     the varlen entry, and the view counts join the plan key."""
     flags = _layout_flags(v_transform, euclid)
@@ -974,19 +942,53 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
              name: ``key_views`` / ``query_views`` / ``key_lens`` / ``key_views_backward`` beside it, ``kv_cache``, and what ``key_mask``
              refuses.  ``return_lse`` without grad is served.
     """
+    route, cfg, mask, packed, carriers, trans_coeff, tau = _resolve(
+        q, k, v, f_dims, packed, so3_degree=so3_degree, trans_coeff=trans_coeff, tau=tau, scale=scale, v_transform=v_transform, euclid=euclid,
+        pretransformed=pretransformed, use_dma=use_dma, kv_mode=kv_mode, kv_cache=kv_cache, precise=precise, key_views=key_views,
+        key_lens=key_lens, key_views_backward=key_views_backward, query_views=query_views, return_lse=return_lse, key_mask=key_mask,
+        key_mask_backward=key_mask_backward, query_mask=query_mask, key_mask_rep_grad=key_mask_rep_grad)
+    scale = cfg[4]
+    if route == "staged":
+        return _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, kv_cache,
+                               key_views=mask.views and mask.views[1], key_lens=mask.key_lens, return_lse=return_lse)
+    if route == "apply":
+        return _generic_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, precise=bool(precise),
+                                carriers=carriers, return_lse=return_lse)
+    if route == "fused":
+        # (a cache serves the unmasked call alone here: a masked call under grad never reads or fills one -- the kv_cache refusal does not
+        # look at tau, so such a call can come with a dict)
+        if mask.kind is not None:
+            kv_cache = None
+        return (_FusedAttnLse if return_lse else _FusedAttn).apply(q, k, v, trans_coeff, tau, (cfg, kv_cache, mask),
+                                                                   packed.get("vrep_q"), packed.get("vrep_k"), packed.get("cs_q"),
+                                                                   packed.get("cs_k"), *carriers)
+    c = _fused_forward(q, k, v, cfg, kv_cache, mask, packed, trans_coeff, tau)[0]
+    return (c.out, c.lse) if return_lse else c.out
+
+
+def _resolve(q, k, v, f_dims, packed, *, so3_degree, trans_coeff, tau, scale, v_transform, euclid, pretransformed, use_dma, kv_mode, kv_cache,
+             precise, key_views, key_lens, key_views_backward, query_views, return_lse, key_mask, key_mask_backward, query_mask,
+             key_mask_rep_grad):
+    """The host-only half of ``gta_attention`` (its arguments, the keyword-only ones by keyword): every refusal, in a fixed order, then how the call runs.
+    -> (route, cfg, mask, packed, carriers, trans_coeff, tau): route 'fused' (through ``_FusedAttn``: every unmasked call, a masked one under
+    grad), 'forward' (a masked call without grad: ``_fused_forward`` alone), 'staged' or 'apply' (``generic_route``);
+    cfg = (f_dims, so3_degree, Nq, Nk, scale, flags), flags None off the fused routes; the ``_Mask`` record; the tables the kernels read
+    (detached) and their carriers (``repgrad.split_tables``); trans_coeff and tau as tensors or None."""
+    shape, Tk = tuple(q.shape), k.shape[2]
+    B, Tq = shape[0], shape[2]
+    views_given = key_views is not None or key_lens is not None or key_views_backward or query_views is not None
     if key_mask_backward and key_mask is None and query_mask is None:
         raise native.GtaError("key_mask_backward=True comes with key_mask")
     if key_mask_rep_grad and not key_mask_backward:
         raise native.GtaError("key_mask_rep_grad=True comes with key_mask_backward=True (the pose / coordinate gradients are a pass after "
                               "the masked backward)")
-    if query_mask is not None:
-        if key_views is not None or key_lens is not None or key_views_backward or query_views is not None:
-            raise native.GtaError("query_mask with key_views / query_views / key_lens / key_views_backward: a query mask runs on the key_mask "
-                                  "route -- say the valid views as a key_mask (and the valid query rows as the query_mask)")
-        if kv_cache is not None:
-            raise native.GtaError("query_mask with kv_cache: a cache serves later query sets, a query mask belongs to one (no cached query-mask "
-                                  "calls yet)")
-    if key_mask is not None and (key_views is not None or key_lens is not None or key_views_backward or query_views is not None):
+    if query_mask is not None and views_given:
+        raise native.GtaError("query_mask with key_views / query_views / key_lens / key_views_backward: a query mask runs on the key_mask "
+                              "route -- say the valid views as a key_mask (and the valid query rows as the query_mask)")
+    if query_mask is not None and kv_cache is not None:
+        raise native.GtaError("query_mask with kv_cache: a cache serves later query sets, a query mask belongs to one (no cached query-mask "
+                              "calls yet)")
+    if key_mask is not None and views_given:
         raise native.GtaError("key_mask with key_views (or its companions): a call takes one key mask -- a prefix of views is a mask too")
     if query_views is not None and not key_views_backward:
         raise native.GtaError("query_views masks padded query rows in the backward: it needs key_views_backward=True")
@@ -995,7 +997,7 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
     if key_lens is not None and key_views is None:
         raise native.GtaError("key_lens comes with the key_views it was built from")
     if scale is None:
-        scale = q.shape[-1] ** -0.5
+        scale = shape[-1] ** -0.5
     # tables that require grad (poses / coordinates as autograd leaves): the kernels read detached tables, the gradients go to the carriers
     packed, carriers = _repgrad.split_tables(packed)
     if kv_cache is not None and torch.is_grad_enabled() and (carriers or any(torch.is_tensor(t) and t.requires_grad for t in (q, k, v, trans_coeff))):
@@ -1011,88 +1013,55 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
         raise native.GtaError("return_lse under grad with key_views_backward: gta_attn_bwd_varlen takes no gradient of the log-sum-exp "
                               "(drop return_lse, or call under torch.no_grad())")
     Nq, Nk = _views(f_dims, packed, q, k)
+    masked = key_mask is not None or query_mask is not None
     if key_views is not None:
-        key_views = check_key_views(key_views, q.shape[0], Nk if "vrep_k" in packed else None)
-        if k.shape[2] % Nk:
-            raise native.GtaError(f"key_views: {k.shape[2]} key tokens do not split evenly into {Nk} views")
+        key_views = check_key_views(key_views, B, Nk if "vrep_k" in packed else None)
+        _refuse_uneven("key_views", "key", Tk, Nk)
         if query_views is not None:
-            query_views = check_key_views(query_views, q.shape[0], Nq if "vrep_q" in packed else None, name="query_views")
-            if q.shape[2] % Nq:
-                raise native.GtaError(f"query_views: {q.shape[2]} query tokens do not split evenly into {Nq} views")
-        if key_views_backward and any(c is not None and not c.is_cuda for c in carriers):
-            # said here, by name, before the forward is launched: the pass that serves them has no CPU path
-            raise native.GtaError("key_views_backward: the gradients of rep tables or poses come from a GPU pass (gta_rep_grad_sums_varlen): "
-                                  "tables and poses that require grad must be CUDA tensors")
-    how = dict(v_transform=v_transform, euclid=euclid, precise=bool(precise), needs_grad=needs_grad, key_views=key_views is not None,
-               key_views_backward=bool(key_views_backward))
-    if key_mask is not None or query_mask is not None:
+            query_views = check_key_views(query_views, B, Nq if "vrep_q" in packed else None, name="query_views")
+            _refuse_uneven("query_views", "query", Tq, Nq)
+        if key_views_backward:
+            _refuse_cpu_carriers("key_views_backward", "gta_rep_grad_sums_varlen", carriers)
+    if masked:
         if key_mask is not None:
-            check_key_mask(key_mask, q.shape[0], k.shape[2])
+            check_key_mask(key_mask, B, Tk)
         if query_mask is not None:
-            check_query_mask(query_mask, q.shape[0], q.shape[2])
+            check_query_mask(query_mask, B, Tq)
         if key_mask_backward and needs_grad:
             if carriers and key_mask_rep_grad:
-                if key_mask is not None and k.shape[2] % Nk:
-                    raise native.GtaError(f"key_mask_rep_grad: {k.shape[2]} key tokens do not split evenly into {Nk} views")
-                if query_mask is not None and q.shape[2] % Nq:
-                    raise native.GtaError(f"key_mask_rep_grad: {q.shape[2]} query tokens do not split evenly into {Nq} views")
-                if any(c is not None and not c.is_cuda for c in carriers):
-                    # said here, by name, before the forward is launched: the pass that serves them has no CPU path
-                    raise native.GtaError("key_mask_rep_grad: the gradients of rep tables or poses come from a GPU pass (gta_rep_grad_sums_masked): "
-                                          "tables and poses that require grad must be CUDA tensors")
+                if key_mask is not None:
+                    _refuse_uneven("key_mask_rep_grad", "key", Tk, Nk)
+                if query_mask is not None:
+                    _refuse_uneven("key_mask_rep_grad", "query", Tq, Nq)
+                _refuse_cpu_carriers("key_mask_rep_grad", "gta_rep_grad_sums_masked", carriers)
             elif carriers:
                 raise native.GtaError("key_mask_backward: no pose / coordinate gradients under a key mask yet (gta_rep_grad_sums_varlen knows "
                                       "prefixes only): detach the rep tables and poses")
             if return_lse:
                 raise native.GtaError("return_lse under grad with key_mask_backward: gta_attn_bwd_gather takes no gradient of the log-sum-exp "
                                       "(drop return_lse, or call under torch.no_grad())")
-        flags = attention_route(tuple(q.shape), k.shape[2], q.dtype, f_dims, so3_degree, Nq, Nk, pretransformed=pretransformed, use_dma=use_dma,
-                                kv_mode=kv_mode, kv_cache=kv_cache is not None, v_transform=v_transform, euclid=euclid, precise=bool(precise),
-                                needs_grad=needs_grad, key_mask=True, key_mask_backward=bool(key_mask_backward))
-        cfg = ({k_: int(v_) for k_, v_ in f_dims.items()}, int(so3_degree), Nq, Nk, float(scale), flags)
-        if query_mask is not None:
-            q_live, q_lens = query_mask_tensors(query_mask, q.device)
-            key_idx, key_lens_m = (_all_keys_tensors(q.shape[0], k.shape[2], q.device) if key_mask is None
-                                   else key_index_tensors(key_mask, q.device))
-            tables = [packed.get(t) for t in ("vrep_q", "vrep_k", "cs_q", "cs_k")]
-            if needs_grad:
-                k_live = effective_key_mask(key_mask, q.device) if carriers and key_mask is not None else None
-                return _GatherAttn.apply(q, k, v, trans_coeff, tau, cfg, key_idx, key_lens_m, *tables, q_live, q_lens, k_live, *carriers)
-            c = _gather_forward(q, k, v, cfg, packed, trans_coeff, tau, None, None, key_idx=key_idx, key_lens=key_lens_m, q_live=q_live)[0]
-            return (c.out, c.lse) if return_lse else c.out
-        if needs_grad:          # (key_mask_backward: anything else was refused above)
-            key_idx, key_lens_m = key_index_tensors(key_mask, q.device)
-            tables = [packed.get(t) for t in ("vrep_q", "vrep_k", "cs_q", "cs_k")]
-            if carriers:        # (key_mask_rep_grad: refused above without it)
-                return _GatherAttn.apply(q, k, v, trans_coeff, tau, cfg, key_idx, key_lens_m, *tables, None, None,
-                                         effective_key_mask(key_mask, q.device), *carriers)
-            return _GatherAttn.apply(q, k, v, trans_coeff, tau, cfg, key_idx, key_lens_m, *tables)
-        c = _gather_forward(q, k, v, cfg, packed, trans_coeff, tau, key_mask, kv_cache)[0]
-        return (c.out, c.lse) if return_lse else c.out
-    flags = attention_route(tuple(q.shape), k.shape[2], q.dtype, f_dims, so3_degree, Nq, Nk, pretransformed=pretransformed, use_dma=use_dma,
+    how = dict(v_transform=v_transform, euclid=euclid, precise=bool(precise), needs_grad=needs_grad)
+    if masked:          # (key_views and its companions beside a mask were refused above)
+        how.update(key_mask=True, key_mask_backward=bool(key_mask_backward))
+    else:
+        how.update(key_views=key_views is not None, key_views_backward=bool(key_views_backward))
+    flags = attention_route(shape, Tk, q.dtype, f_dims, so3_degree, Nq, Nk, pretransformed=pretransformed, use_dma=use_dma,
                             kv_mode=kv_mode, kv_cache=kv_cache is not None, **how)
-    # no fused kernel: 'staged' or 'apply' (under key_views: 'staged', or it raises)
-    route = generic_route(tuple(q.shape), k.shape[2], q.dtype, f_dims, so3_degree, Nq, Nk, **how) if flags is None else "fused"
-    if key_views is not None and key_lens is None:
-        key_lens = key_lens_tensor(key_views, k.shape[2] // Nk, q.device)
-    if route == "staged":
-        return _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, kv_cache,
-                               key_views=key_views, key_lens=key_lens, return_lse=return_lse)
-    if route == "apply":
-        if return_lse and needs_grad and precise and q.dtype == torch.float32:
-            raise native.GtaError("return_lse under grad with precise=True at this layout: the exact-fp32 backward (gta_plain32) takes no "
-                                  "gradient of the log-sum-exp; the fused fp32-faithful backward (float32, dh <= 64, fused layouts) does")
-        return _generic_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, precise=bool(precise),
-                                carriers=carriers, return_lse=return_lse)
     cfg = ({k_: int(v_) for k_, v_ in f_dims.items()}, int(so3_degree), Nq, Nk, float(scale), flags)
-    tables = [packed.get(t) for t in ("vrep_q", "vrep_k", "cs_q", "cs_k")]
-    if key_views is None:
-        return (_GtaAttnLse if return_lse else _GtaAttn).apply(q, k, v, trans_coeff, tau, kv_cache, cfg, *tables, *carriers)
-    if needs_grad:          # (key_views_backward: anything else was refused above, return_lse included)
-        q_lens = None if query_views is None else key_lens_tensor(query_views, q.shape[2] // Nq, q.device)
-        return _VarlenAttn.apply(q, k, v, trans_coeff, tau, cfg, key_lens, q_lens, (query_views, key_views), *tables, *carriers)
-    c = _varlen_forward(q, k, v, cfg, packed, trans_coeff, tau, key_lens, key_views, kv_cache)[0]
-    return (c.out, c.lse) if return_lse else c.out
+    if masked:           # (attention_route never answers None under a mask: the generic layouts have no gather pre-pass)
+        return "fused" if needs_grad else "forward", cfg, _gather_mask(key_mask, query_mask, q, k, needs_grad, carriers), packed, carriers, \
+            trans_coeff, tau
+    # no fused kernel: 'staged' or 'apply' (under key_views: 'staged', or it raises)
+    route = generic_route(shape, Tk, q.dtype, f_dims, so3_degree, Nq, Nk, **how) if flags is None else "fused"
+    if route == "apply" and return_lse and needs_grad and precise and q.dtype == torch.float32:
+        raise native.GtaError("return_lse under grad with precise=True at this layout: the exact-fp32 backward (gta_plain32) takes no "
+                              "gradient of the log-sum-exp; the fused fp32-faithful backward (float32, dh <= 64, fused layouts) does")
+    mask = _NO_MASK
+    if key_views is not None:
+        # (under grad: key_views_backward -- anything else was refused above, return_lse included; query_views masks the backward alone)
+        mask = _views_mask(key_views, key_lens, query_views if needs_grad and route == "fused" else None, q, k, Nq, Nk)
+        route = "forward" if route == "fused" and not needs_grad else route
+    return route, cfg, mask, packed, carriers, trans_coeff, tau
 
 
 class _MergeAttn(torch.autograd.Function):
@@ -1140,6 +1109,13 @@ def gta_attention_merge(outs, lses):
 
 _KEY_SIDE_TABLES = ("vrep_k", "cs_k", "coord_k", "grad_cs_k", "grad_coord_k")
 
+# the keywords of ``gta_attention`` that mask a call, as the layers hand them on: masks and view counts first (absent when None), then the
+# opt-in flags (absent unless set)
+MASK_OPT_INS = ("key_views_backward", "key_mask_backward", "key_mask_rep_grad")
+MASK_KEYWORDS = ("key_views", "key_mask", "query_views", "query_mask") + MASK_OPT_INS
+# what ``gta_attention_by_view_groups`` refuses: the key-side masks among them (a query mask and its opt-ins go to every group's call)
+_NOT_PER_GROUP = ("kv_cache", "key_views", "key_lens", "key_views_backward", "query_views", "return_attmap", "key_mask")
+
 
 def gta_attention_by_view_groups(q, k, v, f_dims: Dict[str, int], packed: dict, *, views_per_call: int, num_key_views: Optional[int] = None,
                                  **kw):
@@ -1151,12 +1127,11 @@ def gta_attention_by_view_groups(q, k, v, f_dims: Dict[str, int], packed: dict, 
     rows are copied per group (vrep_k per view, cs_k / coord_k per token).  The number of key views is that of ``packed['vrep_k']``;
     a layout without view tables says it with ``num_key_views``.  Differentiable wherever ``gta_attention(..., return_lse=True)`` is.  Every
     other keyword goes to ``gta_attention``; ``kv_cache``, ``key_views`` (with its companions), ``key_mask`` and ``return_attmap`` are refused."""
-    for name in ("kv_cache", "key_views", "key_lens", "key_views_backward", "query_views", "return_attmap", "key_mask"):
+    for name in _NOT_PER_GROUP:
         if kw.get(name) is not None and kw.get(name) is not False:
             raise native.GtaError(f"gta_attention_by_view_groups takes no {name}: every group is a call of its own")
     return_lse = bool(kw.get("return_lse", False))
-    kw = {n_: v_ for n_, v_ in kw.items() if n_ not in ("kv_cache", "key_views", "key_lens", "key_views_backward", "query_views", "return_attmap",
-                                                         "return_lse", "key_mask")}
+    kw = {n_: v_ for n_, v_ in kw.items() if n_ not in _NOT_PER_GROUP + ("return_lse",)}
     sizes = None if isinstance(views_per_call, (int, np.integer)) and not isinstance(views_per_call, bool) else views_per_call
     try:
         sizes = None if sizes is None else [int(x) for x in sizes if not isinstance(x, bool) and isinstance(x, (int, np.integer))]
@@ -1234,8 +1209,8 @@ def attention_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree:
     if key_mask:
         if key_views:
             raise native.GtaError("key_mask with key_views: a call takes one key mask")
-        _key_mask_refusals(needs_grad=needs_grad, precise=precise, pretransformed=pretransformed, kv_mode=kv_mode,
-                           key_mask_backward=key_mask_backward)
+        _mask_refusals("key_mask", needs_grad=needs_grad, precise=precise, pretransformed=pretransformed, kv_mode=kv_mode,
+                       backward=key_mask_backward)
         rc = native.attn_fwd_supported(probe(flags))
         if rc == native.E_UNSUPPORTED:
             raise native.GtaError("key_mask: the staged and rho-apply layouts (t2, euclid, so3 of degree 1, unaligned slabs) have no gather "
@@ -1243,8 +1218,8 @@ def attention_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree:
         native.check(native.attn_fwd_gather_supported(probe(flags)), "gta_attn_fwd_gather_supported")
         return flags
     if key_views:
-        _key_views_refusals(needs_grad=needs_grad, precise=precise, pretransformed=pretransformed, kv_mode=kv_mode,
-                            key_views_backward=key_views_backward)
+        _mask_refusals("key_views", needs_grad=needs_grad, precise=precise, pretransformed=pretransformed, kv_mode=kv_mode,
+                       backward=key_views_backward)
         if native.attn_fwd_supported(probe(flags)) == native.E_UNSUPPORTED:         # a generic layout
             return None
         # a fused layout: what the varlen entry refuses now is a flag (GTA_FLAG_FUSED_KV, ...), and that is said, not routed elsewhere

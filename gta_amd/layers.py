@@ -81,6 +81,10 @@ class FeedForward(nn.Module):
         return self.net(x)
 
 
+# the masks among gta.MASK_KEYWORDS, and what the paths without one (the elementwise_mul ablation, the dense attention map) say they lack
+_MASKS = {"key_views": "per-scene key mask", "key_mask": "key mask", "query_mask": "query mask"}
+
+
 class Attention(nn.Module):
     """GTA multi-head attention (layers.py:172-444, ``method == 'gta'`` branch)."""
 
@@ -158,12 +162,9 @@ class Attention(nn.Module):
         B, H, Tq, dh = q.shape
         tau = self.attend.tau if self.attend is not None else None
         if self.elementwise_mul:                                          # layers.py:410-419
-            if extras.get("key_views") is not None:
-                raise _gta.native.GtaError("key_views: the elementwise_mul ablation has no per-scene key mask")
-            if extras.get("key_mask") is not None:
-                raise _gta.native.GtaError("key_mask: the elementwise_mul ablation has no key mask")
-            if extras.get("query_mask") is not None:
-                raise _gta.native.GtaError("query_mask: the elementwise_mul ablation has no query mask")
+            for name, what in _MASKS.items():
+                if extras.get(name) is not None:
+                    raise _gta.native.GtaError(f"{name}: the elementwise_mul ablation has no {what}")
             ex = dict(vecrep_q=self.rep_to_vec(extras["flattened_rep_q"]), vecrep_k=self.rep_to_vec(extras["flattened_rep_k"]),
                       vecinvrep_q=self.rep_to_vec(extras["flattened_invrep_q"]))
             out, _ = _gta.multihead_vecrep_attention(q, k, v, attn_fn=self, extras=ex, tau=tau)
@@ -173,35 +174,25 @@ class Attention(nn.Module):
                 attn = _gta.attention_map(ex["vecrep_q"][:, None] * q, ex["vecrep_k"][:, None] * k, {"triv": dh}, {},
                                           tau=tau, scale=self.scale)
             return out, attn
-        # per-scene numbers of valid input views (srt.TransformingSRT's input_views): absent by default
-        key_views = extras.get("key_views") if extras is not None else None
-        if key_views is not None and return_attmap:
-            raise _gta.native.GtaError("key_views with return_attmap: the dense attention map has no per-scene key mask")
-        # a bool [B, Tk] mask of the keys to attend (srt.TransformingSRT's input_mask): absent by default
-        key_mask = extras.get("key_mask") if extras is not None else None
-        if key_mask is not None and return_attmap:
-            raise _gta.native.GtaError("key_mask with return_attmap: the dense attention map has no key mask")
-        # (training on such batches) the opt-in backward, and the valid query views of a self-attention layer -- both absent by default
-        kvb = bool(extras.get("key_views_backward")) if extras is not None else False
-        kmb = bool(extras.get("key_mask_backward")) if extras is not None else False
-        # (refining poses through such batches) pose / coordinate gradients under the masks: srt.TransformingSRT's input_mask_rep_grad
-        kmr = bool(extras.get("key_mask_rep_grad")) if extras is not None else False
-        query_views = extras.get("query_views") if extras is not None else None
-        # a bool [B, Tq] mask of the live query rows (srt.TransformingSRT's input_mask_queries, self-attention layers): absent by default
-        query_mask = extras.get("query_mask") if extras is not None else None
-        if query_mask is not None and return_attmap:
-            raise _gta.native.GtaError("query_mask with return_attmap: the dense attention map has no query mask")
+        # the mask keywords (set by srt.TransformingSRT: input_views, input_mask, input_mask_queries, their opt-in backwards and
+        # input_mask_rep_grad), all absent by default: a mask or view count goes on when it is there, an opt-in flag as True when it is set
+        masks = {}
+        for name in _gta.MASK_KEYWORDS if extras is not None else ():
+            val = extras.get(name)
+            if name in _gta.MASK_OPT_INS:
+                val = True if val else None
+            if val is not None:
+                masks[name] = val
+        for name, what in _MASKS.items():
+            if name in masks and return_attmap:
+                raise _gta.native.GtaError(f"{name} with return_attmap: the dense attention map has no {what}")
         packed = _gta.pack_reps(extras, self.f_dims)
         out = _gta.gta_attention(
             q, k, v, self.f_dims, packed,
             so3_degree=_gta._so3_degree(self.f_dims, packed, extras),
             trans_coeff=self.trans_coeff, tau=tau,
             scale=self.scale, v_transform=self.method_args.get("v_transform", True), euclid=self.euclid,
-            kv_cache=kv_cache, precise=self.precise and q.dtype == torch.float32 and kv_cache is None,
-            **({"key_views": key_views} if key_views is not None else {}), **({"key_mask": key_mask} if key_mask is not None else {}),
-            **({"key_views_backward": True} if kvb else {}), **({"query_views": query_views} if query_views is not None else {}),
-            **({"key_mask_backward": True} if kmb else {}), **({"query_mask": query_mask} if query_mask is not None else {}),
-            **({"key_mask_rep_grad": True} if kmr else {}))
+            kv_cache=kv_cache, precise=self.precise and q.dtype == torch.float32 and kv_cache is None, **masks)
         out = out.permute(0, 2, 1, 3).reshape(B, Tq, H * dh)              # free: out is [B,Tq,H,dh] in memory
         attn = None
         if return_attmap:                                                  # layers.py:441-442

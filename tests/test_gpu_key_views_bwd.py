@@ -191,7 +191,7 @@ def test_bits_of_the_scene_alone(run, side, dtype):
         tc = c.tc.clone().requires_grad_() if c.tc is not None else None
         ta = torch.tensor([TAU], device="cuda", requires_grad=True)
         cfg = ({k_: int(v_) for k_, v_ in c.f_dims.items()}, int(c.so3), 1 if side == "dec" else n, n, float(c.scale), flags)
-        out = G2._GtaAttn.apply(q, k, v, tc, ta, None, cfg, pk.get("vrep_q"), pk.get("vrep_k"), pk.get("cs_q"), pk.get("cs_k"))
+        out = G2._FusedAttn.apply(q, k, v, tc, ta, (cfg, None, G2._Mask()), pk.get("vrep_q"), pk.get("vrep_k"), pk.get("cs_q"), pk.get("cs_k"))
         out.backward(w[b:b + 1, :, :rows].to(out.dtype))
         torch.cuda.synchronize()
         assert torch.equal(q.grad[0], dq[b, :, :rows]), (run, side, dtype, b, "dq")

@@ -115,7 +115,7 @@ def test_padding_is_never_read(run, side, dtype):
 
 @pytest.mark.parametrize("run, side, dtype", CASES)
 def test_scene_alone(run, side, dtype):
-    """4. against `_GtaAttn` on scene b alone with keys, queries (encoder leg) and tables cut to the prefixes, on the same kernels (the
+    """4. against the unmasked `_FusedAttn` on scene b alone with keys, queries (encoder leg) and tables cut to the prefixes, on the same kernels (the
     flags of test_bits_of_the_scene_alone): each leaf gradient within 1e-6 of max |ref|"""
     c = _case(run, side, dtype)
     grads, _ = _got(run, side, dtype)
@@ -130,8 +130,8 @@ def test_scene_alone(run, side, dtype):
         q, k, v = c.dev
         q, k, v = (t.detach().clone().requires_grad_() for t in (q[b:b + 1, :, :rows], k[b:b + 1, :, :n * PK], v[b:b + 1, :, :n * PK]))
         cfg = ({k_: int(v_) for k_, v_ in c.f_dims.items()}, int(c.so3), 1 if side == "dec" else n, n, float(c.scale), flags)
-        out = G2._GtaAttn.apply(q, k, v, c.tc, None, None, cfg, packed.get("vrep_q"), packed.get("vrep_k"), packed.get("cs_q"),
-                                packed.get("cs_k"), *carriers)
+        out = G2._FusedAttn.apply(q, k, v, c.tc, None, (cfg, None, G2._Mask()), packed.get("vrep_q"), packed.get("vrep_k"), packed.get("cs_q"),
+                                  packed.get("cs_k"), *carriers)
         out.backward(w[b:b + 1, :, :rows].to(out.dtype))
         torch.cuda.synchronize()
         for name in _leaf_names(side):

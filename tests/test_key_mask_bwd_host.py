@@ -1,7 +1,7 @@
 """Host side of the backward through a key mask (`gta_attention(..., key_mask=m, key_mask_backward=True)`, `gta_attn_bwd_gather`): the two
 exported symbols and their ctypes signatures against include/gta_hip.h, the refusals of the new entry (the rows tests/test_abi_refusals.py pins
 for `gta_attn_bwd_varlen`, repeated, plus the null `key_idx`), the refused combinations of the Python layer (each raises `GtaError` naming its
-reason before anything is launched -- these tests run without a GPU, on CPU tensors), the autograd wiring of `_GatherAttn` with the two native
+reason before anything is launched -- these tests run without a GPU, on CPU tensors), the autograd wiring of `_FusedAttn` under a key mask with the two native
 calls replaced, and the flag's way through `layers.Attention` and `TransformingSRT`."""
 import ctypes
 
@@ -170,7 +170,7 @@ def test_routes():
 
 
 def test_autograd_wiring(monkeypatch):
-    """`_GatherAttn` with the two native calls replaced: the forward gets the tensors of key_index_tensors, the backward the same two, the
+    """`_FusedAttn` under a key mask with the two native calls replaced: the forward gets the tensors of key_index_tensors, the backward the same two, the
     forward's workspace as kv_images and no q_lens; five gradients come back"""
     seen = {}
 

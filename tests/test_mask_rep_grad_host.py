@@ -1,7 +1,7 @@
 """Host side of pose and coordinate gradients under key and query masks (`gta_attention(..., key_mask_rep_grad=True)`): without the keyword
 the old refusal stands word for word; the new refusals name their reasons before anything is launched (these tests run without a GPU, on CPU
 tensors); `repgrad.table_grads(masks=)` on the CPU with `native.rep_grad_sums` replaced by a torch fp64 sum; the autograd wiring of
-`_GatherAttn` with carriers, natives replaced; the effective key mask; the keyword's way through `layers.Attention` and `TransformingSRT`."""
+`_FusedAttn` under the masks with carriers, natives replaced; the effective key mask; the keyword's way through `layers.Attention` and `TransformingSRT`."""
 from types import SimpleNamespace
 
 import pytest
@@ -201,7 +201,7 @@ def test_effective_key_mask():
 # ---- autograd wiring --------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("with_query_mask", [False, True])
 def test_autograd_wiring(monkeypatch, with_query_mask):
-    """`_GatherAttn` with carriers, the native calls and `table_grads` replaced: the backward hands table_grads the pairs (q, dq), (dout, out)
+    """`_FusedAttn` under the masks with carriers, the native calls and `table_grads` replaced: the backward hands table_grads the pairs (q, dq), (dout, out)
     and (dk, k), (dv, v), direct=False and masks=(q_live, k_live) -- the objects the forward was given --, and its six results come back as the
     carriers' gradients beside the five others"""
     seen = {}
@@ -238,8 +238,8 @@ def test_autograd_wiring(monkeypatch, with_query_mask):
     q_live, q_lens = G2.query_mask_tensors(torch.ones(B, TQ, dtype=torch.bool), "cpu") if with_query_mask else (None, None)
     flags = G2.attention_route((B, H, TQ, 64), TK, torch.float32, CL, 0, 1, NK, key_mask=True, needs_grad=True, key_mask_backward=True)
     cfg = (dict(CL), 0, 1, NK, 0.125, flags)
-    out = G2._GatherAttn.apply(q, k, v, tc, ta, cfg, key_idx, key_lens, packed["vrep_q"], packed["vrep_k"], packed["cs_q"], packed["cs_k"],
-                               q_live, q_lens, k_live, *carriers)
+    mask = G2._Mask("gather", key_idx=key_idx, key_lens=key_lens, q_live=q_live, q_lens=q_lens, k_live=k_live)
+    out = G2._FusedAttn.apply(q, k, v, tc, ta, (cfg, None, mask), packed["vrep_q"], packed["vrep_k"], packed["cs_q"], packed["cs_k"], *carriers)
     out.sum().backward()
     desc, tables, meta, q_pairs, k_pairs, direct, kw = seen["tg"]
     assert direct is False and set(kw) == {"masks"} and kw["masks"][0] is q_live and kw["masks"][1] is k_live
@@ -254,10 +254,17 @@ def test_autograd_wiring(monkeypatch, with_query_mask):
     assert cs_q.grad is None
 
 
+def _mask_and_carriers(args):
+    """of the arguments `_FusedAttn.apply` got: the mask record of its one non-tensor argument (cfg, kv_cache, mask), and the carriers"""
+    (cfg, kv_cache, mask), = [a for a in args if isinstance(a, tuple)]
+    assert mask.kind == "gather" and kv_cache is None
+    return mask, tuple(args[G2._FusedAttn.CARRIERS:])
+
+
 def test_gta_attention_uploads_the_mask_once_and_hands_it_on(monkeypatch):
     """the public call: k_live is built beside key_idx / key_lens (None for the all-True mask of a query_mask-only call), the carriers go in"""
     got = []
-    monkeypatch.setattr(G2._GatherAttn, "apply", staticmethod(lambda *a: got.append(a) or torch.zeros(1)))
+    monkeypatch.setattr(G2._FusedAttn, "apply", staticmethod(lambda *a: got.append(a) or torch.zeros(1)))
     monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))             # (the carriers' device check, nothing else here)
     monkeypatch.setattr(G2, "attention_route", lambda *a, **k: native.FLAG_V_TRANSFORM)
     q = torch.zeros(B, H, TK, 64, requires_grad=True)
@@ -268,15 +275,16 @@ def test_gta_attention_uploads_the_mask_once_and_hands_it_on(monkeypatch):
     for kw, want_k, want_q in (({"key_mask": km}, True, False), ({"key_mask": km, "query_mask": qm}, True, True), ({"query_mask": qm}, False, True)):
         got.clear()
         gta_amd.gta_attention(q, q, q, CL, packed, key_mask_backward=True, key_mask_rep_grad=True, **kw)
-        a = got[0]
-        assert len(a) == 15 + 6 and a[15] is packed["vrep_q"] and a[16] is None
-        assert (a[12] is not None) == want_q and (a[14] is not None) == want_k
+        mask, carriers = _mask_and_carriers(got[0])
+        assert len(carriers) == 6 and carriers[0] is packed["vrep_q"] and carriers[1] is None
+        assert (mask.q_live is not None) == want_q and (mask.k_live is not None) == want_k
         if want_k:
-            assert torch.equal(a[14], km) and a[14].dtype == torch.bool
+            assert torch.equal(mask.k_live, km) and mask.k_live.dtype == torch.bool
     # without tables that require grad nothing is built
     got.clear()
     gta_amd.gta_attention(q, q, q, CL, {k_: v_.detach() for k_, v_ in packed.items()}, key_mask=km, key_mask_backward=True, key_mask_rep_grad=True)
-    assert len(got[0]) == 12
+    mask, carriers = _mask_and_carriers(got[0])
+    assert carriers == () and mask.k_live is None and mask.q_live is None and mask.q_lens is None
 
 
 # ---- the keyword's way down ---------------------------------------------------------------------------------------------------------------------------

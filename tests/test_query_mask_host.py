@@ -1,7 +1,7 @@
 """Host side of the query-side mask (`gta_attention(..., query_mask=m)`, `gta_attn_fwd_qmask` / `gta_attn_bwd_qmask`): the four exported symbols
 and their ctypes signatures against include/gta_hip.h, the null `q_live`, the refused combinations of the Python layer (each raises `GtaError`
 naming its reason before anything is launched -- these tests run without a GPU, on CPU tensors), `query_mask_tensors` on hand-made masks, the
-autograd wiring of `_GatherAttn` with the native calls replaced, and the mask's way through `layers.Attention` and `TransformingSRT`."""
+autograd wiring of `_FusedAttn` under the masks with the native calls replaced, and the mask's way through `layers.Attention` and `TransformingSRT`."""
 import ctypes
 
 import pytest
@@ -163,7 +163,7 @@ def test_attn_bwd_takes_q_live_with_the_gather():
 # ---- autograd wiring ----------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("with_key_mask", [True, False])
 def test_autograd_wiring(monkeypatch, with_key_mask):
-    """`_GatherAttn` with the native calls replaced: the same q_live / q_lens objects reach gta_attn_fwd_qmask and gta_attn_bwd_qmask, beside the
+    """`_FusedAttn` under the masks with the native calls replaced: the same q_live / q_lens objects reach gta_attn_fwd_qmask and gta_attn_bwd_qmask, beside the
     key tensors (without key_mask: an arange and the full count) and the forward's workspace as kv_images; without query_mask neither appears"""
     seen = {}
 
@@ -325,3 +325,26 @@ def test_the_encoder_selects_masked_tokens_away():
             enc(images, None, None, {"query_mask": torch.ones(2, 9, dtype=torch.bool)})
     finally:
         S.pre_compute_reps_encoder = real
+
+
+def test_view_groups_hand_the_query_mask_to_every_group(monkeypatch):
+    """`gta_attention_by_view_groups` refuses the key-side masks (every group is a call of its own) but serves a query mask: it goes, with its
+    opt-ins, to each group's `gta_attention` call as it was given"""
+    seen = []
+
+    def fake(q, k, v, f_dims, packed, **kw):
+        seen.append(kw)
+        return torch.zeros(q.shape), torch.zeros(q.shape[:3])
+
+    monkeypatch.setattr(G2, "gta_attention", fake)
+    monkeypatch.setattr(G2, "gta_attention_merge", lambda outs, lses: (outs[0], lses[0]))
+    q, k = torch.zeros(B, H, TQ, 64), torch.zeros(B, H, TK, 64)
+    packed = {"vrep_q": torch.zeros(B, 1, native.VREP_STRIDE), "vrep_k": torch.zeros(B, NK, native.VREP_STRIDE)}
+    qm = _qm()
+    out = G2.gta_attention_by_view_groups(q, k, k, CL, packed, views_per_call=2, query_mask=qm, key_mask_backward=True, key_mask_rep_grad=True)
+    assert tuple(out.shape) == (B, H, TQ, 64) and len(seen) == -(-NK // 2)
+    for kw in seen:
+        assert kw["query_mask"] is qm and kw["key_mask_backward"] is True and kw["key_mask_rep_grad"] is True and kw["return_lse"] is True
+    for name, val in (("key_mask", _mask()), ("key_views", [1] * B), ("kv_cache", {})):
+        with pytest.raises(native.GtaError, match=f"gta_attention_by_view_groups takes no {name}"):
+            G2.gta_attention_by_view_groups(q, k, k, CL, packed, views_per_call=2, query_mask=qm, **{name: val})
