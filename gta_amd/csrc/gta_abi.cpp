@@ -27,6 +27,8 @@ int gta_fwd2_dispatch(GtaFwdParams& p, const GtaFwdSel& s, int dhp, int esz, boo
 int gta_bwd_dispatch(const GtaBwdParams& p, const float* dlse, int dhp, int esz, hipStream_t stream);
 int gta_merge_dispatch(const GtaMergeParams& p, int esz, hipStream_t stream);
 int gta_merge_bwd_dispatch(const GtaMergeBwdParams& p, int esz, hipStream_t stream);
+int gta_maskidx_dispatch(const uint8_t* key_mask, int B, int Tk, int32_t* key_idx, int32_t* key_lens, uint8_t* k_live,
+                         const uint8_t* query_mask, int Tq, int32_t* q_lens, hipStream_t stream);
 int gta_bwd_varlen_dispatch(const GtaBwdParams& p, const int32_t* key_lens, const int32_t* q_lens, int dhp, int esz, hipStream_t stream);
 int gta_bwd_gather_dispatch(const GtaBwdParams& p, const int32_t* key_idx, const int32_t* key_lens, int dhp, int esz, hipStream_t stream);
 int gta_bwd_qmask_dispatch(const GtaBwdParams& p, const int32_t* key_idx, const int32_t* key_lens, const int32_t* q_lens, const uint8_t* q_live,
@@ -679,6 +681,21 @@ extern "C" int gta_attn_merge_bwd(int32_t dtype, int32_t n, int32_t B, int32_t H
     return launch_status(gta_merge_bwd_dispatch(p, esz, (hipStream_t)stream), "no kernel instance");
 }
 
+// ---------------------------------------------------------------------------------------------
+// index tensors of a key mask and a query mask (gta_maskidx.hip)
+// ---------------------------------------------------------------------------------------------
+extern "C" int gta_mask_index(const uint8_t* key_mask, int32_t B, int32_t Tk, int32_t* key_idx, int32_t* key_lens, uint8_t* k_live,
+                              const uint8_t* query_mask, int32_t Tq, int32_t* q_lens, void* stream) {
+    if (B < 1) return fail(GTA_E_BADARG, "B must be at least 1");
+    if (!key_mask && !query_mask) return fail(GTA_E_BADARG, "null key_mask and null query_mask: one of the two is needed");
+    if (key_mask && Tk < 1) return fail(GTA_E_BADARG, "Tk must be at least 1 with a key_mask");
+    if (query_mask && Tq < 1) return fail(GTA_E_BADARG, "Tq must be at least 1 with a query_mask");
+    if (key_mask && !key_idx) return fail(GTA_E_BADARG, "null key_idx (a key_mask comes with key_idx and key_lens)");
+    if (key_mask && !key_lens) return fail(GTA_E_BADARG, "null key_lens (a key_mask comes with key_idx and key_lens)");
+    if (query_mask && !q_lens) return fail(GTA_E_BADARG, "null q_lens (a query_mask comes with q_lens)");
+    return launch_status(gta_maskidx_dispatch(key_mask, B, Tk, key_idx, key_lens, k_live, query_mask, Tq, q_lens, (hipStream_t)stream),
+                         "no kernel instance");
+}
 
 // ---------------------------------------------------------------------------------------------
 // plain attention (identity layout) with an optional key bias: the attention stage of the generic path

@@ -635,6 +635,82 @@ def _all_keys_tensors(B: int, Tk: int, device) -> Tuple[torch.Tensor, torch.Tens
             torch.full((B,), Tk, dtype=torch.int32, device=device))
 
 
+class MaskIndex(namedtuple("_MaskIndexFields", "key_mask query_mask key_idx key_lens k_live q_live q_lens", defaults=(None,) * 7)):
+    """Everything the masked kernels read of a key mask and / or a query mask, built once (``mask_index``) and handed to every
+    ``gta_attention`` call on those masks as its ``mask_index`` companion -- all layers of a step share one record.  Immutable.
+      key_mask, query_mask   the very mask objects it was built from (``gta_attention`` compares by identity: no compare, no sync)
+      key_idx [B, Tk] int32, key_lens [B] int32   ``key_index_tensors``
+      k_live [B, Tk] bool    ``effective_key_mask``: the mask with token 0 of a scene without a live key set
+      q_live [B, Tq] bool, q_lens [B] int32       ``query_mask_tensors``: the query mask, contiguous, on the device; its last live row + 1
+    The fields of an absent side are None: that is every record ``mask_index`` returns.  One more shape is accepted by ``gta_attention`` and
+    made by no constructor here: a record WITHOUT a key mask (``key_mask`` and ``k_live`` None) that still carries ``key_idx`` / ``key_lens``
+    -- the index of every key (an arange per scene, the full count), which a call under a query mask alone otherwise builds itself on each
+    call; a caller who keeps that pair puts it into the record with ``_replace`` and the call then builds nothing."""
+    __slots__ = ()
+
+    def keys_only(self) -> "MaskIndex":
+        """the record of the same ``key_mask`` without a query side (a decoder behind an encoder with a query mask): the same key tensors,
+        nothing launched"""
+        return self._replace(query_mask=None, q_live=None, q_lens=None)
+
+
+def _on_device(mask, device, name):
+    if mask.is_cuda and mask.device != device:
+        raise native.GtaError(f"{name} lives on {mask.device}, the call on {device}")
+    return mask.contiguous().to(device, non_blocking=True)
+
+
+def mask_index(key_mask: Optional[torch.Tensor] = None, query_mask: Optional[torch.Tensor] = None, *, device) -> MaskIndex:
+    """The ``MaskIndex`` of ``key_mask`` (bool [B, Tk]) and / or ``query_mask`` (bool [B, Tq]) on ``device``: ONE launch
+    (``gta_mask_index``, gta_maskidx.hip) on the current stream in place of ``key_index_tensors``, ``query_mask_tensors`` and
+    ``effective_key_mask``, with their results bit for bit.  Validation as there: a CPU key mask has its values looked at (a scene without
+    a valid key raises) and is uploaded; a CUDA mask is never read on the host -- a scene of it without a valid key attends its token 0.
+    The same tensor may be both masks (self-attention over padded tokens): it is passed for both sides."""
+    if key_mask is None and query_mask is None:
+        raise native.GtaError("mask_index needs a key_mask or a query_mask")
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    km = qm = None
+    if key_mask is not None:
+        check_key_mask(key_mask)
+        km = _on_device(key_mask, device, "key_mask")
+    if query_mask is not None:
+        check_query_mask(query_mask)
+        qm = km if query_mask is key_mask else _on_device(query_mask, device, "query_mask")
+    if km is not None and qm is not None and km.shape[0] != qm.shape[0]:
+        raise native.GtaError(f"key_mask has {km.shape[0]} scenes, query_mask {qm.shape[0]}")
+    B = (km if km is not None else qm).shape[0]
+    key_idx = key_lens = k_live = q_lens = None
+    if km is not None:
+        key_idx = torch.empty(km.shape, dtype=torch.int32, device=device)
+        key_lens = torch.empty(B, dtype=torch.int32, device=device)
+        k_live = torch.empty(km.shape, dtype=torch.bool, device=device)
+    if qm is not None:
+        q_lens = torch.empty(B, dtype=torch.int32, device=device)
+    native.mask_index(km, key_idx, key_lens, k_live, qm, q_lens)
+    return MaskIndex(key_mask, query_mask, key_idx, key_lens, k_live, qm, q_lens)
+
+
+def _check_mask_index(mi, key_mask, query_mask, B, Tq, Tk, device):
+    """``gta_attention``'s ``mask_index`` is a companion of its masks, as ``key_lens`` is of ``key_views``: accepted only beside the very mask
+    objects it was built from (identity: nothing is compared, nothing syncs), complete for each side it has, and on the call's device.
+    (The masks' shapes were held against B, Tq, Tk before; a record without a key side may still carry the index of every key,
+    ``_all_keys_tensors``, which the call builds itself otherwise.)"""
+    def fits(t, shape, dtype):
+        return torch.is_tensor(t) and t.device == device and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous()
+    ok = isinstance(mi, MaskIndex) and (key_mask is not None or query_mask is not None) and mi.key_mask is key_mask and mi.query_mask is query_mask
+    if ok and (key_mask is not None or mi.key_idx is not None):
+        ok = fits(mi.key_idx, (B, Tk), torch.int32) and fits(mi.key_lens, (B,), torch.int32)
+    if ok and key_mask is not None:
+        ok = fits(mi.k_live, (B, Tk), torch.bool)
+    if ok and query_mask is not None:
+        ok = fits(mi.q_live, (B, Tq), torch.bool) and fits(mi.q_lens, (B,), torch.int32)
+    if not ok:
+        raise native.GtaError("mask_index comes with the key_mask / query_mask it was built from (gta_amd.mask_index(key_mask, query_mask, "
+                              "device=q.device): the same mask objects, no key_views, tensors on the call's device)")
+
+
 def _plan_key(family: str, flags, dt, B, H, Tk, dh, f_dims, so3_degree, Nk, scale, key_views):
     """what the images of a cache depend on besides the keys, reps and trans_coeff (the caller's contract, see gta_attention): the family
     ('fused' / 'staged': different tile images), the key side's shape and layout, the dtype (bf16 / fp32 inputs pick different instances), the
@@ -710,9 +786,16 @@ def _views_mask(key_views, key_lens, query_views, q, k, Nq, Nk) -> _Mask:
     return _Mask("views", key_lens=key_lens, q_lens=q_lens, views=(query_views, key_views))
 
 
-def _gather_mask(key_mask, query_mask, q, k, needs_grad, carriers) -> _Mask:
+def _gather_mask(key_mask, query_mask, q, k, needs_grad, carriers, mask_index=None) -> _Mask:
     """``key_mask`` and / or ``query_mask`` (both validated).  A query mask without a key mask runs under an all-True one; a forward-only call
-    without a query mask leaves the key tensors to the launcher."""
+    without a query mask leaves the key tensors to the launcher.  ``mask_index`` (checked: ``_check_mask_index``): the record's tensors
+    stand where this would build them -- the very objects, on every path -- and nothing is built but the all-True index it does not carry."""
+    if mask_index is not None:
+        key_idx, key_lens = mask_index.key_idx, mask_index.key_lens
+        if key_idx is None:
+            key_idx, key_lens = _all_keys_tensors(q.shape[0], k.shape[2], q.device)
+        k_live = mask_index.k_live if needs_grad and carriers and key_mask is not None else None
+        return _Mask("gather", key_idx, key_lens, mask_index.q_live, mask_index.q_lens, k_live)
     if query_mask is None and not needs_grad:
         return _Mask("gather", key_mask=key_mask)
     q_live, q_lens = (None, None) if query_mask is None else query_mask_tensors(query_mask, q.device)
@@ -864,7 +947,8 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
                   kv_mode: str = "auto", kv_cache: Optional[dict] = None, precise: Optional[bool] = None,
                   key_views=None, key_lens: Optional[torch.Tensor] = None, key_views_backward: bool = False,
                   query_views=None, return_lse: bool = False, key_mask: Optional[torch.Tensor] = None, key_mask_backward: bool = False,
-                  query_mask: Optional[torch.Tensor] = None, key_mask_rep_grad: bool = False):
+                  query_mask: Optional[torch.Tensor] = None, key_mask_rep_grad: bool = False,
+                  mask_index: Optional[MaskIndex] = None):
     """Fused GTA attention on packed reps.  q [B,H,Tq,dh], k/v [B,H,Tk,dh] -> out [B,H,Tq,dh].
 
     kv_mode: 'prepass' = K/V rep pre-pass + lean attention kernel (two launches; at dh = 96 in the MSN layout the attention kernel is
@@ -941,12 +1025,18 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
              an arange (no sort) -- and with everything that route refuses: under grad it needs ``key_mask_backward=True``.  Refused by
              name: ``key_views`` / ``query_views`` / ``key_lens`` / ``key_views_backward`` beside it, ``kv_cache``, and what ``key_mask``
              refuses.  ``return_lse`` without grad is served.
+    mask_index: the ``MaskIndex`` of this call's ``key_mask`` / ``query_mask`` (``gta_amd.mask_index``: one launch builds every tensor the
+             masked kernels read) -- a companion of the masks, as ``key_lens`` is of ``key_views``.  The call then builds nothing from the
+             masks: forward, ``kv_cache``, backward and the rep-gradient pass run on the record's tensors, so one record serves every layer of
+             a step, with results bit for bit those of the call without it.  The masks are still passed and every refusal above runs on
+             them as before; the record is accepted only beside the very mask objects it was built from (an identity check: no compare,
+             no sync) and on the call's device, anything else raises ``GtaError``.
     """
     route, cfg, mask, packed, carriers, trans_coeff, tau = _resolve(
         q, k, v, f_dims, packed, so3_degree=so3_degree, trans_coeff=trans_coeff, tau=tau, scale=scale, v_transform=v_transform, euclid=euclid,
         pretransformed=pretransformed, use_dma=use_dma, kv_mode=kv_mode, kv_cache=kv_cache, precise=precise, key_views=key_views,
         key_lens=key_lens, key_views_backward=key_views_backward, query_views=query_views, return_lse=return_lse, key_mask=key_mask,
-        key_mask_backward=key_mask_backward, query_mask=query_mask, key_mask_rep_grad=key_mask_rep_grad)
+        key_mask_backward=key_mask_backward, query_mask=query_mask, key_mask_rep_grad=key_mask_rep_grad, mask_index=mask_index)
     scale = cfg[4]
     if route == "staged":
         return _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, kv_cache,
@@ -968,7 +1058,7 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
 
 def _resolve(q, k, v, f_dims, packed, *, so3_degree, trans_coeff, tau, scale, v_transform, euclid, pretransformed, use_dma, kv_mode, kv_cache,
              precise, key_views, key_lens, key_views_backward, query_views, return_lse, key_mask, key_mask_backward, query_mask,
-             key_mask_rep_grad):
+             key_mask_rep_grad, mask_index=None):
     """The host-only half of ``gta_attention`` (its arguments, the keyword-only ones by keyword): every refusal, in a fixed order, then how the call runs.
     -> (route, cfg, mask, packed, carriers, trans_coeff, tau): route 'fused' (through ``_FusedAttn``: every unmasked call, a masked one under
     grad), 'forward' (a masked call without grad: ``_fused_forward`` alone), 'staged' or 'apply' (``generic_route``);
@@ -1047,10 +1137,12 @@ def _resolve(q, k, v, f_dims, packed, *, so3_degree, trans_coeff, tau, scale, v_
         how.update(key_views=key_views is not None, key_views_backward=bool(key_views_backward))
     flags = attention_route(shape, Tk, q.dtype, f_dims, so3_degree, Nq, Nk, pretransformed=pretransformed, use_dma=use_dma,
                             kv_mode=kv_mode, kv_cache=kv_cache is not None, **how)
+    if mask_index is not None:          # (behind every refusal of the masks themselves: their messages are what they were)
+        _check_mask_index(mask_index, key_mask, query_mask, B, Tq, Tk, q.device)
     cfg = ({k_: int(v_) for k_, v_ in f_dims.items()}, int(so3_degree), Nq, Nk, float(scale), flags)
     if masked:           # (attention_route never answers None under a mask: the generic layouts have no gather pre-pass)
-        return "fused" if needs_grad else "forward", cfg, _gather_mask(key_mask, query_mask, q, k, needs_grad, carriers), packed, carriers, \
-            trans_coeff, tau
+        mask = _gather_mask(key_mask, query_mask, q, k, needs_grad, carriers, mask_index)
+        return "fused" if needs_grad else "forward", cfg, mask, packed, carriers, trans_coeff, tau
     # no fused kernel: 'staged' or 'apply' (under key_views: 'staged', or it raises)
     route = generic_route(shape, Tk, q.dtype, f_dims, so3_degree, Nq, Nk, **how) if flags is None else "fused"
     if route == "apply" and return_lse and needs_grad and precise and q.dtype == torch.float32:
@@ -1112,9 +1204,9 @@ _KEY_SIDE_TABLES = ("vrep_k", "cs_k", "coord_k", "grad_cs_k", "grad_coord_k")
 # the keywords of ``gta_attention`` that mask a call, as the layers hand them on: masks and view counts first (absent when None), then the
 # opt-in flags (absent unless set)
 MASK_OPT_INS = ("key_views_backward", "key_mask_backward", "key_mask_rep_grad")
-MASK_KEYWORDS = ("key_views", "key_mask", "query_views", "query_mask") + MASK_OPT_INS
+MASK_KEYWORDS = ("key_views", "key_mask", "query_views", "query_mask", "mask_index") + MASK_OPT_INS
 # what ``gta_attention_by_view_groups`` refuses: the key-side masks among them (a query mask and its opt-ins go to every group's call)
-_NOT_PER_GROUP = ("kv_cache", "key_views", "key_lens", "key_views_backward", "query_views", "return_attmap", "key_mask")
+_NOT_PER_GROUP = ("kv_cache", "key_views", "key_lens", "key_views_backward", "query_views", "return_attmap", "key_mask", "mask_index")
 
 
 def gta_attention_by_view_groups(q, k, v, f_dims: Dict[str, int], packed: dict, *, views_per_call: int, num_key_views: Optional[int] = None,
@@ -1126,7 +1218,7 @@ def gta_attention_by_view_groups(q, k, v, f_dims: Dict[str, int], packed: dict, 
     K and V of a group are token slices of k and v (tokens are view-major: no copy where the slice keeps 16-byte rows); the key-side tables'
     rows are copied per group (vrep_k per view, cs_k / coord_k per token).  The number of key views is that of ``packed['vrep_k']``;
     a layout without view tables says it with ``num_key_views``.  Differentiable wherever ``gta_attention(..., return_lse=True)`` is.  Every
-    other keyword goes to ``gta_attention``; ``kv_cache``, ``key_views`` (with its companions), ``key_mask`` and ``return_attmap`` are refused."""
+    other keyword goes to ``gta_attention``; ``kv_cache``, ``key_views`` (with its companions), ``key_mask``, ``mask_index`` and ``return_attmap`` are refused."""
     for name in _NOT_PER_GROUP:
         if kw.get(name) is not None and kw.get(name) is not False:
             raise native.GtaError(f"gta_attention_by_view_groups takes no {name}: every group is a call of its own")

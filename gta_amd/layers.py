@@ -82,7 +82,7 @@ class FeedForward(nn.Module):
 
 
 # the masks among gta.MASK_KEYWORDS, and what the paths without one (the elementwise_mul ablation, the dense attention map) say they lack
-_MASKS = {"key_views": "per-scene key mask", "key_mask": "key mask", "query_mask": "query mask"}
+_MASKS = {"key_views": "per-scene key mask", "key_mask": "key mask", "query_mask": "query mask", "mask_index": "mask index"}
 
 
 class Attention(nn.Module):
@@ -175,7 +175,7 @@ class Attention(nn.Module):
                                           tau=tau, scale=self.scale)
             return out, attn
         # the mask keywords (set by srt.TransformingSRT: input_views, input_mask, input_mask_queries, their opt-in backwards and
-        # input_mask_rep_grad), all absent by default: a mask or view count goes on when it is there, an opt-in flag as True when it is set
+        # input_mask_rep_grad; input_mask_index: the masks' ready-made MaskIndex), all absent by default: a mask or view count goes on when it is there, an opt-in flag as True when it is set
         masks = {}
         for name in _gta.MASK_KEYWORDS if extras is not None else ():
             val = extras.get(name)

@@ -54,6 +54,7 @@ ABI_SYMBOLS = (
     "gta_attn_fwd_gather", "gta_attn_fwd_gather_supported",
     "gta_attn_bwd_gather", "gta_attn_bwd_gather_supported",
     "gta_attn_fwd_qmask", "gta_attn_fwd_qmask_supported", "gta_attn_bwd_qmask", "gta_attn_bwd_qmask_supported",
+    "gta_mask_index",
 )
 MERGE_MAX = 8           # partial attentions per gta_attn_merge call
 
@@ -175,6 +176,8 @@ def lib():
         L.gta_attn_merge.argtypes = [c_int32] * 6 + [ctypes.POINTER(c_void_p), P64] * 2 + [c_void_p, P64] * 2 + [c_void_p]
         L.gta_attn_merge_bwd.argtypes = ([c_int32] * 6 + [ctypes.POINTER(c_void_p), P64] * 2 + [c_void_p, P64] * 2
                                          + [ctypes.POINTER(c_void_p), P64] * 2 + [c_void_p])
+        # key side (mask, B, Tk, key_idx, key_lens, k_live), query side (mask, Tq, q_lens), stream
+        L.gta_mask_index.argtypes = [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]
         _lib = L
     return _lib
 
@@ -561,6 +564,31 @@ def attn_merge_bwd(outs, lses, dout, dlse, douts, dlses):
                                    _ptr_array(lses), _strides(*lses), _ptr(dout), _strides(dout), _ptr(dlse),
                                    None if dlse is None else _strides(dlse), _ptr_array(douts), _strides(*douts), _ptr_array(dlses),
                                    _strides(*dlses), _stream()), "gta_attn_merge_bwd")
+
+
+def mask_index(key_mask, key_idx, key_lens, k_live, query_mask, q_lens):
+    """gta_mask_index: one launch -> key_idx [B, Tk] int32, key_lens [B] int32, k_live [B, Tk] bool (or None) of ``key_mask`` (bool [B, Tk])
+    and q_lens [B] int32 of ``query_mask`` (bool [B, Tq]); either mask may be None, not both.  Everything is a contiguous device tensor:
+    the kernel indexes the rows from B, Tk and Tq alone, so the shapes are held against the masks here."""
+    if key_mask is None and query_mask is None:
+        raise GtaError("gta_mask_index needs a key_mask or a query_mask")
+    B = (key_mask if key_mask is not None else query_mask).shape[0]
+    wants = []
+    if key_mask is not None:
+        wants += [("key_mask", key_mask, tuple(key_mask.shape), torch.bool), ("key_idx", key_idx, tuple(key_mask.shape), torch.int32),
+                  ("key_lens", key_lens, (B,), torch.int32)]
+        if k_live is not None:
+            wants.append(("k_live", k_live, tuple(key_mask.shape), torch.bool))
+    if query_mask is not None:
+        wants += [("query_mask", query_mask, (B, query_mask.shape[1] if query_mask.dim() == 2 else -1), torch.bool),
+                  ("q_lens", q_lens, (B,), torch.int32)]
+    for name, t, shape, dtype in wants:
+        if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape or len(shape) != (1 if name.endswith("lens") else 2) \
+                or not t.is_contiguous():
+            raise GtaError(f"gta_mask_index: {name} must be a contiguous {dtype} tensor of shape {shape}")
+    _require_cuda(*(t for _, t, _, _ in wants))
+    check(lib().gta_mask_index(_ptr(key_mask), B, 0 if key_mask is None else key_mask.shape[1], _ptr(key_idx), _ptr(key_lens), _ptr(k_live),
+                               _ptr(query_mask), 0 if query_mask is None else query_mask.shape[1], _ptr(q_lens), _stream()), "gta_mask_index")
 
 
 def attn_bwd_varlen_supported(desc: GtaAttnDesc) -> int:

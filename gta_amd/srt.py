@@ -20,6 +20,7 @@ import torch.nn as nn
 from torch.nn import init
 
 from . import native
+from .gta import mask_index
 from .layers import Transformer
 from .reps import pre_compute_reps_decoder, pre_compute_reps_encoder
 
@@ -187,7 +188,7 @@ class TransformingSRT(nn.Module):
 
     def forward(self, input_images, input_camera_pos, input_rays, target_camera_pos, target_rays, extras=None, input_views=None,
                 input_views_backward=False, input_mask=None, input_mask_backward=False, input_mask_queries=False,
-                input_mask_rep_grad=False):
+                input_mask_rep_grad=False, input_mask_index=False):
         """``input_views``: per-scene numbers of valid input views (a host sequence of length B, each in 1..N) for batches that mix
         view counts: scene b's first ``input_views[b]`` views are its input, the rest of its [N, ...] slots is padding that no valid
         token ever attends to -- in the encoder's self-attention and in the decoder's cross-attention (``gta_attention``'s
@@ -218,7 +219,12 @@ class TransformingSRT(nn.Module):
         under a mask, as before.  True: ``extras['input_transforms']``, ``['input_coord']`` and ``['target_*']`` may require grad
         (``gta_attention``'s ``key_mask_rep_grad``): the extrinsics of a view without a valid token and the coordinates of a masked token
         get exact zeros on every side that carries the mask -- the key side always, the encoder's query side with ``input_mask_queries``.
-        Without ``input_mask_queries`` the encoder's masked tokens are live query rows and send their (finite) share."""
+        Without ``input_mask_queries`` the encoder's masked tokens are live query rows and send their (finite) share.
+
+        ``input_mask_index``: only with ``input_mask``.  False (default): every layer builds the tensors its kernels read from the mask
+        itself, as before.  True: they are built once per forward, in one launch (``gta_amd.mask_index``: the key side, and under
+        ``input_mask_queries`` the query side from the same tensor), and every encoder and decoder layer runs on that one record
+        (``gta_attention``'s ``mask_index``; the decoder on its ``keys_only()``).  Same results bit for bit, forward and backward."""
         extras = {} if extras is None else extras
         if input_mask_backward and input_mask is None:
             raise native.GtaError("input_mask_backward=True comes with input_mask")
@@ -226,6 +232,8 @@ class TransformingSRT(nn.Module):
             raise native.GtaError("input_mask_queries=True comes with input_mask")
         if input_mask_rep_grad and not input_mask_backward:
             raise native.GtaError("input_mask_rep_grad=True comes with input_mask_backward=True")
+        if input_mask_index and input_mask is None:
+            raise native.GtaError("input_mask_index=True comes with input_mask")
         if input_mask is not None:
             if input_views is not None:
                 raise native.GtaError("input_mask with input_views: a call takes one key mask -- a prefix of views is a mask too")
@@ -237,6 +245,8 @@ class TransformingSRT(nn.Module):
                 extras["key_mask_rep_grad"] = True
             if input_mask_queries:
                 extras["query_mask"] = extras["key_mask"]      # (the encoder's layers: Tq = Tk, the same tokens on both sides)
+            if input_mask_index:                               # one record for every layer of this forward
+                extras["mask_index"] = mask_index(extras["key_mask"], extras.get("query_mask"), device=input_images.device)
         if input_views is not None:
             extras = dict(extras)                      # the caller's dict never carries these counts into a later call (as render_image)
             extras["key_views"] = input_views
@@ -248,6 +258,8 @@ class TransformingSRT(nn.Module):
             extras = {k_: v_ for k_, v_ in extras.items() if k_ != "query_views"}      # the decoder's queries are the target rays: all live
         if input_mask_queries:
             extras = {k_: v_ for k_, v_ in extras.items() if k_ != "query_mask"}       # (likewise)
+            if input_mask_index:
+                extras["mask_index"] = extras["mask_index"].keys_only()
         return self.decode(z, target_camera_pos, target_rays, extras=extras)
 
 

@@ -427,6 +427,25 @@ int gta_attn_bwd_qmask(const GtaAttnDesc* desc,
                        float* dtrans_coeff, float* dtau,
                        void* workspace, int64_t workspace_bytes, void* stream);
 
+/* What the masked entries above read, built from the masks in one launch (gta_maskidx.hip; gta_amd.mask_index): one 256-thread workgroup
+ * per (scene, side), no workspace, no atomics (every output element has one writer), nothing read back by the host.
+ *   key_mask: [B, Tk] uint8 on the device (the storage of a contiguous bool tensor), non-zero = the key token is live; or NULL.
+ *   query_mask: [B, Tq] uint8 on the device, non-zero = the query row is live; or NULL.  It may be key_mask itself (then Tq = Tk).  It is
+ *       what the entries above take as q_live, as it is: nothing is written for it but q_lens.
+ *   key_idx: [B, Tk] int32, written whole: row b is a permutation of [0, Tk), scene b's live tokens in ascending order, then its masked
+ *       tokens in ascending order (the indices of a stable sort of the negated mask).  gta_attn_bwd_gather walks the whole row.
+ *   key_lens: [B] int32, the number of live tokens of scene b, unclamped: 0 for a scene without one (the attention kernels clamp to 1).
+ *   k_live: [B, Tk] uint8 or NULL: key_mask as 0 / 1 bytes, with token 0 of a scene without a live token set (the token such a scene
+ *       attends over under the clamp; what gta_rep_grad_sums_masked takes as `live` on the key side).
+ *   q_lens: [B] int32: 1 + the index of scene b's last live query row, 0 for a scene without one.
+ *   Checked before anything touches the device, each GTA_E_BADARG with a gta_strerror text that names the argument: B < 1; both masks
+ *       NULL; a given mask with T < 1 (Tk / Tq of an absent side is not read); key_mask without key_idx or key_lens; query_mask without
+ *       q_lens.  The outputs of an absent side are not touched. */
+int gta_mask_index(const uint8_t* key_mask, int32_t B, int32_t Tk,
+                   int32_t* key_idx, int32_t* key_lens, uint8_t* k_live,
+                   const uint8_t* query_mask, int32_t Tq, int32_t* q_lens,
+                   void* stream);
+
 /* -------------------------------------------------------------------------------------------
  * Gradients of the reps: camera poses and patch coordinates (what autograd over gta.py:134-279 gives the reference's
  * se3rep / inv_se3rep / so2rep / t2rep tensors; the Wigner-D blocks stay detached, gta.py:194-197,267).  A pass after the

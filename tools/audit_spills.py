@@ -186,6 +186,19 @@ def audit_others():
             problems.append(f"{row['kernel']}: {row['scratch']} scratch accesses")
     if n_merge != 4:
         problems.append(f"gta_merge.hip: {n_merge} kernel instances found (expected 4)")
+    # the mask-index kernel (gta_maskidx.hip): one instance, a handful of registers, no scratch of either kind (hard)
+    xtext = _asm("gta_maskidx.hip")
+    n_maskidx = 0
+    for name, _, body, vgpr in _kernels(xtext, r"gta_mask_index_kernel()"):
+        meta = xtext[xtext.index(".amdhsa_kernel " + name):][:4000]
+        private = int(re.search(r"\.amdhsa_private_segment_fixed_size\s+(\d+)", meta).group(1))
+        row = {"kernel": "gta_mask_index_kernel", "vgpr": vgpr, "scratch": body.count("scratch_") + private}
+        report.append(row)
+        n_maskidx += 1
+        if row["scratch"]:
+            problems.append(f"{row['kernel']}: scratch in use ({row['scratch']})")
+    if n_maskidx != 1:
+        problems.append(f"gta_maskidx.hip: {n_maskidx} kernel instances found (expected 1)")
     text = _asm("gta_wgrad.hip")
     for name, _, body, vgpr in _kernels(text, r"wgrad_kernelILb(\d)E"):
         lines = body.split("\n")

@@ -16,7 +16,7 @@ import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SOURCES = ["gta_reps", "gta_fwd", "gta_prep", "gta_fwd2", "gta_fwd_gen", "gta_fwd_cl", "gta_fwd64", "gta_bwd", "gta_apply", "gta_plain32", "gta_repgrad", "gta_merge",
+SOURCES = ["gta_reps", "gta_fwd", "gta_prep", "gta_fwd2", "gta_fwd_gen", "gta_fwd_cl", "gta_fwd64", "gta_bwd", "gta_apply", "gta_plain32", "gta_repgrad", "gta_merge", "gta_maskidx",
            "gta_block", "gta_wgrad"]                                                             # (the block library's kernels)
 NO_SLP = {"gta_fwd2", "gta_fwd64", "gta_fwd_gen", "gta_fwd_cl", "gta_bwd", "gta_prep"}          # (FLAGS_* of the Makefile)
 VARLEN = ("gta_fwd2_kernel", "gta_kv_prep_kernel", "gta_gen_prep_kernel", "gta_gen_attn_kernel", "gta_bwd_prep_kernel")
