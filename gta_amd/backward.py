@@ -45,7 +45,8 @@ def attn_bwd(cfg, q, k, v, out, dout, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k, k
     key_idx / key_lens; dk / dv rows of masked tokens are zeros.
     q_live (with key_idx and key_lens; q_lens allowed): ``gta_attn_bwd_qmask`` -- the query-side mask of ``attn_fwd_qmask``; dq rows of dead rows
     are zeros and nothing of them (q, out, dout, lse) is used.
-    dlse ([B,H,Tq], the gradient of the forward's lse; not with key_lens): ``gta_attn_bwd_dlse`` -- the backward of the pair (out, lse)."""
+    dlse ([B,H,Tq], the gradient of the forward's lse): ``gta_attn_bwd_dlse`` -- the backward of the pair (out, lse); with key_lens, key_idx or
+    q_live the ``_dlse`` twin of that entry (``gta_attn_bwd_varlen_dlse`` / ``_gather_dlse`` / ``_qmask_dlse``), where a dead row's dlse is never read."""
     if q_live is not None and (key_idx is None or key_lens is None):
         raise native.GtaError("q_live comes with key_idx and key_lens (gta_attn_bwd_qmask runs on the key_mask route)")
     if key_idx is not None and (key_lens is None or (q_lens is not None and q_live is None)):
@@ -66,10 +67,18 @@ def attn_bwd(cfg, q, k, v, out, dout, lse, tc, ta, vrep_q, vrep_k, cs_q, cs_k, k
     ws = torch.empty(native.attn_bwd_workspace_bytes(desc), device=q.device, dtype=torch.uint8)
     dta = torch.empty(1, device=q.device, dtype=torch.float32) if (want_dtau and ta is not None) else None
     if dlse is not None:
-        if key_lens is not None:
-            raise native.GtaError("return_lse: gta_attn_bwd_varlen takes no gradient of the log-sum-exp")
-        native.attn_bwd_dlse(desc, q, k, v, out, dout, lse, dlse.to(torch.float32).contiguous(), vrep_q, vrep_k, cs_q, cs_k, tc, ta, kv_images,
-                             dq, dk, dv, dtc, ws, dta)
+        dlse = dlse.to(torch.float32).contiguous()
+        if q_live is not None:
+            native.attn_bwd_qmask_dlse(desc, q, k, v, out, dout, lse, dlse, vrep_q, vrep_k, cs_q, cs_k, tc, ta, key_idx, key_lens, q_live, q_lens,
+                                       kv_images, dq, dk, dv, dtc, ws, dta)
+        elif key_idx is not None:
+            native.attn_bwd_gather_dlse(desc, q, k, v, out, dout, lse, dlse, vrep_q, vrep_k, cs_q, cs_k, tc, ta, key_idx, key_lens, kv_images,
+                                        dq, dk, dv, dtc, ws, dta)
+        elif key_lens is not None:
+            native.attn_bwd_varlen_dlse(desc, q, k, v, out, dout, lse, dlse, vrep_q, vrep_k, cs_q, cs_k, tc, ta, key_lens, q_lens, kv_images,
+                                        dq, dk, dv, dtc, ws, dta)
+        else:
+            native.attn_bwd_dlse(desc, q, k, v, out, dout, lse, dlse, vrep_q, vrep_k, cs_q, cs_k, tc, ta, kv_images, dq, dk, dv, dtc, ws, dta)
     elif q_live is not None:
         native.attn_bwd_qmask(desc, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, tc, ta, key_idx, key_lens, q_live, q_lens, kv_images,
                               dq, dk, dv, dtc, ws, dta)

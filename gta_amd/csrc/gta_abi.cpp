@@ -29,10 +29,10 @@ int gta_merge_dispatch(const GtaMergeParams& p, int esz, hipStream_t stream);
 int gta_merge_bwd_dispatch(const GtaMergeBwdParams& p, int esz, hipStream_t stream);
 int gta_maskidx_dispatch(const uint8_t* key_mask, int B, int Tk, int32_t* key_idx, int32_t* key_lens, uint8_t* k_live,
                          const uint8_t* query_mask, int Tq, int32_t* q_lens, hipStream_t stream);
-int gta_bwd_varlen_dispatch(const GtaBwdParams& p, const int32_t* key_lens, const int32_t* q_lens, int dhp, int esz, hipStream_t stream);
-int gta_bwd_gather_dispatch(const GtaBwdParams& p, const int32_t* key_idx, const int32_t* key_lens, int dhp, int esz, hipStream_t stream);
+int gta_bwd_varlen_dispatch(const GtaBwdParams& p, const int32_t* key_lens, const int32_t* q_lens, const float* dlse, int dhp, int esz, hipStream_t stream);
+int gta_bwd_gather_dispatch(const GtaBwdParams& p, const int32_t* key_idx, const int32_t* key_lens, const float* dlse, int dhp, int esz, hipStream_t stream);
 int gta_bwd_qmask_dispatch(const GtaBwdParams& p, const int32_t* key_idx, const int32_t* key_lens, const int32_t* q_lens, const uint8_t* q_live,
-                           int dhp, int esz, hipStream_t stream);
+                           const float* dlse, int dhp, int esz, hipStream_t stream);
 
 namespace {
 
@@ -534,10 +534,11 @@ int bwd_call(const GtaAttnDesc* d, const void* q, const void* k, const void* v, 
     p.Pq = d->Tq / d->Nq; p.Pk = d->Tk / d->Nk; p.invPq = 1.0f / (float)p.Pq; p.invPk = 1.0f / (float)p.Pk;
     p.dh = d->dh; p.nso2 = d->d_so2 / 2; p.flags = d->flags; p.scale = d->scale;
     if (d->H > 65535 || d->B > 65535) return fail(GTA_E_UNSUPPORTED, "B or H above 65535");
-    return launch_status(qmask ? gta_bwd_qmask_dispatch(p, key_idx, key_lens, q_lens, q_live, dhp, esz, (hipStream_t)stream)
-                         : gather ? gta_bwd_gather_dispatch(p, key_idx, key_lens, dhp, esz, (hipStream_t)stream)
-                         : varlen ? gta_bwd_varlen_dispatch(p, key_lens, q_lens, dhp, esz, (hipStream_t)stream)
-                                : gta_bwd_dispatch(p, with_dlse ? dlse : nullptr, dhp, esz, (hipStream_t)stream), "no kernel instance");
+    if (!with_dlse) dlse = nullptr;
+    return launch_status(qmask ? gta_bwd_qmask_dispatch(p, key_idx, key_lens, q_lens, q_live, dlse, dhp, esz, (hipStream_t)stream)
+                         : gather ? gta_bwd_gather_dispatch(p, key_idx, key_lens, dlse, dhp, esz, (hipStream_t)stream)
+                         : varlen ? gta_bwd_varlen_dispatch(p, key_lens, q_lens, dlse, dhp, esz, (hipStream_t)stream)
+                                : gta_bwd_dispatch(p, dlse, dhp, esz, (hipStream_t)stream), "no kernel instance");
 }
 }  // namespace
 
@@ -609,6 +610,47 @@ extern "C" int gta_attn_bwd_qmask(const GtaAttnDesc* d, const void* q, const voi
                                   const int64_t* dout_stride, float* dtrans_coeff, float* dtau, void* workspace,
                                   int64_t workspace_bytes, void* stream) {
     return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, true, key_lens, q_lens, true, key_idx, true, q_live, false, nullptr,
+                    kv_images, dq, dk, dv, dqkv_stride, dout_stride, dtrans_coeff, dtau, workspace, workspace_bytes, stream);
+}
+
+// The masked backwards of the pair (out, lse): each base entry with dlse behind lse, as gta_attn_bwd_dlse relates to gta_attn_bwd -- the DLSE
+// twin of the entry's q-side pre-pass, every walk as in the base entry.  A dead row's dlse is never read
+extern "C" int gta_attn_bwd_varlen_dlse_supported(const GtaAttnDesc* desc) { return gta_attn_bwd_varlen_supported(desc); }
+
+extern "C" int gta_attn_bwd_varlen_dlse(const GtaAttnDesc* d, const void* q, const void* k, const void* v, const void* out,
+                                        const void* dout, const float* lse, const float* dlse, const float* vrep_q, const float* vrep_k,
+                                        const float* cs_q, const float* cs_k, const float* trans_coeff, const float* tau,
+                                        const int32_t* key_lens, const int32_t* q_lens,
+                                        const void* kv_images, void* dq, void* dk, void* dv, const int64_t* dqkv_stride,
+                                        const int64_t* dout_stride, float* dtrans_coeff, float* dtau, void* workspace,
+                                        int64_t workspace_bytes, void* stream) {
+    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, true, key_lens, q_lens, false, nullptr, false, nullptr, true, dlse, kv_images, dq, dk, dv,
+                    dqkv_stride, dout_stride, dtrans_coeff, dtau, workspace, workspace_bytes, stream);
+}
+
+extern "C" int gta_attn_bwd_gather_dlse_supported(const GtaAttnDesc* desc) { return gta_attn_bwd_gather_supported(desc); }
+
+extern "C" int gta_attn_bwd_gather_dlse(const GtaAttnDesc* d, const void* q, const void* k, const void* v, const void* out,
+                                        const void* dout, const float* lse, const float* dlse, const float* vrep_q, const float* vrep_k,
+                                        const float* cs_q, const float* cs_k, const float* trans_coeff, const float* tau,
+                                        const int32_t* key_idx, const int32_t* key_lens,
+                                        const void* kv_images, void* dq, void* dk, void* dv, const int64_t* dqkv_stride,
+                                        const int64_t* dout_stride, float* dtrans_coeff, float* dtau, void* workspace,
+                                        int64_t workspace_bytes, void* stream) {
+    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, true, key_lens, nullptr, true, key_idx, false, nullptr, true, dlse,
+                    kv_images, dq, dk, dv, dqkv_stride, dout_stride, dtrans_coeff, dtau, workspace, workspace_bytes, stream);
+}
+
+extern "C" int gta_attn_bwd_qmask_dlse_supported(const GtaAttnDesc* desc) { return gta_attn_bwd_qmask_supported(desc); }
+
+extern "C" int gta_attn_bwd_qmask_dlse(const GtaAttnDesc* d, const void* q, const void* k, const void* v, const void* out,
+                                       const void* dout, const float* lse, const float* dlse, const float* vrep_q, const float* vrep_k,
+                                       const float* cs_q, const float* cs_k, const float* trans_coeff, const float* tau,
+                                       const int32_t* key_idx, const int32_t* key_lens, const uint8_t* q_live, const int32_t* q_lens,
+                                       const void* kv_images, void* dq, void* dk, void* dv, const int64_t* dqkv_stride,
+                                       const int64_t* dout_stride, float* dtrans_coeff, float* dtau, void* workspace,
+                                       int64_t workspace_bytes, void* stream) {
+    return bwd_call(d, q, k, v, out, dout, lse, vrep_q, vrep_k, cs_q, cs_k, trans_coeff, tau, true, key_lens, q_lens, true, key_idx, true, q_live, true, dlse,
                     kv_images, dq, dk, dv, dqkv_stride, dout_stride, dtrans_coeff, dtau, workspace, workspace_bytes, stream);
 }
 

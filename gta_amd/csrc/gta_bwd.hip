@@ -240,27 +240,42 @@ struct BPrepSmem {
 // and argument block are what they were.
 // DLSE instances (gta_attn_bwd_dlse: the gradient of the pair (out, lse)): LENS = const float*, the row gradients dlse [B,H,Tq] of the
 // log-sum-exp.  dS_ij = P_ij (dP_ij - D_i + dlse_i), so these instances store -(D - dlse) where the others store -D and every walk stays as it
-// is; never combined with VARLEN.
+// is (with VARLEN or QMASK: the twins below).
 // QMASK instance (gta_attn_bwd_qmask): LENS = (const int32_t*, const uint8_t*), q_lens and q_live [B, Tq] (non-zero = a live row).  A row is
 // live iff t < q_lens[b] and q_live[b, t] is set; a dead row takes the path of the rows past the prefix -- zero image rows, statistics
 // (-1e30, 0), no term in the partials, and nothing of the row (q, dout, out, lse, cs_q, its view's record) enters arithmetic.
 GTA_DEV const int32_t* first_len() { return nullptr; }
 GTA_DEV const int32_t* first_len(const int32_t* a) { return a; }
 GTA_DEV const int32_t* first_len(const float*) { return nullptr; }
+// DLSE twins of the masked instances (gta_attn_bwd_varlen_dlse / _gather_dlse / _qmask_dlse): dlse trails the pack -- LENS = (const int32_t*,
+// const float*) or (const int32_t*, const uint8_t*, const float*).  A live row stores -(D - dlse); a dead row (past the prefix, or its byte of
+// q_live clear) stores (-1e30, 0) as in the twin without dlse and its dlse is never loaded -- it may hold NaN, as its dout may (the merge's
+// backward writes dlse_i = a_i (dlse + <dout, out_i - out>) on exactly those rows).  The images and the lse half are those of the twin.
 GTA_DEV const int32_t* first_len(const int32_t* a, const uint8_t*) { return a; }
+GTA_DEV const int32_t* first_len(const int32_t* a, const float*) { return a; }
+GTA_DEV const int32_t* first_len(const int32_t* a, const uint8_t*, const float*) { return a; }
 GTA_DEV const uint8_t* second_live(const int32_t*, const uint8_t* m) { return m; }
+GTA_DEV const uint8_t* second_live(const int32_t*, const uint8_t* m, const float*) { return m; }
 GTA_DEV const float* first_dlse() { return nullptr; }
 GTA_DEV const float* first_dlse(const int32_t*) { return nullptr; }
 GTA_DEV const float* first_dlse(const float* a) { return a; }
+GTA_DEV const float* first_dlse(const int32_t*, const uint8_t*) { return nullptr; }
+GTA_DEV const float* first_dlse(const int32_t*, const float* a) { return a; }
+GTA_DEV const float* first_dlse(const int32_t*, const uint8_t*, const float* a) { return a; }
 template <class... LENS> struct LensIsDlse : std::false_type {};
 template <> struct LensIsDlse<const float*> : std::true_type {};
+template <> struct LensIsDlse<const int32_t*, const float*> : std::true_type {};
+template <> struct LensIsDlse<const int32_t*, const uint8_t*, const float*> : std::true_type {};
+template <class... LENS> struct LensIsQmask : std::false_type {};
+template <> struct LensIsQmask<const int32_t*, const uint8_t*> : std::true_type {};
+template <> struct LensIsQmask<const int32_t*, const uint8_t*, const float*> : std::true_type {};
 template <int DHP, int ESZ, bool X3 = false, bool VARLEN = false, class... LENS>
 __global__ __launch_bounds__(256) void gta_bwd_prep_kernel(const GtaBwdParams p, LENS... lens) {
     static_assert(!(X3 && VARLEN), "no fp32-faithful VARLEN instances");
     constexpr bool DLSE = LensIsDlse<LENS...>::value;
-    constexpr bool QMASK = sizeof...(LENS) == 2;         // (q_lens, q_live)
-    static_assert(sizeof...(LENS) == (QMASK ? 2 : (VARLEN || DLSE) ? 1 : 0) && !(VARLEN && DLSE) && (!QMASK || VARLEN),
-                  "q_lens comes with VARLEN, dlse without it, q_live behind q_lens");
+    constexpr bool QMASK = LensIsQmask<LENS...>::value;  // (q_lens, q_live[, dlse])
+    static_assert(sizeof...(LENS) == (VARLEN ? 1 : 0) + (QMASK ? 1 : 0) + (DLSE ? 1 : 0) && (!QMASK || VARLEN),
+                  "q_lens comes with VARLEN, q_live behind q_lens, dlse last");
     using S = BPrepSmem<DHP, ESZ, X3>;
     constexpr int CHP = DHP / 8, U = S::U, IMG = S::IMG;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -422,12 +437,17 @@ __global__ __launch_bounds__(256) void gta_bwd_prep_kernel(const GtaBwdParams p,
         const int tt = j * BN + tid;
         if constexpr (QMASK) {                // (tid < 64: tid is the row `valid` was worked out for -- a dead row's lse and D are not read)
             st[tid] = valid ? -(p.lse[((long)b * p.H + h) * p.Tq + tt] * LOG2E) : -1e30f;
+            if constexpr (DLSE) {             // (a dead row's dlse is not read either: the load sits in the live arm)
+                const float* dlse = first_dlse(lens...);
+                st[64 + tid] = valid ? -(((dsum[tid] + dsum[64 + tid]) + (dsum[128 + tid] + dsum[192 + tid])) - dlse[((long)b * p.H + h) * p.Tq + tt]) : 0.f;
+            } else {
             st[64 + tid] = valid ? -((dsum[tid] + dsum[64 + tid]) + (dsum[128 + tid] + dsum[192 + tid])) : 0.f;
+            }
         } else {
         st[tid] = tt < GTA_TQB ? -(p.lse[((long)b * p.H + h) * p.Tq + tt] * LOG2E) : -1e30f;
-        if constexpr (DLSE) {
+        if constexpr (DLSE) {                 // (VARLEN: GTA_TQB <= Tq -- rows at or past the prefix, the ragged tile's included, never index dlse)
             const float* dlse = first_dlse(lens...);
-            st[64 + tid] = tt < p.Tq ? -(((dsum[tid] + dsum[64 + tid]) + (dsum[128 + tid] + dsum[192 + tid])) - dlse[((long)b * p.H + h) * p.Tq + tt]) : 0.f;
+            st[64 + tid] = tt < GTA_TQB ? -(((dsum[tid] + dsum[64 + tid]) + (dsum[128 + tid] + dsum[192 + tid])) - dlse[((long)b * p.H + h) * p.Tq + tt]) : 0.f;
         } else {
             st[64 + tid] = tt < GTA_TQB ? -((dsum[tid] + dsum[64 + tid]) + (dsum[128 + tid] + dsum[192 + tid])) : 0.f;
         }
@@ -2138,9 +2158,10 @@ int run_bwd(const GtaBwdParams& p, const float* dlse, hipStream_t stream) {
 
 // gta_attn_bwd_varlen: the VARLEN instances of the compiled kernels, whatever run_bwd would select for the shape (never the generated streams)
 template <int DHP, int ESZ>
-int run_bwd_varlen(const GtaBwdParams& p, const int32_t* key_lens, const int32_t* q_lens, hipStream_t stream) {
+int run_bwd_varlen(const GtaBwdParams& p, const int32_t* key_lens, const int32_t* q_lens, const float* dlse, hipStream_t stream) {
     const int n_qt = (p.Tq + BN - 1) / BN;
     if (int rc = gta_lds_optin<&gta_bwd_prep_kernel<DHP, ESZ, false, true, const int32_t*>>(BPrepSmem<DHP, ESZ>::total(GTA_MAX_VIEWS))) return rc;
+    if (int rc = gta_lds_optin<&gta_bwd_prep_kernel<DHP, ESZ, false, true, const int32_t*, const float*>>(BPrepSmem<DHP, ESZ>::total(GTA_MAX_VIEWS))) return rc;
     if (int rc = gta_lds_optin<&gta_bwd_dq_varlen_kernel<DHP, ESZ>>(DqSmem<DHP>::total(GTA_MAX_VIEWS))) return rc;
     if (int rc = gta_lds_optin<&gta_bwd_dkv_varlen_kernel<DHP, ESZ>>(DkvSmem<DHP>::total(GTA_MAX_VIEWS))) return rc;
     const long prep_grid = ((long)p.B * n_qt + 7) / 8 * 8 * p.H;
@@ -2148,7 +2169,9 @@ int run_bwd_varlen(const GtaBwdParams& p, const int32_t* key_lens, const int32_t
     if (prep_grid > 0x7fffffffL || n_dq > 0x7fffffffL || n_dkv > 0x7fffffffL) return GTA_E_UNSUPPORTED;
     const int lds_prep = BPrepSmem<DHP, ESZ>::total(p.vrep_q ? p.Nq : 0);
     const int lds_dq = DqSmem<DHP>::total(p.vrep_q ? p.Nq : 0), lds_dkv = DkvSmem<DHP>::total(p.vrep_k ? p.Nk : 0);
-    hipLaunchKernelGGL((gta_bwd_prep_kernel<DHP, ESZ, false, true, const int32_t*>), dim3((unsigned)prep_grid), dim3(256), lds_prep, stream, p, q_lens);
+    if (dlse) hipLaunchKernelGGL((gta_bwd_prep_kernel<DHP, ESZ, false, true, const int32_t*, const float*>), dim3((unsigned)prep_grid), dim3(256), lds_prep, stream,
+                                 p, q_lens, dlse);
+    else hipLaunchKernelGGL((gta_bwd_prep_kernel<DHP, ESZ, false, true, const int32_t*>), dim3((unsigned)prep_grid), dim3(256), lds_prep, stream, p, q_lens);
     hipLaunchKernelGGL((gta_bwd_dq_varlen_kernel<DHP, ESZ>), dim3((unsigned)n_dq), dim3(256), lds_dq, stream, p, key_lens, q_lens);
     hipLaunchKernelGGL((gta_bwd_dkv_varlen_kernel<DHP, ESZ>), dim3((unsigned)n_dkv), dim3(256), lds_dkv, stream, p, key_lens, q_lens);
     if (p.dtrans_coeff)
@@ -2161,10 +2184,11 @@ int run_bwd_varlen(const GtaBwdParams& p, const int32_t* key_lens, const int32_t
 // gta_attn_bwd_gather: run_bwd_varlen with the GATHER instance of the dK/dV walk -- three launches, never the generated streams.  The query side
 // has no lengths of its own here (q_lens = NULL: every query row is live)
 template <int DHP, int ESZ>
-int run_bwd_gather(const GtaBwdParams& p, const int32_t* key_idx, const int32_t* key_lens, hipStream_t stream) {
+int run_bwd_gather(const GtaBwdParams& p, const int32_t* key_idx, const int32_t* key_lens, const float* dlse, hipStream_t stream) {
     const int n_qt = (p.Tq + BN - 1) / BN;
     const int32_t* q_lens = nullptr;
     if (int rc = gta_lds_optin<&gta_bwd_prep_kernel<DHP, ESZ, false, true, const int32_t*>>(BPrepSmem<DHP, ESZ>::total(GTA_MAX_VIEWS))) return rc;
+    if (int rc = gta_lds_optin<&gta_bwd_prep_kernel<DHP, ESZ, false, true, const int32_t*, const float*>>(BPrepSmem<DHP, ESZ>::total(GTA_MAX_VIEWS))) return rc;
     if (int rc = gta_lds_optin<&gta_bwd_dq_varlen_kernel<DHP, ESZ>>(DqSmem<DHP>::total(GTA_MAX_VIEWS))) return rc;
     if (int rc = gta_lds_optin<&gta_bwd_dkv_gather_kernel<DHP, ESZ>>(DkvSmem<DHP>::total(GTA_MAX_VIEWS))) return rc;
     const long prep_grid = ((long)p.B * n_qt + 7) / 8 * 8 * p.H;
@@ -2172,7 +2196,9 @@ int run_bwd_gather(const GtaBwdParams& p, const int32_t* key_idx, const int32_t*
     if (prep_grid > 0x7fffffffL || n_dq > 0x7fffffffL || n_dkv > 0x7fffffffL) return GTA_E_UNSUPPORTED;
     const int lds_prep = BPrepSmem<DHP, ESZ>::total(p.vrep_q ? p.Nq : 0);
     const int lds_dq = DqSmem<DHP>::total(p.vrep_q ? p.Nq : 0), lds_dkv = DkvSmem<DHP>::total(p.vrep_k ? p.Nk : 0);
-    hipLaunchKernelGGL((gta_bwd_prep_kernel<DHP, ESZ, false, true, const int32_t*>), dim3((unsigned)prep_grid), dim3(256), lds_prep, stream, p, q_lens);
+    if (dlse) hipLaunchKernelGGL((gta_bwd_prep_kernel<DHP, ESZ, false, true, const int32_t*, const float*>), dim3((unsigned)prep_grid), dim3(256), lds_prep, stream,
+                                 p, q_lens, dlse);
+    else hipLaunchKernelGGL((gta_bwd_prep_kernel<DHP, ESZ, false, true, const int32_t*>), dim3((unsigned)prep_grid), dim3(256), lds_prep, stream, p, q_lens);
     hipLaunchKernelGGL((gta_bwd_dq_varlen_kernel<DHP, ESZ>), dim3((unsigned)n_dq), dim3(256), lds_dq, stream, p, key_lens, q_lens);
     hipLaunchKernelGGL((gta_bwd_dkv_gather_kernel<DHP, ESZ>), dim3((unsigned)n_dkv), dim3(256), lds_dkv, stream, p, key_lens, q_lens, key_idx);
     if (p.dtrans_coeff)
@@ -2185,9 +2211,12 @@ int run_bwd_gather(const GtaBwdParams& p, const int32_t* key_idx, const int32_t*
 // gta_attn_bwd_qmask: run_bwd_gather with the QMASK instances of the q-side pre-pass and of the dQ walk.  q_lens may be null (Tq: the dK/dV walk
 // then runs over every query tile, the dead ones adding exact zeros)
 template <int DHP, int ESZ>
-int run_bwd_qmask(const GtaBwdParams& p, const int32_t* key_idx, const int32_t* key_lens, const int32_t* q_lens, const uint8_t* q_live, hipStream_t stream) {
+int run_bwd_qmask(const GtaBwdParams& p, const int32_t* key_idx, const int32_t* key_lens, const int32_t* q_lens, const uint8_t* q_live, const float* dlse,
+                  hipStream_t stream) {
     const int n_qt = (p.Tq + BN - 1) / BN;
     if (int rc = gta_lds_optin<&gta_bwd_prep_kernel<DHP, ESZ, false, true, const int32_t*, const uint8_t*>>(BPrepSmem<DHP, ESZ>::total(GTA_MAX_VIEWS))) return rc;
+    if (int rc = gta_lds_optin<&gta_bwd_prep_kernel<DHP, ESZ, false, true, const int32_t*, const uint8_t*, const float*>>(BPrepSmem<DHP, ESZ>::total(GTA_MAX_VIEWS)))
+        return rc;
     if (int rc = gta_lds_optin<&gta_bwd_dq_qmask_kernel<DHP, ESZ>>(DqSmem<DHP>::total(GTA_MAX_VIEWS))) return rc;
     if (int rc = gta_lds_optin<&gta_bwd_dkv_gather_kernel<DHP, ESZ>>(DkvSmem<DHP>::total(GTA_MAX_VIEWS))) return rc;
     const long prep_grid = ((long)p.B * n_qt + 7) / 8 * 8 * p.H;
@@ -2195,8 +2224,10 @@ int run_bwd_qmask(const GtaBwdParams& p, const int32_t* key_idx, const int32_t* 
     if (prep_grid > 0x7fffffffL || n_dq > 0x7fffffffL || n_dkv > 0x7fffffffL) return GTA_E_UNSUPPORTED;
     const int lds_prep = BPrepSmem<DHP, ESZ>::total(p.vrep_q ? p.Nq : 0);
     const int lds_dq = DqSmem<DHP>::total(p.vrep_q ? p.Nq : 0), lds_dkv = DkvSmem<DHP>::total(p.vrep_k ? p.Nk : 0);
-    hipLaunchKernelGGL((gta_bwd_prep_kernel<DHP, ESZ, false, true, const int32_t*, const uint8_t*>), dim3((unsigned)prep_grid), dim3(256), lds_prep, stream,
-                       p, q_lens, q_live);
+    if (dlse) hipLaunchKernelGGL((gta_bwd_prep_kernel<DHP, ESZ, false, true, const int32_t*, const uint8_t*, const float*>), dim3((unsigned)prep_grid), dim3(256),
+                                 lds_prep, stream, p, q_lens, q_live, dlse);
+    else hipLaunchKernelGGL((gta_bwd_prep_kernel<DHP, ESZ, false, true, const int32_t*, const uint8_t*>), dim3((unsigned)prep_grid), dim3(256), lds_prep, stream,
+                            p, q_lens, q_live);
     hipLaunchKernelGGL((gta_bwd_dq_qmask_kernel<DHP, ESZ>), dim3((unsigned)n_dq), dim3(256), lds_dq, stream, p, key_lens, q_lens, q_live);
     hipLaunchKernelGGL((gta_bwd_dkv_gather_kernel<DHP, ESZ>), dim3((unsigned)n_dkv), dim3(256), lds_dkv, stream, p, key_lens, q_lens, key_idx);
     if (p.dtrans_coeff)
@@ -2208,12 +2239,13 @@ int run_bwd_qmask(const GtaBwdParams& p, const int32_t* key_idx, const int32_t* 
 
 }  // namespace
 
+// dlse (the three masked dispatchers): null = the entry without it, launched as it was; else the DLSE twin of the q-side pre-pass
 int gta_bwd_qmask_dispatch(const GtaBwdParams& p, const int32_t* key_idx, const int32_t* key_lens, const int32_t* q_lens, const uint8_t* q_live,
-                           int dhp, int esz, hipStream_t stream) {
+                           const float* dlse, int dhp, int esz, hipStream_t stream) {
     if (!key_idx || !key_lens || !q_live) return GTA_E_BADARG;
     if (p.flags & GTA_FLAG_FP32_PRODUCTS) return GTA_E_UNSUPPORTED;
-#define GTA_CASEB(D) case D: return esz == 2 ? run_bwd_qmask<D, 2>(p, key_idx, key_lens, q_lens, q_live, stream) \
-                                              : run_bwd_qmask<D, 4>(p, key_idx, key_lens, q_lens, q_live, stream);
+#define GTA_CASEB(D) case D: return esz == 2 ? run_bwd_qmask<D, 2>(p, key_idx, key_lens, q_lens, q_live, dlse, stream) \
+                                              : run_bwd_qmask<D, 4>(p, key_idx, key_lens, q_lens, q_live, dlse, stream);
     switch (dhp) {
         GTA_CASEB(32)
         GTA_CASEB(64)
@@ -2224,10 +2256,11 @@ int gta_bwd_qmask_dispatch(const GtaBwdParams& p, const int32_t* key_idx, const 
     return GTA_E_UNSUPPORTED;
 }
 
-int gta_bwd_gather_dispatch(const GtaBwdParams& p, const int32_t* key_idx, const int32_t* key_lens, int dhp, int esz, hipStream_t stream) {
+int gta_bwd_gather_dispatch(const GtaBwdParams& p, const int32_t* key_idx, const int32_t* key_lens, const float* dlse, int dhp, int esz, hipStream_t stream) {
     if (!key_idx || !key_lens) return GTA_E_BADARG;
     if (p.flags & GTA_FLAG_FP32_PRODUCTS) return GTA_E_UNSUPPORTED;
-#define GTA_CASEB(D) case D: return esz == 2 ? run_bwd_gather<D, 2>(p, key_idx, key_lens, stream) : run_bwd_gather<D, 4>(p, key_idx, key_lens, stream);
+#define GTA_CASEB(D) case D: return esz == 2 ? run_bwd_gather<D, 2>(p, key_idx, key_lens, dlse, stream) \
+                                              : run_bwd_gather<D, 4>(p, key_idx, key_lens, dlse, stream);
     switch (dhp) {
         GTA_CASEB(32)
         GTA_CASEB(64)
@@ -2238,9 +2271,10 @@ int gta_bwd_gather_dispatch(const GtaBwdParams& p, const int32_t* key_idx, const
     return GTA_E_UNSUPPORTED;
 }
 
-int gta_bwd_varlen_dispatch(const GtaBwdParams& p, const int32_t* key_lens, const int32_t* q_lens, int dhp, int esz, hipStream_t stream) {
+int gta_bwd_varlen_dispatch(const GtaBwdParams& p, const int32_t* key_lens, const int32_t* q_lens, const float* dlse, int dhp, int esz, hipStream_t stream) {
     if (!key_lens || (p.flags & GTA_FLAG_FP32_PRODUCTS)) return GTA_E_UNSUPPORTED;
-#define GTA_CASEB(D) case D: return esz == 2 ? run_bwd_varlen<D, 2>(p, key_lens, q_lens, stream) : run_bwd_varlen<D, 4>(p, key_lens, q_lens, stream);
+#define GTA_CASEB(D) case D: return esz == 2 ? run_bwd_varlen<D, 2>(p, key_lens, q_lens, dlse, stream) \
+                                              : run_bwd_varlen<D, 4>(p, key_lens, q_lens, dlse, stream);
     switch (dhp) {
         GTA_CASEB(32)
         GTA_CASEB(64)

@@ -907,7 +907,8 @@ class _FusedAttn(torch.autograd.Function):
 
 class _FusedAttnLse(torch.autograd.Function):
     """``_FusedAttn`` -> (out, lse), both differentiable: the backward takes (dout, dlse), either of which may be None, through
-    ``gta_attn_bwd_dlse`` (dS = P (dP - D + dlse): the q-side pre-pass stores -(D - dlse), every walk is the one of ``gta_attn_bwd``)."""
+    ``gta_attn_bwd_dlse`` (dS = P (dP - D + dlse): the q-side pre-pass stores -(D - dlse), every walk is the one of ``gta_attn_bwd``); under a
+    mask (``masked_lse_backward=True``) through the ``_dlse`` twin of the mask's backward entry."""
 
     @staticmethod
     def forward(ctx, *args):
@@ -948,7 +949,7 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
                   key_views=None, key_lens: Optional[torch.Tensor] = None, key_views_backward: bool = False,
                   query_views=None, return_lse: bool = False, key_mask: Optional[torch.Tensor] = None, key_mask_backward: bool = False,
                   query_mask: Optional[torch.Tensor] = None, key_mask_rep_grad: bool = False,
-                  mask_index: Optional[MaskIndex] = None):
+                  mask_index: Optional[MaskIndex] = None, masked_lse_backward: bool = False):
     """Fused GTA attention on packed reps.  q [B,H,Tq,dh], k/v [B,H,Tk,dh] -> out [B,H,Tq,dh].
 
     kv_mode: 'prepass' = K/V rep pre-pass + lean attention kernel (two launches; at dh = 96 in the MSN layout the attention kernel is
@@ -979,7 +980,7 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
              and the padded tokens' entries -- with ``query_views`` on the query side as well --, whatever those hold (such tables must be
              CUDA tensors: the pass has no CPU path, and a CPU one is refused by name before anything is launched).  Still refused, by
              name: the staged generic layouts under grad, precise=True, pretransformed, kv_mode='fused', return_attmap, and return_lse
-             under grad.
+             under grad without ``masked_lse_backward=True`` (below).
     query_views: only with ``key_views_backward=True``; validated like ``key_views``, against Nq.  Backward only: the query rows of scene b's
              views past ``query_views[b]`` (self-attention over padded views, where they hold anything) send no gradient -- their ``dout`` is
              never read, their dq rows are zero.  The forward still computes (unspecified) output rows for them.
@@ -988,7 +989,8 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
              beside out and ``gta_attention_merge`` combines partial attentions with.  Without grad on every route (fused, key_views, staged,
              rho-apply).  Under grad lse is a differentiable output like out -- the backward takes (dout, dlse), either may be missing -- in
              the default arithmetic (fused layouts and the rho-apply route) and with precise=True where the fused fp32-faithful backward runs
-             (float32, dh <= 64); ``key_views_backward`` and the exact-fp32 route of precise=True (gta_plain32) raise ``GtaError``.
+             (float32, dh <= 64); ``key_views_backward`` / ``key_mask_backward`` without ``masked_lse_backward=True`` and the exact-fp32
+             route of precise=True (gta_plain32) raise ``GtaError``.
     key_mask: a bool [B, Tk] tensor (True: the key is attended; None: every key is) -- ANY per-scene subset of the key tokens: views of
              different size padded inside their slots, a missing view that is not the last, patches to ignore.  out (and lse, with
              ``return_lse``) are those of the attention over the valid keys alone; whatever k, v and cs_k hold at masked tokens is never
@@ -1007,7 +1009,8 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
              self-attention the masked tokens are query rows too, computed as in the forward, and they take part in the backward with whatever
              ``dout`` they get -- so masked QUERY rows (q, cs_q, and the dout that reaches them) must hold finite values; a zero ``dout`` row then
              adds exact zeros to dk / dv.  Still refused, by name: rep tables or poses that require grad without ``key_mask_rep_grad`` (below),
-             return_lse under grad, kv_cache under grad, precise=True, pretransformed, kv_mode='fused', and the staged and rho-apply layouts.
+             return_lse under grad without ``masked_lse_backward=True`` (below), kv_cache under grad, precise=True, pretransformed,
+             kv_mode='fused', and the staged and rho-apply layouts.
     key_mask_rep_grad: only with ``key_mask_backward=True``.  False (default): rep tables or poses that require grad are refused under a mask,
              as they always were.  True: they get their gradients (gta_amd/repgrad.py over the live tokens, ``gta_rep_grad_sums_masked``): the
              key side under the key mask, the query side under ``query_mask`` (without one every query row is live, in self-attention too).
@@ -1015,6 +1018,15 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
              its so2 / coordinate entries, whatever those hold.  Under a CUDA key mask a scene without a valid key attends its token 0, and
              that token counts as live here too.  Such tables must be CUDA tensors (the pass has no CPU path; a CPU one is refused by name
              before anything is launched), and the masked sides' tokens must split evenly into views.
+    masked_lse_backward: only with ``key_views_backward=True`` or ``key_mask_backward=True``.  False (default): ``return_lse`` under grad is
+             refused under those, as it always was.  True: (out, lse) of the masked call is differentiable -- the backward takes (dout, dlse),
+             either may be missing, through ``gta_attn_bwd_varlen_dlse`` (``key_views``, with or without ``query_views``),
+             ``gta_attn_bwd_gather_dlse`` (``key_mask``) or ``gta_attn_bwd_qmask_dlse`` (with ``query_mask``); ``mask_index`` and
+             ``key_mask_rep_grad`` go with it as with the backward without lse.  This is what lets masked partial attentions be merged
+             (``gta_attention_merge``) and trained through.  ``dlse`` of dead rows (``query_mask``) and of rows at or past ``query_views``
+             may hold anything, NaN and Inf included, as their ``dout`` may: it is never read.  Without ``return_lse`` or without grad the
+             flag changes nothing.  Everything else the masked routes refuse stays refused (precise=True, pretransformed, kv_mode='fused',
+             kv_cache under grad, the staged and rho-apply layouts).
     query_mask: a bool [B, Tq] tensor (True: the query row is live; None: every row is) -- the query side of ``key_mask``: padded tokens of
              a self-attention layer, scenes with different numbers of target rays.  A masked (dead) row is never used: its q row, its cs_q
              row and the vrep_q record of a view without a live row may hold anything, NaN and Inf included, and so may its ``dout`` row in
@@ -1036,7 +1048,8 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
         q, k, v, f_dims, packed, so3_degree=so3_degree, trans_coeff=trans_coeff, tau=tau, scale=scale, v_transform=v_transform, euclid=euclid,
         pretransformed=pretransformed, use_dma=use_dma, kv_mode=kv_mode, kv_cache=kv_cache, precise=precise, key_views=key_views,
         key_lens=key_lens, key_views_backward=key_views_backward, query_views=query_views, return_lse=return_lse, key_mask=key_mask,
-        key_mask_backward=key_mask_backward, query_mask=query_mask, key_mask_rep_grad=key_mask_rep_grad, mask_index=mask_index)
+        key_mask_backward=key_mask_backward, query_mask=query_mask, key_mask_rep_grad=key_mask_rep_grad, mask_index=mask_index,
+        masked_lse_backward=masked_lse_backward)
     scale = cfg[4]
     if route == "staged":
         return _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, kv_cache,
@@ -1058,7 +1071,7 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
 
 def _resolve(q, k, v, f_dims, packed, *, so3_degree, trans_coeff, tau, scale, v_transform, euclid, pretransformed, use_dma, kv_mode, kv_cache,
              precise, key_views, key_lens, key_views_backward, query_views, return_lse, key_mask, key_mask_backward, query_mask,
-             key_mask_rep_grad, mask_index=None):
+             key_mask_rep_grad, mask_index=None, masked_lse_backward=False):
     """The host-only half of ``gta_attention`` (its arguments, the keyword-only ones by keyword): every refusal, in a fixed order, then how the call runs.
     -> (route, cfg, mask, packed, carriers, trans_coeff, tau): route 'fused' (through ``_FusedAttn``: every unmasked call, a masked one under
     grad), 'forward' (a masked call without grad: ``_fused_forward`` alone), 'staged' or 'apply' (``generic_route``);
@@ -1072,6 +1085,9 @@ def _resolve(q, k, v, f_dims, packed, *, so3_degree, trans_coeff, tau, scale, v_
     if key_mask_rep_grad and not key_mask_backward:
         raise native.GtaError("key_mask_rep_grad=True comes with key_mask_backward=True (the pose / coordinate gradients are a pass after "
                               "the masked backward)")
+    if masked_lse_backward and not (key_views_backward or key_mask_backward):
+        raise native.GtaError("masked_lse_backward=True comes with key_views_backward=True or key_mask_backward=True (it lets the masked "
+                              "backward take the gradient of the log-sum-exp)")
     if query_mask is not None and views_given:
         raise native.GtaError("query_mask with key_views / query_views / key_lens / key_views_backward: a query mask runs on the key_mask "
                               "route -- say the valid views as a key_mask (and the valid query rows as the query_mask)")
@@ -1099,7 +1115,7 @@ def _resolve(q, k, v, f_dims, packed, *, so3_degree, trans_coeff, tau, scale, v_
     if isinstance(tau, (int, float)):
         tau = None if float(tau) == 1.0 else torch.tensor([float(tau)], device=q.device, dtype=torch.float32)
     needs_grad = torch.is_grad_enabled() and (bool(carriers) or any(torch.is_tensor(t) and t.requires_grad for t in (q, k, v, trans_coeff, tau)))
-    if return_lse and needs_grad and key_views_backward:
+    if return_lse and needs_grad and key_views_backward and not masked_lse_backward:
         raise native.GtaError("return_lse under grad with key_views_backward: gta_attn_bwd_varlen takes no gradient of the log-sum-exp "
                               "(drop return_lse, or call under torch.no_grad())")
     Nq, Nk = _views(f_dims, packed, q, k)
@@ -1127,7 +1143,7 @@ def _resolve(q, k, v, f_dims, packed, *, so3_degree, trans_coeff, tau, scale, v_
             elif carriers:
                 raise native.GtaError("key_mask_backward: no pose / coordinate gradients under a key mask yet (gta_rep_grad_sums_varlen knows "
                                       "prefixes only): detach the rep tables and poses")
-            if return_lse:
+            if return_lse and not masked_lse_backward:
                 raise native.GtaError("return_lse under grad with key_mask_backward: gta_attn_bwd_gather takes no gradient of the log-sum-exp "
                                       "(drop return_lse, or call under torch.no_grad())")
     how = dict(v_transform=v_transform, euclid=euclid, precise=bool(precise), needs_grad=needs_grad)
@@ -1218,7 +1234,10 @@ def gta_attention_by_view_groups(q, k, v, f_dims: Dict[str, int], packed: dict, 
     K and V of a group are token slices of k and v (tokens are view-major: no copy where the slice keeps 16-byte rows); the key-side tables'
     rows are copied per group (vrep_k per view, cs_k / coord_k per token).  The number of key views is that of ``packed['vrep_k']``;
     a layout without view tables says it with ``num_key_views``.  Differentiable wherever ``gta_attention(..., return_lse=True)`` is.  Every
-    other keyword goes to ``gta_attention``; ``kv_cache``, ``key_views`` (with its companions), ``key_mask``, ``mask_index`` and ``return_attmap`` are refused."""
+    other keyword goes to ``gta_attention``; ``kv_cache``, ``key_views`` (with its companions), ``key_mask``, ``mask_index`` and ``return_attmap`` are refused.
+    Under a ``query_mask`` (scenes with different numbers of target rays) the call is trainable with ``key_mask_backward=True,
+    masked_lse_backward=True`` -- every group's call is a ``return_lse=True`` call under the query mask --, ``key_mask_rep_grad=True``
+    included; dead rows get out = +0.0, dq = +0.0 and may hold NaN in q and in the ``dout`` that reaches the merged output."""
     for name in _NOT_PER_GROUP:
         if kw.get(name) is not None and kw.get(name) is not False:
             raise native.GtaError(f"gta_attention_by_view_groups takes no {name}: every group is a call of its own")

@@ -253,7 +253,7 @@ int gta_attn_bwd_gather(const GtaAttnDesc* desc,
  *       gta_attn_bwd launches for the same desc.  An all-zero dlse gives dq, dk, dv, dtrans_coeff and dtau bit for bit those of gta_attn_bwd.
  *       Under GTA_FLAG_FP32_PRODUCTS the centred dtau of the X3 dQ walk accounts for sum_j dS_ij = dlse_i.
  *   gta_attn_bwd_dlse_supported: 0 where gta_attn_bwd serves desc, else its error with the reason in gta_strerror() (layouts without a
- *       fused kernel, GTA_FLAG_PRETRANSFORMED, GTA_FLAG_FP32_PRODUCTS outside fp32 inputs at dh <= 64).  No instance with per-scene prefixes.
+ *       fused kernel, GTA_FLAG_PRETRANSFORMED, GTA_FLAG_FP32_PRODUCTS outside fp32 inputs at dh <= 64).  With per-scene prefixes or masks: the gta_attn_bwd_*_dlse entries below.
  *   Every other argument, check, workspace size and error code: as in gta_attn_bwd. */
 int gta_attn_bwd_dlse_supported(const GtaAttnDesc* desc);
 int gta_attn_bwd_dlse(const GtaAttnDesc* desc,
@@ -426,6 +426,49 @@ int gta_attn_bwd_qmask(const GtaAttnDesc* desc,
                        void* dq, void* dk, void* dv, const int64_t* dqkv_stride, const int64_t* dout_stride,
                        float* dtrans_coeff, float* dtau,
                        void* workspace, int64_t workspace_bytes, void* stream);
+
+/* The masked backwards of the PAIR (out, lse) (gta_attention's masked_lse_backward): gta_attn_bwd_varlen, gta_attn_bwd_gather and
+ * gta_attn_bwd_qmask with the gradient of the log-sum-exp, as gta_attn_bwd_dlse relates to gta_attn_bwd.
+ *   dlse: [B,H,Tq] fp32, contiguous, non-NULL (GTA_E_BADARG, "null dlse") -- d loss / d lse per query row.  The q-side pre-pass runs in the
+ *       DLSE twin of the base entry's instance: a live row stores -(D - dlse) where the base stores -D; the Q'' / dO~ images, the lse half of
+ *       the statistics and every walk are the base entry's.  An all-zero dlse gives every output bit for bit that of the base entry.
+ *   A dead row -- at or past q_lens[b], or with its byte of q_live clear -- stores (-1e30, 0) as in the base entry, and its dlse is never
+ *       loaded: like its dout it may hold anything, NaN and Inf included (gta_attn_merge_bwd writes dlse_i = a_i (dlse + <dout, out_i - out>)
+ *       on exactly those rows).
+ *   *_dlse_supported: what the base entry's query answers.  Every other argument, check, workspace size and error code: as in the base entry. */
+int gta_attn_bwd_varlen_dlse_supported(const GtaAttnDesc* desc);
+int gta_attn_bwd_varlen_dlse(const GtaAttnDesc* desc,
+                             const void* q, const void* k, const void* v, const void* out, const void* dout,
+                             const float* lse, const float* dlse,
+                             const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
+                             const float* trans_coeff, const float* tau,
+                             const int32_t* key_lens, const int32_t* q_lens,
+                             const void* kv_images,
+                             void* dq, void* dk, void* dv, const int64_t* dqkv_stride, const int64_t* dout_stride,
+                             float* dtrans_coeff, float* dtau,
+                             void* workspace, int64_t workspace_bytes, void* stream);
+int gta_attn_bwd_gather_dlse_supported(const GtaAttnDesc* desc);
+int gta_attn_bwd_gather_dlse(const GtaAttnDesc* desc,
+                             const void* q, const void* k, const void* v, const void* out, const void* dout,
+                             const float* lse, const float* dlse,
+                             const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
+                             const float* trans_coeff, const float* tau,
+                             const int32_t* key_idx, const int32_t* key_lens,
+                             const void* kv_images,
+                             void* dq, void* dk, void* dv, const int64_t* dqkv_stride, const int64_t* dout_stride,
+                             float* dtrans_coeff, float* dtau,
+                             void* workspace, int64_t workspace_bytes, void* stream);
+int gta_attn_bwd_qmask_dlse_supported(const GtaAttnDesc* desc);
+int gta_attn_bwd_qmask_dlse(const GtaAttnDesc* desc,
+                            const void* q, const void* k, const void* v, const void* out, const void* dout,
+                            const float* lse, const float* dlse,
+                            const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
+                            const float* trans_coeff, const float* tau,
+                            const int32_t* key_idx, const int32_t* key_lens, const uint8_t* q_live, const int32_t* q_lens,
+                            const void* kv_images,
+                            void* dq, void* dk, void* dv, const int64_t* dqkv_stride, const int64_t* dout_stride,
+                            float* dtrans_coeff, float* dtau,
+                            void* workspace, int64_t workspace_bytes, void* stream);
 
 /* What the masked entries above read, built from the masks in one launch (gta_maskidx.hip; gta_amd.mask_index): one 256-thread workgroup
  * per (scene, side), no workspace, no atomics (every output element has one writer), nothing read back by the host.

@@ -132,6 +132,8 @@ def audit_others():
         for name, (dhp, esz), body, vgpr in _kernels(text, kern + pattern):
             if "JPKiPKhEE" in name:                     # the pre-pass's QMASK instances <dhp, esz, false, true, q_lens, q_live>: below
                 continue
+            if "PKfEE" in name:                         # its masked DLSE twins <.., q_lens[, q_live], dlse>: below
+                continue
             row = {"kernel": f"{kern}_varlen_kernel<{dhp},{esz}>", "vgpr": vgpr, "scratch": body.count("scratch_")}
             report.append(row)
             twin = bwd_scratch.get((kern + "_kernel", dhp, esz))
@@ -174,6 +176,20 @@ def audit_others():
         twin = prep.get((dhp, esz, x3, False))
         if twin is None or n > twin[0]:
             problems.append(f"{row['kernel']} has {n} scratch accesses, its twin without dlse {twin and twin[0]}")
+    # the DLSE twins of the masked pre-pass instances (gta_attn_bwd_varlen_dlse / _gather_dlse: <.., q_lens, dlse>; gta_attn_bwd_qmask_dlse:
+    # <.., q_lens, q_live, dlse>) by the same rule against the masked instance without dlse, one per twin
+    for kind, tail in (("varlen", "JPKiPKfEE"), ("qmask", "JPKiPKhPKfEE")):
+        twins = {r["kernel"]: r["scratch"] for r in report if r["kernel"].startswith(f"gta_bwd_prep_{kind}_kernel<")}
+        n_dlse = 0
+        for name, (dhp, esz), body, vgpr in _kernels(text, r"gta_bwd_prep_kernelILi(\d+)ELi(\d+)ELb0ELb1E" + tail):
+            row = {"kernel": f"gta_bwd_prep_{kind}_dlse_kernel<{dhp},{esz}>", "vgpr": vgpr, "scratch": body.count("scratch_")}
+            report.append(row)
+            n_dlse += 1
+            twin = twins.get(f"gta_bwd_prep_{kind}_kernel<{dhp},{esz}>")
+            if twin is None or row["scratch"] > twin:
+                problems.append(f"{row['kernel']} has {row['scratch']} scratch accesses, its twin without dlse {twin}")
+        if n_dlse != len(twins):
+            problems.append(f"{n_dlse} DLSE twins of gta_bwd_prep_{kind}_kernel for {len(twins)} instances without dlse")
     # the merge kernels (gta_merge.hip): the partials' pointers and strides are indexed by unrolled constants -- no scratch at all (hard)
     mtext = _asm("gta_merge.hip")
     n_merge = 0
