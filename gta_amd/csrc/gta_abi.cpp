@@ -365,14 +365,16 @@ extern "C" int64_t gta_attn_fwd_staged_workspace_bytes(const GtaAttnDesc* desc) 
 }
 
 namespace {
-// both staged entries: key_lens == nullptr is gta_attn_fwd_staged
+// the staged entries: key_lens == nullptr is gta_attn_fwd_staged.  gather (gta_attn_fwd_staged_gather; with key_lens) is the explicit selector of
+// the GATHER instances of the pre-pass -- never "key_idx is non-null"; with GTA_FLAG_KV_READY the indices are not read.
 int staged_call(const GtaAttnDesc* d, const void* q, const void* k, const void* v,
                 const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
                 const float* coord_q, const float* coord_k, const float* trans_coeff, const float* tau, const int32_t* key_lens,
-                void* out, float* lse, void* workspace, int64_t workspace_bytes, void* stream) {
+                bool gather, const int32_t* key_idx, void* out, float* lse, void* workspace, int64_t workspace_bytes, void* stream) {
     int rc = check_common(d);
     if (rc) return rc;
     if (!k || !v || ((!q || !out) && !(d->flags & GTA_FLAG_PREP_ONLY))) return fail(GTA_E_BADARG, "null q/k/v/out");
+    if (gather && !key_idx && !(d->flags & GTA_FLAG_KV_READY)) return fail(GTA_E_BADARG, "null key_idx");
     if ((rc = staged_layout(d))) return rc;
     if ((d->d_se3 > 0 || d->d_so3 > 0) && (!vrep_q || !vrep_k)) return fail(GTA_E_BADARG, "se3/so3 slabs need vrep_q and vrep_k");
     if (d->d_so2 > 0 && (!cs_q || !cs_k)) return fail(GTA_E_BADARG, "so2 slab needs cs_q and cs_k");
@@ -401,7 +403,8 @@ int staged_call(const GtaAttnDesc* d, const void* q, const void* k, const void* 
     p.n_items = (int)n_items;
     p.scale = d->scale;
     p.key_lens = key_lens;
-    rc = gta_gen_dispatch(p, dhp, !(d->flags & GTA_FLAG_KV_READY), !(d->flags & GTA_FLAG_PREP_ONLY), stream);
+    const bool run_prep = !(d->flags & GTA_FLAG_KV_READY), run_attn = !(d->flags & GTA_FLAG_PREP_ONLY);
+    rc = gather ? gta_gen_gather_dispatch(p, run_prep ? key_idx : nullptr, dhp, run_prep, run_attn, stream) : gta_gen_dispatch(p, dhp, run_prep, run_attn, stream);
     if (rc) return fail(rc, gta_gen_error());       // (the launchers read HIP's error, which clears it: they keep its text)
     return GTA_OK;
 }
@@ -411,7 +414,7 @@ extern "C" int gta_attn_fwd_staged(const GtaAttnDesc* d, const void* q, const vo
                                    const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
                                    const float* coord_q, const float* coord_k, const float* trans_coeff, const float* tau,
                                    void* out, float* lse, void* workspace, int64_t workspace_bytes, void* stream) {
-    return staged_call(d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, coord_q, coord_k, trans_coeff, tau, nullptr, out, lse, workspace, workspace_bytes, stream);
+    return staged_call(d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, coord_q, coord_k, trans_coeff, tau, nullptr, false, nullptr, out, lse, workspace, workspace_bytes, stream);
 }
 
 extern "C" int gta_attn_fwd_staged_varlen_supported(const GtaAttnDesc* desc) { return gta_attn_fwd_staged_supported(desc); }
@@ -421,7 +424,19 @@ extern "C" int gta_attn_fwd_staged_varlen(const GtaAttnDesc* d, const void* q, c
                                           const float* coord_q, const float* coord_k, const float* trans_coeff, const float* tau,
                                           const int32_t* key_lens, void* out, float* lse, void* workspace, int64_t workspace_bytes, void* stream) {
     if (!key_lens) return fail(GTA_E_BADARG, "null key_lens");
-    return staged_call(d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, coord_q, coord_k, trans_coeff, tau, key_lens, out, lse, workspace, workspace_bytes, stream);
+    return staged_call(d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, coord_q, coord_k, trans_coeff, tau, key_lens, false, nullptr, out, lse, workspace, workspace_bytes, stream);
+}
+
+// Any per-scene subset of the key tokens on the staged layouts: gta_attn_fwd_staged_varlen with the GATHER instances of gta_gen_prep_kernel
+extern "C" int gta_attn_fwd_staged_gather_supported(const GtaAttnDesc* desc) { return gta_attn_fwd_staged_supported(desc); }
+
+extern "C" int gta_attn_fwd_staged_gather(const GtaAttnDesc* d, const void* q, const void* k, const void* v,
+                                          const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
+                                          const float* coord_q, const float* coord_k, const float* trans_coeff, const float* tau,
+                                          const int32_t* key_idx, const int32_t* key_lens, void* out, float* lse,
+                                          void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!key_lens) return fail(GTA_E_BADARG, "null key_lens");
+    return staged_call(d, q, k, v, vrep_q, vrep_k, cs_q, cs_k, coord_q, coord_k, trans_coeff, tau, key_lens, true, key_idx, out, lse, workspace, workspace_bytes, stream);
 }
 
 

@@ -45,15 +45,20 @@ GTA_DEV ApplyParams gen_row_params(const GtaGenParams& p, int mode) {
 }
 
 // Rows [t0, t0 + R) of one (b,h) (base: its row 0, rs bytes between rows) -> an fp32 stage [R][dh + 1]: 16-byte units, consecutive
-// threads take consecutive units of a row (coalesced); rows past T become zero rows.  NT threads share the work.
-template <int NT>
-GTA_DEV void gen_rows_in(float* stage, const char* base, long rs, int t0, int T, int R, int dh, int esz, int tid) {
+// threads take consecutive units of a row (coalesced); rows past T become zero rows.  NT threads share the work.  GATHER: stage row r is the
+// row of token tok[r] (an LDS row of R token numbers, each inside the scene), still for t0 + r < T alone.
+template <int NT, bool GATHER = false>
+GTA_DEV void gen_rows_in(float* stage, const char* base, long rs, int t0, int T, int R, int dh, int esz, int tid, const int* tok = nullptr) {
     const int U = dh * esz / 16, per = 16 / esz;
     for (int idx = tid; idx < R * U; idx += NT) {
         const int r = idx / U, u = idx - r * U;
         float* dst = stage + r * (dh + 1) + u * per;
         u32x4_t w = {0u, 0u, 0u, 0u};
-        if (t0 + r < T) w = *reinterpret_cast<const u32x4_t*>(base + (long)(t0 + r) * rs + u * 16);
+        if constexpr (GATHER) {
+            if (t0 + r < T) w = *reinterpret_cast<const u32x4_t*>(base + (long)tok[r] * rs + u * 16);
+        } else {
+            if (t0 + r < T) w = *reinterpret_cast<const u32x4_t*>(base + (long)(t0 + r) * rs + u * 16);
+        }
         if (esz == 2) {
             float x[8];
             unpack8(w, x);
@@ -85,6 +90,8 @@ GTA_DEV void gen_rows_out(const float* stage, char* base, long rs, int t0, int T
     }
 }
 
+GTA_DEV const int32_t* first_gen_idx(const int32_t* key_idx) { return key_idx; }
+
 template <int DHP>
 struct GenPrepSmem {
     static constexpr int CHP = DHP / 8;
@@ -95,15 +102,26 @@ struct GenPrepSmem {
     static constexpr int OFF_IMGK = OFF_SV + STAGE_F * 4;
     static constexpr int OFF_IMGV = OFF_IMGK + IMG;
     static constexpr int TOTAL = OFF_IMGV + IMG;
+    static constexpr int OFF_TOK = TOTAL;                 // (GATHER instances alone) the tile's 64 token numbers
+    static constexpr int TOTAL_GATHER = TOTAL + BN * 4;
     static_assert(OFF_IMGK % 16 == 0, "image alignment");
 };
 
 // VARLEN (both kernels): scene b's keys are the prefix of p.key_lens[b] tokens -- the pre-pass skips the tiles past it and treats the rows
 // of its last tile past it as it treats the rows past Tk (zero rows, bias 0, no table read); the attention kernel walks and masks by it.
-template <int DHP, bool VARLEN = false>
-__global__ __launch_bounds__(256) void gta_gen_prep_kernel(const GtaGenParams p) {
+//
+// GATHER (gta_attn_fwd_staged_gather; VARLEN plus a gather): scene b's keys are ANY p.key_lens[b] of its tokens, compacted -- image row r of
+// tile j is built from token key_idx[b * Tk + 64 j + r] (clamped into [0, Tk): no value moves a load out of the scene's K, V or table rows):
+// its K / V rows, its view record, its (cos, sin) and coord rows; its bias goes to the COMPACTED position 64 j + r.  The zero rows and the
+// skipped tiles are those of VARLEN.  key_idx entries at or past the count are never read, nor is any token that no live entry names.  The
+// GATHER instances alone take the trailing argument (IDX = const int32_t*: key_idx, [B, Tk] on the device) and 256 bytes of LDS for the
+// tile's token numbers; without it IDX is empty and the kernel's arguments are what they were.
+template <int DHP, bool VARLEN = false, class... IDX>
+__global__ __launch_bounds__(256) void gta_gen_prep_kernel(const GtaGenParams p, const IDX... idx) {
     using S = GenPrepSmem<DHP>;
     constexpr int CHP = S::CHP;
+    constexpr bool GATHER = sizeof...(IDX) == 1;
+    static_assert(sizeof...(IDX) <= 1 && (!GATHER || VARLEN), "key_idx comes with GATHER, which compacts into a per-scene prefix");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -128,19 +146,30 @@ __global__ __launch_bounds__(256) void gta_gen_prep_kernel(const GtaGenParams p)
     float* sv = reinterpret_cast<float*>(smem + S::OFF_SV);
     const char* kg = (const char*)p.k + ((long)b * p.k_sb + (long)h * p.k_sh) * p.esz;
     const char* vg = (const char*)p.v + ((long)b * p.v_sb + (long)h * p.v_sh) * p.esz;
-    gen_rows_in<256>(sk, kg, p.k_st * p.esz, j * BN, GTA_TKB, BN, dh, p.esz, tid);
-    gen_rows_in<256>(sv, vg, p.v_st * p.esz, j * BN, GTA_TKB, BN, dh, p.esz, tid);
-    __syncthreads();
-    // rho_k: lane == key row; the rows past Tk stay zero rows (score 0 and bias 0: the attention kernel masks them)
     const int t = j * BN + lane;
+    const int* stok = nullptr;
+    if constexpr (GATHER) {
+        // the tile's token numbers -> LDS (a dead row's entry is not read from key_idx, and never used)
+        int* w = reinterpret_cast<int*>(smem + S::OFF_TOK);
+        if (wave == 0) w[lane] = t < tk_b ? min(max(first_gen_idx(idx...)[(long)b * p.Tk + t], 0), p.Tk - 1) : 0;
+        __syncthreads();
+        stok = w;
+    }
+    gen_rows_in<256, GATHER>(sk, kg, p.k_st * p.esz, j * BN, GTA_TKB, BN, dh, p.esz, tid, stok);
+    gen_rows_in<256, GATHER>(sv, vg, p.v_st * p.esz, j * BN, GTA_TKB, BN, dh, p.esz, tid, stok);
+    __syncthreads();
+    // rho_k: lane == key row; the rows past Tk stay zero rows (score 0 and bias 0: the attention kernel masks them).  (GATHER) rho_k of the
+    // row's TOKEN -- its view record, its (cos, sin) and coord rows --, the bias at the compacted position t
+    int tok = t;
+    if constexpr (GATHER) tok = stok[lane];
     if (wave == 0) {
         ApplyParams a = gen_row_params(p, 1);
         a.key_bias = p.kbias;
-        if (t < GTA_TKB) apply_row(a, b, h, t, LIn{sk + lane * rowf}, LOut{sk + lane * rowf});
+        if (t < GTA_TKB) apply_row(a, b, h, tok, LIn{sk + lane * rowf}, LOut{sk + lane * rowf}, GATHER ? t : -1);
         else if (p.kbias) p.kbias[((long)b * p.H + h) * a.bias_pitch + t] = 0.f;
     } else if (wave == 1 && p.xv) {
         const ApplyParams a = gen_row_params(p, 1);
-        if (t < GTA_TKB) apply_row(a, b, h, t, LIn{sv + lane * rowf}, LOut{sv + lane * rowf});
+        if (t < GTA_TKB) apply_row(a, b, h, tok, LIn{sv + lane * rowf}, LOut{sv + lane * rowf});
     }
 #undef GTA_TKB
     __syncthreads();
@@ -378,14 +407,15 @@ int gen_hip_status(int rc_on_error) {
     return rc_on_error;
 }
 
-template <int DHP, bool VARLEN>
-int launch_gen_prep(const GtaGenParams& p, hipStream_t stream) {
+template <int DHP, bool VARLEN, class... IDX>
+int launch_gen_prep(const GtaGenParams& p, hipStream_t stream, IDX... idx) {
     using S = GenPrepSmem<DHP>;
-    if (int rc = gta_lds_optin<&gta_gen_prep_kernel<DHP, VARLEN>>(S::TOTAL)) { gen_hip_status(rc); return rc; }
+    constexpr int lds = sizeof...(IDX) ? S::TOTAL_GATHER : S::TOTAL;
+    if (int rc = gta_lds_optin<&gta_gen_prep_kernel<DHP, VARLEN, IDX...>>(lds)) { gen_hip_status(rc); return rc; }
     const long rows = (long)p.B * p.n_tiles;
     const long grid = (rows + 7) / 8 * 8 * p.H;
     if (grid > 0x7fffffffL) { g_gen_error = "pre-pass grid too large"; return GTA_E_UNSUPPORTED; }
-    hipLaunchKernelGGL((gta_gen_prep_kernel<DHP, VARLEN>), dim3((unsigned)grid), dim3(256), S::TOTAL, stream, p);
+    hipLaunchKernelGGL((gta_gen_prep_kernel<DHP, VARLEN, IDX...>), dim3((unsigned)grid), dim3(256), lds, stream, p, idx...);
     return gen_hip_status(GTA_E_LAUNCH);
 }
 
@@ -410,10 +440,10 @@ static_assert(gen_attn_lds<32, true>() == 27648 && gen_attn_lds<64, true>() == 5
               gen_attn_lds<128, true>() == 101376, "attention LDS bytes with the bias slots");
 
 template <int DHP>
-int gen_dispatch(const GtaGenParams& p, bool run_prep, bool run_attn, hipStream_t stream) {
-    if (p.key_lens) {                                     // the VARLEN instances (gta_attn_fwd_staged_varlen)
+int gen_dispatch(const GtaGenParams& p, bool gather, const int32_t* key_idx, bool run_prep, bool run_attn, hipStream_t stream) {
+    if (p.key_lens) {                                     // the VARLEN instances (gta_attn_fwd_staged_varlen); gather: the GATHER pre-pass before them
         if (run_prep)
-            if (int rc = launch_gen_prep<DHP, true>(p, stream)) return rc;
+            if (int rc = gather ? launch_gen_prep<DHP, true>(p, stream, key_idx) : launch_gen_prep<DHP, true>(p, stream)) return rc;
         if (!run_attn) return GTA_OK;
         return p.kbias ? launch_gen_attn<DHP, true, true>(p, stream) : launch_gen_attn<DHP, false, true>(p, stream);
     }
@@ -437,13 +467,26 @@ long gta_gen_workspace_bytes(int B, int H, int Tk, int dhp) {
 
 const char* gta_gen_error() { return g_gen_error; }
 
-int gta_gen_dispatch(const GtaGenParams& p, int dhp, bool run_prep, bool run_attn, void* stream) {
+namespace {
+int gen_dispatch_dhp(const GtaGenParams& p, bool gather, const int32_t* key_idx, int dhp, bool run_prep, bool run_attn, void* stream) {
     g_gen_error = "no kernel instance";
     switch (dhp) {
-        case 32: return gen_dispatch<32>(p, run_prep, run_attn, (hipStream_t)stream);
-        case 64: return gen_dispatch<64>(p, run_prep, run_attn, (hipStream_t)stream);
-        case 96: return gen_dispatch<96>(p, run_prep, run_attn, (hipStream_t)stream);
-        case 128: return gen_dispatch<128>(p, run_prep, run_attn, (hipStream_t)stream);
+        case 32: return gen_dispatch<32>(p, gather, key_idx, run_prep, run_attn, (hipStream_t)stream);
+        case 64: return gen_dispatch<64>(p, gather, key_idx, run_prep, run_attn, (hipStream_t)stream);
+        case 96: return gen_dispatch<96>(p, gather, key_idx, run_prep, run_attn, (hipStream_t)stream);
+        case 128: return gen_dispatch<128>(p, gather, key_idx, run_prep, run_attn, (hipStream_t)stream);
     }
     return GTA_E_UNSUPPORTED;
+}
+}  // namespace
+
+int gta_gen_dispatch(const GtaGenParams& p, int dhp, bool run_prep, bool run_attn, void* stream) {
+    return gen_dispatch_dhp(p, false, nullptr, dhp, run_prep, run_attn, stream);
+}
+
+// the GATHER pre-pass (gta_attn_fwd_staged_gather): p.key_lens counts the compacted keys, key_idx names them (read by the pre-pass alone)
+int gta_gen_gather_dispatch(const GtaGenParams& p, const int32_t* key_idx, int dhp, bool run_prep, bool run_attn, void* stream) {
+    g_gen_error = "the gather comes with key_lens, and its pre-pass with key_idx";
+    if (!p.key_lens || (run_prep && !key_idx)) return GTA_E_BADARG;
+    return gen_dispatch_dhp(p, true, key_idx, dhp, run_prep, run_attn, stream);
 }

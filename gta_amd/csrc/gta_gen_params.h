@@ -22,4 +22,6 @@ struct GtaGenParams {
 long gta_gen_image_bytes(int B, int H, int Tk, int dhp);
 long gta_gen_workspace_bytes(int B, int H, int Tk, int dhp);
 int gta_gen_dispatch(const GtaGenParams& p, int dhp, bool run_prep, bool run_attn, void* stream);      // (p.key_lens set: the VARLEN instances)
+// the same with the GATHER instances of the pre-pass: image row r of tile j of scene b from token key_idx[b, 64 j + r] ([B, Tk] int32 on the device)
+int gta_gen_gather_dispatch(const GtaGenParams& p, const int32_t* key_idx, int dhp, bool run_prep, bool run_attn, void* stream);
 const char* gta_gen_error();               // after a failed gta_gen_dispatch on this thread: HIP's own words for it (static storage)

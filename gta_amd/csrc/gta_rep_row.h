@@ -40,8 +40,9 @@ GTA_DEV void row_decode(long row, int T, int H, int& b, int& h, int& t) {
     b = (int)(row / ((long)T * H));
 }
 
+// bias_t: where the row's key bias goes in its (b, h) line, when that is not its token (-1: at t) -- the compacted position under a gather
 template <class In, class Out>
-GTA_DEV void apply_row(const ApplyParams& p, const int b, const int h, const int t, const In X, const Out Y) {
+GTA_DEV void apply_row(const ApplyParams& p, const int b, const int h, const int t, const In X, const Out Y, const int bias_t = -1) {
     const float tc = p.trans_coeff ? *p.trans_coeff : 1.0f;
     const int n = t / p.P;
     const float* vr = p.vrep ? p.vrep + ((long)b * p.N + n) * GTA_VREP_STRIDE : nullptr;
@@ -115,7 +116,7 @@ GTA_DEV void apply_row(const ApplyParams& p, const int b, const int h, const int
             Y(ch, v0); Y(ch + 1, v1); Y(ch + 2, v2); sq += v0 * v0 + v1 * v1 + v2 * v2;
         }
     }
-    if (p.key_bias) p.key_bias[((long)b * p.H + h) * p.bias_pitch + t] = -0.5f * p.bias_scale * sq;
+    if (p.key_bias) p.key_bias[((long)b * p.H + h) * p.bias_pitch + (bias_t < 0 ? t : bias_t)] = -0.5f * p.bias_scale * sq;
 }
 
 }  // namespace

@@ -462,6 +462,10 @@ def _generic_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scal
     return fn.apply(q, k, v, tc, ta, (f_dims, so3_degree, scale, v_transform, euclid, precise), packed, *carriers)
 
 
+_NO_GATHER_PREPASS = ("key_mask: the staged and rho-apply layouts (t2, euclid, so3 of degree 1, unaligned slabs) have no gather "
+                      "pre-pass: ")
+
+
 def _probe(dtype, q_shape, Tk: int, f_dims, so3_degree: int, Nq: int, Nk: int, flags: int):
     """the descriptor the routes ask the library about: the call's sizes at contiguous strides"""
     B, H, Tq, dh = q_shape
@@ -471,7 +475,7 @@ def _probe(dtype, q_shape, Tk: int, f_dims, so3_degree: int, Nq: int, Nk: int, f
 
 def generic_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree: int, Nq: int, Nk: int, *, v_transform: bool = True,
                   euclid: bool = False, precise: bool = False, needs_grad: bool = False, key_views: bool = False,
-                  key_views_backward: bool = False) -> str:
+                  key_views_backward: bool = False, key_mask_generic: bool = False) -> str:
     """How ``gta_attention`` runs a call that ``attention_route`` hands to the generic path (it answered None):
     'staged' = the staged generic forward (``gta_attn_fwd_staged``: K/V pre-pass + one attention kernel, honours ``kv_cache``) when the
                library serves the descriptor, no gradient is needed and the arithmetic is the default one;
@@ -479,7 +483,23 @@ def generic_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree: i
     Sizes alone decide, as in ``attention_route`` (the descriptor is probed at contiguous strides); needs no GPU.
     key_views=True (the call comes with per-scene view counts): 'staged' means its varlen entry (``gta_attn_fwd_staged_varlen``), and a
     call that would be 'apply' raises ``GtaError`` instead -- ``_GenericAttn`` has no key mask; that holds under ``key_views_backward`` too (the
-    backward with per-scene prefixes serves the fused layouts alone)."""
+    backward with per-scene prefixes serves the fused layouts alone).
+    key_mask_generic=True (the call comes with a key mask and its opt-in to these layouts): 'staged' means the gather entry
+    (``gta_attn_fwd_staged_gather``), and everything else raises ``GtaError``: a call under grad (forward only, whatever ``key_mask_backward``
+    says), precise=True, and the layouts the staged entry refuses too, which keep the words of the call without the opt-in."""
+    if key_mask_generic:
+        if key_views:
+            raise native.GtaError("key_mask with key_views: a call takes one key mask")
+        if needs_grad:
+            raise native.GtaError("key_mask_generic is forward-only: the staged generic layouts (t2, euclid, so3 of degree 1, unaligned slabs) "
+                                  "have no masked backward, and key_mask_backward serves the fused layouts alone: call under torch.no_grad()")
+        _mask_refusals("key_mask", precise=precise)
+        rc = native.E_UNSUPPORTED
+        if dtype in (torch.float32, torch.bfloat16):
+            rc = native.attn_fwd_staged_gather_supported(_probe(dtype, q_shape, Tk, f_dims, so3_degree, Nq, Nk, _layout_flags(v_transform, euclid)))
+        if rc != 0:
+            raise native.GtaError(_NO_GATHER_PREPASS + f"gta_attn_fwd_staged_gather_supported: {native.lib().gta_strerror(rc).decode()}")
+        return "staged"
     if key_views:
         _mask_refusals("key_views", needs_grad=needs_grad, precise=precise, backward=key_views_backward)
         if needs_grad:
@@ -922,20 +942,33 @@ class _FusedAttnLse(torch.autograd.Function):
 
 
 def _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, kv_cache=None, key_views=None,
-                    key_lens=None, return_lse=False):
+                    key_lens=None, return_lse=False, mask=None):
     """The generic path without a gradient: one pre-pass launch + one attention launch (``gta_attn_fwd_staged``), and the attention
     launch alone on a call that finds its K'/V' images in ``kv_cache`` -- the contract of ``_fused_forward``: images and plan key are stored by
     the first call, later calls against another key set / plan raise ``GtaError``.  ``key_views`` (validated) with ``key_lens`` (device):
-    the varlen entry, and the view counts join the plan key."""
+    the varlen entry, and the view counts join the plan key.  ``mask`` (a ``_Mask`` of kind "gather", no query side): the gather entry
+    (``gta_attn_fwd_staged_gather``) -- the plan key ends in "key_mask", the cache holds ``key_idx`` / ``key_lens`` beside the compacted
+    images and later calls run on the stored lengths, as in ``_fused_forward``."""
     flags = _layout_flags(v_transform, euclid)
     Nq, Nk = _views(f_dims, packed, q, k)
     c = _setup_call(q, k, v, f_dims, so3_degree, Nq, Nk, scale, flags, packed, trans_coeff, tau)
     B, H, Tk, dh = c.k.shape
     # (the workspace's size does not depend on the query side)
-    plan_key = None if kv_cache is None else _plan_key("staged", flags, c.q.dtype, B, H, Tk, dh, f_dims, so3_degree, Nk, scale, key_views)
+    plan_key = None if kv_cache is None else _plan_key("staged", flags, c.q.dtype, B, H, Tk, dh, f_dims, so3_degree, Nk, scale,
+                                                       "key_mask" if mask is not None else key_views)
     ws = _two_stage_workspace(c.desc, flags, plan_key, kv_cache, c.q.device, native.attn_fwd_staged_workspace_bytes(c.desc))
     tables = [packed.get(t) for t in ("vrep_q", "vrep_k", "cs_q", "cs_k", "coord_q", "coord_k")]
-    if key_views is not None:
+    if mask is not None:
+        key_idx, key_lens = mask.key_idx, mask.key_lens
+        if c.desc.flags & native.FLAG_KV_READY:
+            key_idx, key_lens = None, kv_cache["key_lens"]
+        else:
+            if key_lens is None:
+                key_idx, key_lens = key_index_tensors(mask.key_mask, c.q.device)
+            if kv_cache is not None:
+                kv_cache["key_idx"], kv_cache["key_lens"] = key_idx, key_lens
+        native.attn_fwd_staged_gather(c.desc, c.q, c.k, c.v, *tables, c.tc, c.ta, key_idx, key_lens, c.out, c.lse, ws)
+    elif key_views is not None:
         native.attn_fwd_staged_varlen(c.desc, c.q, c.k, c.v, *tables, c.tc, c.ta, key_lens, c.out, c.lse, ws)
     else:
         native.attn_fwd_staged(c.desc, c.q, c.k, c.v, *tables, c.tc, c.ta, c.out, c.lse, ws)
@@ -949,7 +982,7 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
                   key_views=None, key_lens: Optional[torch.Tensor] = None, key_views_backward: bool = False,
                   query_views=None, return_lse: bool = False, key_mask: Optional[torch.Tensor] = None, key_mask_backward: bool = False,
                   query_mask: Optional[torch.Tensor] = None, key_mask_rep_grad: bool = False,
-                  mask_index: Optional[MaskIndex] = None, masked_lse_backward: bool = False):
+                  mask_index: Optional[MaskIndex] = None, masked_lse_backward: bool = False, key_mask_generic: bool = False):
     """Fused GTA attention on packed reps.  q [B,H,Tq,dh], k/v [B,H,Tk,dh] -> out [B,H,Tq,dh].
 
     kv_mode: 'prepass' = K/V rep pre-pass + lean attention kernel (two launches; at dh = 96 in the MSN layout the attention kernel is
@@ -1037,6 +1070,12 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
              an arange (no sort) -- and with everything that route refuses: under grad it needs ``key_mask_backward=True``.  Refused by
              name: ``key_views`` / ``query_views`` / ``key_lens`` / ``key_views_backward`` beside it, ``kv_cache``, and what ``key_mask``
              refuses.  ``return_lse`` without grad is served.
+    key_mask_generic: only with ``key_mask``.  False (default): a key mask on a layout without a fused kernel (t2 slab, euclid, so3 of degree
+             1, unaligned slabs) raises "no gather pre-pass", as it always did.  True: such a call runs the staged generic forward over the
+             masked keys (``gta_attn_fwd_staged_gather``: the GATHER instances of its pre-pass compact the valid keys and their euclid
+             bias, its VARLEN attention kernel attends over them) -- forward only (under grad it raises, ``key_mask_backward`` or not),
+             no ``query_mask``, with ``return_lse``, ``mask_index`` and ``kv_cache`` as on the fused layouts; layouts the staged entry
+             refuses too (dh % 8 != 0, dh > 128) keep the old words.  On a fused layout it changes nothing.
     mask_index: the ``MaskIndex`` of this call's ``key_mask`` / ``query_mask`` (``gta_amd.mask_index``: one launch builds every tensor the
              masked kernels read) -- a companion of the masks, as ``key_lens`` is of ``key_views``.  The call then builds nothing from the
              masks: forward, ``kv_cache``, backward and the rep-gradient pass run on the record's tensors, so one record serves every layer of
@@ -1049,11 +1088,12 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
         pretransformed=pretransformed, use_dma=use_dma, kv_mode=kv_mode, kv_cache=kv_cache, precise=precise, key_views=key_views,
         key_lens=key_lens, key_views_backward=key_views_backward, query_views=query_views, return_lse=return_lse, key_mask=key_mask,
         key_mask_backward=key_mask_backward, query_mask=query_mask, key_mask_rep_grad=key_mask_rep_grad, mask_index=mask_index,
-        masked_lse_backward=masked_lse_backward)
+        masked_lse_backward=masked_lse_backward, key_mask_generic=key_mask_generic)
     scale = cfg[4]
     if route == "staged":
         return _staged_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, kv_cache,
-                               key_views=mask.views and mask.views[1], key_lens=mask.key_lens, return_lse=return_lse)
+                               key_views=mask.views and mask.views[1], key_lens=mask.key_lens, return_lse=return_lse,
+                               mask=mask if mask.kind == "gather" else None)
     if route == "apply":
         return _generic_forward(q, k, v, f_dims, packed, so3_degree, trans_coeff, tau, scale, v_transform, euclid, precise=bool(precise),
                                 carriers=carriers, return_lse=return_lse)
@@ -1071,10 +1111,11 @@ def gta_attention(q, k, v, f_dims: Dict[str, int], packed: dict, *, so3_degree: 
 
 def _resolve(q, k, v, f_dims, packed, *, so3_degree, trans_coeff, tau, scale, v_transform, euclid, pretransformed, use_dma, kv_mode, kv_cache,
              precise, key_views, key_lens, key_views_backward, query_views, return_lse, key_mask, key_mask_backward, query_mask,
-             key_mask_rep_grad, mask_index=None, masked_lse_backward=False):
+             key_mask_rep_grad, mask_index=None, masked_lse_backward=False, key_mask_generic=False):
     """The host-only half of ``gta_attention`` (its arguments, the keyword-only ones by keyword): every refusal, in a fixed order, then how the call runs.
     -> (route, cfg, mask, packed, carriers, trans_coeff, tau): route 'fused' (through ``_FusedAttn``: every unmasked call, a masked one under
-    grad), 'forward' (a masked call without grad: ``_fused_forward`` alone), 'staged' or 'apply' (``generic_route``);
+    grad), 'forward' (a masked call without grad: ``_fused_forward`` alone), 'staged' or 'apply' (``generic_route``; 'staged' with a mask
+    record of kind "gather" for a key mask under ``key_mask_generic``);
     cfg = (f_dims, so3_degree, Nq, Nk, scale, flags), flags None off the fused routes; the ``_Mask`` record; the tables the kernels read
     (detached) and their carriers (``repgrad.split_tables``); trans_coeff and tau as tensors or None."""
     shape, Tk = tuple(q.shape), k.shape[2]
@@ -1082,6 +1123,8 @@ def _resolve(q, k, v, f_dims, packed, *, so3_degree, trans_coeff, tau, scale, v_
     views_given = key_views is not None or key_lens is not None or key_views_backward or query_views is not None
     if key_mask_backward and key_mask is None and query_mask is None:
         raise native.GtaError("key_mask_backward=True comes with key_mask")
+    if key_mask_generic and key_mask is None and query_mask is None:
+        raise native.GtaError("key_mask_generic=True comes with key_mask")
     if key_mask_rep_grad and not key_mask_backward:
         raise native.GtaError("key_mask_rep_grad=True comes with key_mask_backward=True (the pose / coordinate gradients are a pass after "
                               "the masked backward)")
@@ -1148,7 +1191,7 @@ def _resolve(q, k, v, f_dims, packed, *, so3_degree, trans_coeff, tau, scale, v_
                                       "(drop return_lse, or call under torch.no_grad())")
     how = dict(v_transform=v_transform, euclid=euclid, precise=bool(precise), needs_grad=needs_grad)
     if masked:          # (key_views and its companions beside a mask were refused above)
-        how.update(key_mask=True, key_mask_backward=bool(key_mask_backward))
+        how.update(key_mask=True, key_mask_backward=bool(key_mask_backward), key_mask_generic=bool(key_mask_generic))
     else:
         how.update(key_views=key_views is not None, key_views_backward=bool(key_views_backward))
     flags = attention_route(shape, Tk, q.dtype, f_dims, so3_degree, Nq, Nk, pretransformed=pretransformed, use_dma=use_dma,
@@ -1156,7 +1199,13 @@ def _resolve(q, k, v, f_dims, packed, *, so3_degree, trans_coeff, tau, scale, v_
     if mask_index is not None:          # (behind every refusal of the masks themselves: their messages are what they were)
         _check_mask_index(mask_index, key_mask, query_mask, B, Tq, Tk, q.device)
     cfg = ({k_: int(v_) for k_, v_ in f_dims.items()}, int(so3_degree), Nq, Nk, float(scale), flags)
-    if masked:           # (attention_route never answers None under a mask: the generic layouts have no gather pre-pass)
+    if masked and flags is None:
+        # a staged generic layout under key_mask_generic (without it attention_route raised "no gather pre-pass"); never under grad
+        if query_mask is not None:
+            raise native.GtaError("query_mask: the staged generic layouts (t2, euclid, so3 of degree 1, unaligned slabs) have no query-side "
+                                  "mask (key_mask_generic serves the key side alone)")
+        return "staged", cfg, _gather_mask(key_mask, None, q, k, False, (), mask_index), packed, carriers, trans_coeff, tau
+    if masked:
         mask = _gather_mask(key_mask, query_mask, q, k, needs_grad, carriers, mask_index)
         return "fused" if needs_grad else "forward", cfg, mask, packed, carriers, trans_coeff, tau
     # no fused kernel: 'staged' or 'apply' (under key_views: 'staged', or it raises)
@@ -1219,7 +1268,7 @@ _KEY_SIDE_TABLES = ("vrep_k", "cs_k", "coord_k", "grad_cs_k", "grad_coord_k")
 
 # the keywords of ``gta_attention`` that mask a call, as the layers hand them on: masks and view counts first (absent when None), then the
 # opt-in flags (absent unless set)
-MASK_OPT_INS = ("key_views_backward", "key_mask_backward", "key_mask_rep_grad")
+MASK_OPT_INS = ("key_views_backward", "key_mask_backward", "key_mask_rep_grad", "key_mask_generic")
 MASK_KEYWORDS = ("key_views", "key_mask", "query_views", "query_mask", "mask_index") + MASK_OPT_INS
 # what ``gta_attention_by_view_groups`` refuses: the key-side masks among them (a query mask and its opt-ins go to every group's call)
 _NOT_PER_GROUP = ("kv_cache", "key_views", "key_lens", "key_views_backward", "query_views", "return_attmap", "key_mask", "mask_index")
@@ -1298,7 +1347,8 @@ KV_MODES = {
 def attention_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree: int, Nq: int, Nk: int, *, v_transform: bool = True,
                     euclid: bool = False, pretransformed: bool = False, use_dma: bool = True, kv_mode: str = "auto",
                     kv_cache: bool = False, precise: bool = False, needs_grad: bool = False, key_views: bool = False,
-                    key_views_backward: bool = False, key_mask: bool = False, key_mask_backward: bool = False) -> Optional[int]:
+                    key_views_backward: bool = False, key_mask: bool = False, key_mask_backward: bool = False,
+                    key_mask_generic: bool = False) -> Optional[int]:
     """How ``gta_attention`` runs a call: the descriptor flags of the fused path, or None for the generic one (rho-apply kernels around the
     plain attention kernel).  q_shape = (B, H, Tq, dh); Tk keys; dtype of q.
 
@@ -1312,7 +1362,9 @@ def attention_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree:
 
     key_mask=True (the call comes with a key mask): the flags of ``gta_attn_fwd_gather`` -- the two-stage plan --, never None: the layouts
     without a fused kernel have no gather pre-pass and raise ``GtaError`` like every other combination without one.  key_mask_backward=True
-    lets needs_grad through: the same flags serve ``gta_attn_bwd_gather``."""
+    lets needs_grad through: the same flags serve ``gta_attn_bwd_gather``.  key_mask_generic=True (beside key_mask) changes nothing on a fused
+    layout; on a layout without a fused kernel the answer is then None -- ``generic_route`` answers for the gather entry of the staged kernels
+    (``gta_attn_fwd_staged_gather``) and says every refusal of it, a call under grad among them."""
     if kv_mode not in KV_MODES:
         raise ValueError(f"kv_mode {kv_mode!r}")
     flags = KV_MODES[kv_mode] | _layout_flags(v_transform, euclid) | (0 if use_dma else native.FLAG_NO_DMA)
@@ -1323,9 +1375,12 @@ def attention_route(q_shape, Tk: int, dtype, f_dims: Dict[str, int], so3_degree:
         _mask_refusals("key_mask", needs_grad=needs_grad, precise=precise, pretransformed=pretransformed, kv_mode=kv_mode,
                        backward=key_mask_backward)
         rc = native.attn_fwd_supported(probe(flags))
+        if rc == native.E_UNSUPPORTED and key_mask_generic:         # a generic layout under the opt-in: the staged gather entry, or its refusals
+            generic_route(q_shape, Tk, dtype, f_dims, so3_degree, Nq, Nk, v_transform=v_transform, euclid=euclid, precise=precise,
+                          needs_grad=needs_grad, key_mask_generic=True)
+            return None
         if rc == native.E_UNSUPPORTED:
-            raise native.GtaError("key_mask: the staged and rho-apply layouts (t2, euclid, so3 of degree 1, unaligned slabs) have no gather "
-                                  f"pre-pass: gta_attn_fwd_supported: {native.lib().gta_strerror(rc).decode()}")
+            raise native.GtaError(_NO_GATHER_PREPASS + f"gta_attn_fwd_supported: {native.lib().gta_strerror(rc).decode()}")
         native.check(native.attn_fwd_gather_supported(probe(flags)), "gta_attn_fwd_gather_supported")
         return flags
     if key_views:

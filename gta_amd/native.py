@@ -57,6 +57,7 @@ ABI_SYMBOLS = (
     "gta_mask_index",
     "gta_attn_bwd_varlen_dlse", "gta_attn_bwd_varlen_dlse_supported", "gta_attn_bwd_gather_dlse", "gta_attn_bwd_gather_dlse_supported",
     "gta_attn_bwd_qmask_dlse", "gta_attn_bwd_qmask_dlse_supported",
+    "gta_attn_fwd_staged_gather", "gta_attn_fwd_staged_gather_supported",
 )
 MERGE_MAX = 8           # partial attentions per gta_attn_merge call
 
@@ -157,6 +158,9 @@ def lib():
         L.gta_attn_fwd_qmask_supported.argtypes = [ctypes.POINTER(GtaAttnDesc)]
         L.gta_attn_fwd_staged_varlen.argtypes = [ctypes.POINTER(GtaAttnDesc)] + [c_void_p] * 15 + [c_int64, c_void_p]
         L.gta_attn_fwd_staged_varlen_supported.argtypes = [ctypes.POINTER(GtaAttnDesc)]
+        # gta_attn_fwd_staged_varlen with key_idx ([B, Tk] int32, device) in front of key_lens
+        L.gta_attn_fwd_staged_gather.argtypes = [ctypes.POINTER(GtaAttnDesc)] + [c_void_p] * 16 + [c_int64, c_void_p]
+        L.gta_attn_fwd_staged_gather_supported.argtypes = [ctypes.POINTER(GtaAttnDesc)]
         # gta_attn_bwd with key_lens, q_lens ([B] int32, device; q_lens may be NULL) in front of kv_images
         L.gta_attn_bwd_varlen.argtypes = ([ctypes.POINTER(GtaAttnDesc)] + [c_void_p] * 18
                                           + [ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_int64, c_void_p])
@@ -430,6 +434,14 @@ def attn_fwd_staged_varlen(desc: GtaAttnDesc, q, k, v, vrep_q, vrep_k, cs_q, cs_
               workspace, key_lens)
 
 
+def _staged_fwd_gather(desc: GtaAttnDesc, q, k, v, vrep_q, vrep_k, cs_q, cs_k, coord_q, coord_k, trans_coeff, tau, key_idx, key_lens, out,
+                       lse, workspace: torch.Tensor):
+    """``native.attn_fwd_staged_gather`` (served by name, see ``_OPT_IN_ENTRIES`` below): ``attn_fwd_staged_varlen`` over the key_lens[b] tokens key_idx[b, :key_lens[b]] names (see ``attn_fwd_gather``): the GATHER instances
+    of the staged pre-pass compact them, the euclid key bias with them.  key_idx may be None under FLAG_KV_READY (it is not read)."""
+    _fwd_call("gta_attn_fwd_staged_gather", desc, (q, k, v), (vrep_q, vrep_k, cs_q, cs_k, coord_q, coord_k, trans_coeff, tau), out, lse,
+              workspace, key_lens, key_idx)
+
+
 def attn_fwd_workspace_bytes(desc: GtaAttnDesc) -> int:
     return int(lib().gta_attn_fwd_workspace_bytes(ctypes.byref(desc)))
 
@@ -464,6 +476,11 @@ def attn_fwd_qmask_supported(desc: GtaAttnDesc) -> int:
 
 def attn_fwd_staged_varlen_supported(desc: GtaAttnDesc) -> int:
     return lib().gta_attn_fwd_staged_varlen_supported(ctypes.byref(desc))
+
+
+def attn_fwd_staged_gather_supported(desc: GtaAttnDesc) -> int:
+    """0 when gta_attn_fwd_staged_gather (any per-scene subset of the key tokens, staged layouts) serves desc, else a GTA_E_* code; needs no GPU"""
+    return lib().gta_attn_fwd_staged_gather_supported(ctypes.byref(desc))
 
 
 def forward_family(desc: GtaAttnDesc, varlen: bool = False):
@@ -685,16 +702,17 @@ def _masked_bwd_qmask_dlse(desc: GtaAttnDesc, q, k, v, out, dout, lse, dlse, vre
               (key_idx, key_lens, q_live, q_lens), kv_images, dq, dk, dv, dtrans_coeff, workspace, dtau, dlse=(dlse,))
 
 
-# ``native.attn_bwd_varlen_dlse`` / ``attn_bwd_gather_dlse`` / ``attn_bwd_qmask_dlse``: served by name here and kept out of ``dir(native)``.
-# The recorder of call routes (tests/_call_routes.py) takes every ``attn_bwd*`` function ``dir()`` lists for a launch entry that its frozen
-# record of the default routes must have called; these three sit behind an opt-in no recorded case sets, so that record cannot hold them.
-_MASKED_DLSE_ENTRIES = {"attn_bwd_varlen_dlse": _masked_bwd_varlen_dlse, "attn_bwd_gather_dlse": _masked_bwd_gather_dlse,
-                        "attn_bwd_qmask_dlse": _masked_bwd_qmask_dlse}
+# ``native.attn_bwd_varlen_dlse`` / ``attn_bwd_gather_dlse`` / ``attn_bwd_qmask_dlse`` and ``native.attn_fwd_staged_gather``: served by name
+# here and kept out of ``dir(native)``.  The recorder of call routes (tests/_call_routes.py) takes every ``attn_fwd*`` / ``attn_bwd*`` function
+# ``dir()`` lists for a launch entry that its frozen record of the default routes must have called; these sit behind opt-ins no recorded case
+# sets (``masked_lse_backward``, ``key_mask_generic``), so that record cannot hold them.
+_OPT_IN_ENTRIES = {"attn_bwd_varlen_dlse": _masked_bwd_varlen_dlse, "attn_bwd_gather_dlse": _masked_bwd_gather_dlse,
+                   "attn_bwd_qmask_dlse": _masked_bwd_qmask_dlse, "attn_fwd_staged_gather": _staged_fwd_gather}
 
 
 def __getattr__(name):
     try:
-        return _MASKED_DLSE_ENTRIES[name]
+        return _OPT_IN_ENTRIES[name]
     except KeyError:
         raise AttributeError(f"module {__name__!r} has no attribute {name!r}") from None
 

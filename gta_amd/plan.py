@@ -56,7 +56,8 @@ class ForwardPlan:
     turned into the device tensor of key lengths once (``key_lens``); every call then goes through the varlen entry of its family.
 
     ``key_mask``: a bool [B, Tk] mask of the keys to attend (``gta_attention``), fixed when the plan is built: its index and length tensors
-    are built once (``key_idx``, ``key_lens``) and every call goes through ``gta_attn_fwd_gather``.  Fused layouts only; not with ``key_views``."""
+    are built once (``key_idx``, ``key_lens``) and every call goes through the gather entry of its family (``gta_attn_fwd_gather``,
+    ``gta_attn_fwd_staged_gather``).  Not with ``key_views``."""
 
     def __init__(self, q, k, v, f_dims: dict, *, so3_degree: int = 0, Nq: int = 1, Nk: int = 1,
                  scale: Optional[float] = None, v_transform: bool = True, flags: int = 0, euclid: bool = False, key_views=None,
@@ -87,12 +88,13 @@ class ForwardPlan:
         if key_mask is not None:
             from .gta import key_index_tensors
             if self._staged:
-                raise native.GtaError("key_mask: the staged layouts (t2, euclid, so3 of degree 1, unaligned slabs) have no gather pre-pass")
-            native.check(native.attn_fwd_gather_supported(self.desc), "gta_attn_fwd_gather_supported")
+                native.check(native.attn_fwd_staged_gather_supported(self.desc), "gta_attn_fwd_staged_gather_supported")
+            else:
+                native.check(native.attn_fwd_gather_supported(self.desc), "gta_attn_fwd_gather_supported")
             self.key_idx, self.key_lens = key_index_tensors(key_mask, q.device)
         self.ws = torch.empty(native.attn_fwd_staged_workspace_bytes(self.desc) if self._staged else native.attn_fwd_workspace_bytes(self.desc),
                               device=q.device, dtype=torch.uint8)
-        # the entry every call goes through, resolved once: its name (gta_attn_fwd[_staged][_varlen]), the bound function, whether the coordinate
+        # the entry every call goes through, resolved once: its name (gta_attn_fwd[_staged][_varlen | _gather]), the bound function, whether the coordinate
         # tables are among its arguments, and the arguments that never change (key_lens where it takes them; the plan's own buffers)
         self._entry = "gta_attn_fwd" + ("_staged" if self._staged else "") + ("_gather" if self.key_idx is not None else
                                                                               "_varlen" if self.key_lens is not None else "")

@@ -188,7 +188,7 @@ class TransformingSRT(nn.Module):
 
     def forward(self, input_images, input_camera_pos, input_rays, target_camera_pos, target_rays, extras=None, input_views=None,
                 input_views_backward=False, input_mask=None, input_mask_backward=False, input_mask_queries=False,
-                input_mask_rep_grad=False, input_mask_index=False):
+                input_mask_rep_grad=False, input_mask_index=False, input_mask_generic=False):
         """``input_views``: per-scene numbers of valid input views (a host sequence of length B, each in 1..N) for batches that mix
         view counts: scene b's first ``input_views[b]`` views are its input, the rest of its [N, ...] slots is padding that no valid
         token ever attends to -- in the encoder's self-attention and in the decoder's cross-attention (``gta_attention``'s
@@ -224,7 +224,12 @@ class TransformingSRT(nn.Module):
         ``input_mask_index``: only with ``input_mask``.  False (default): every layer builds the tensors its kernels read from the mask
         itself, as before.  True: they are built once per forward, in one launch (``gta_amd.mask_index``: the key side, and under
         ``input_mask_queries`` the query side from the same tensor), and every encoder and decoder layer runs on that one record
-        (``gta_attention``'s ``mask_index``; the decoder on its ``keys_only()``).  Same results bit for bit, forward and backward."""
+        (``gta_attention``'s ``mask_index``; the decoder on its ``keys_only()``).  Same results bit for bit, forward and backward.
+
+        ``input_mask_generic``: only with ``input_mask``.  False (default): a model whose attention layout has no fused kernel (the t2 and
+        euclid configs, so3 of degree 1) refuses the mask, as before.  True: every layer of such a model runs the staged generic forward
+        over the masked keys (``gta_attention``'s ``key_mask_generic``) -- inference only, no ``input_mask_queries``; on the fused layouts
+        it changes nothing."""
         extras = {} if extras is None else extras
         if input_mask_backward and input_mask is None:
             raise native.GtaError("input_mask_backward=True comes with input_mask")
@@ -234,6 +239,8 @@ class TransformingSRT(nn.Module):
             raise native.GtaError("input_mask_rep_grad=True comes with input_mask_backward=True")
         if input_mask_index and input_mask is None:
             raise native.GtaError("input_mask_index=True comes with input_mask")
+        if input_mask_generic and input_mask is None:
+            raise native.GtaError("input_mask_generic=True comes with input_mask")
         if input_mask is not None:
             if input_views is not None:
                 raise native.GtaError("input_mask with input_views: a call takes one key mask -- a prefix of views is a mask too")
@@ -243,6 +250,8 @@ class TransformingSRT(nn.Module):
                 extras["key_mask_backward"] = True
             if input_mask_rep_grad:
                 extras["key_mask_rep_grad"] = True
+            if input_mask_generic:
+                extras["key_mask_generic"] = True
             if input_mask_queries:
                 extras["query_mask"] = extras["key_mask"]      # (the encoder's layers: Tq = Tk, the same tokens on both sides)
             if input_mask_index:                               # one record for every layer of this forward
@@ -272,7 +281,7 @@ def _token_mask(input_mask):
 
 @torch.no_grad()
 def render_image(model: "TransformingSRT", z, camera_pos, rays, extras, max_num_rays: int = 8192, reuse_kv: bool = True, input_views=None,
-                 input_mask=None):
+                 input_mask=None, input_mask_generic=False):
     """Full-image decode of one target view per scene, in query chunks (trainer.py:137-181).
 
     z [B,K,C] scene tokens from ``model.encoder`` (whose call also left the key-side reps in ``extras``);
@@ -282,8 +291,11 @@ def render_image(model: "TransformingSRT", z, camera_pos, rays, extras, max_num_
     the chunks (GTA_FLAG_KV_READY), so a chunk costs the query side plus the attention kernel only.
     ``input_views``: per-scene numbers of valid input views (``TransformingSRT.forward``); the cached images are then the masked ones.
     ``input_mask``: a bool mask over the scene tokens (``TransformingSRT.forward``) instead: every layer's cache then holds the compacted
-    images with the indices and lengths they were built under."""
+    images with the indices and lengths they were built under.  ``input_mask_generic`` (only with ``input_mask``): as in
+    ``TransformingSRT.forward`` -- the layouts without a fused kernel then cache the compacted images of the staged generic forward."""
     from .gta import make_2dcoord
+    if input_mask_generic and input_mask is None:
+        raise native.GtaError("input_mask_generic=True comes with input_mask")
     B, h, w = rays.shape[:3]
     coord = torch.from_numpy(make_2dcoord(h, w)).to(z.device).flatten(0, 1)[None].expand(B, -1, -1)   # [B,h*w,2]
     rays = rays.flatten(1, 2)
@@ -296,6 +308,8 @@ def render_image(model: "TransformingSRT", z, camera_pos, rays, extras, max_num_
         if input_views is not None:
             raise native.GtaError("input_mask with input_views: a call takes one key mask -- a prefix of views is a mask too")
         ex["key_mask"] = _token_mask(input_mask)
+    if input_mask_generic:
+        ex["key_mask_generic"] = True
     if reuse_kv:
         ex["gta_kv_cache"] = {}
     for i in range(0, h * w, max_num_rays):

@@ -381,6 +381,23 @@ int gta_attn_fwd_gather(const GtaAttnDesc* desc, const void* q, const void* k, c
                         const float* trans_coeff, const float* tau, const int32_t* key_idx, const int32_t* key_lens, void* out, float* lse,
                         void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The same on the staged generic layouts (gta_attention's key_mask with key_mask_generic): gta_attn_fwd_staged_varlen whose pre-pass runs in
+ * its GATHER instances.  Image row r of tile j of scene b is built from token tok = key_idx[b, 64 j + r]: its K / V rows, the view record of
+ * view tok / P, its cs_k and coord_k rows; under GTA_FLAG_EUCLID its bias -0.5 scale |k'|^2 is stored at the COMPACTED position 64 j + r of
+ * (b, h), where the attention step streams it.  Rows at or past key_lens[b] in the last written tile are zero rows with bias 0.0; the tiles
+ * past it are not written.  The attention step is the VARLEN gta_gen_attn_kernel as it is.
+ *   key_idx, key_lens: as in gta_attn_fwd_gather (either NULL: GTA_E_BADARG; key_idx may be NULL under GTA_FLAG_KV_READY, which does not
+ *       read it).  Tokens no index names are never loaded: their k, v, cs_k and coord_k rows may hold anything, NaN and Inf included; the
+ *       vrep_k record of a view without a named token is never read.
+ *   gta_attn_fwd_staged_gather_supported: what gta_attn_fwd_staged_supported answers.  Forward only.
+ *   Every other argument, check and error code: as in gta_attn_fwd_staged_varlen. */
+int gta_attn_fwd_staged_gather_supported(const GtaAttnDesc* desc);
+int gta_attn_fwd_staged_gather(const GtaAttnDesc* desc, const void* q, const void* k, const void* v,
+                               const float* vrep_q, const float* vrep_k, const float* cs_q, const float* cs_k,
+                               const float* coord_q, const float* coord_k, const float* trans_coeff, const float* tau,
+                               const int32_t* key_idx, const int32_t* key_lens, void* out, float* lse,
+                               void* workspace, int64_t workspace_bytes, void* stream);
+
 /* A query-side mask beside the key mask (gta_attention's query_mask): gta_attn_fwd_gather whose attention step runs in the QMASK twins of the
  * VARLEN gta_fwd2_kernel instances (every layout, head size and input type those exist for; one workgroup per work item).
  *   q_live: [B, Tq] uint8 on the device (the storage of a bool tensor), non-zero = the query row is live.  NULL: GTA_E_BADARG.

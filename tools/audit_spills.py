@@ -364,12 +364,13 @@ def audit_gen():
     text = _asm("gta_fwd_gen.hip", ("-fno-slp-vectorize",))
     report, problems = [], []
     for name, groups, body, vgpr in _kernels(text, r"gta_gen_(prep|attn)_kernelILi(\d+)E(?:Lb(\d)E)(?:Lb(\d)E)?"):
-        # template arguments: prep <DHP, VARLEN>, attn <DHP, BIAS, VARLEN>
+        # template arguments: prep <DHP, VARLEN[, key_idx]>, attn <DHP, BIAS, VARLEN>
         kind, dhp, b1, b2 = re.search(r"gta_gen_(prep|attn)_kernelILi(\d+)E(?:Lb(\d)E)(?:Lb(\d)E)?", name).groups()
         bias, varlen = (b1, b2) if kind == "attn" else ("0", b1)
         dhp = int(dhp)
-        lds = (2 * 64 * (dhp + 1) * 4 + 2 * 64 * dhp * 2) if kind == "prep" else 3 * 2 * 64 * dhp * 2 + (3 * 4 * 256 if bias == "1" else 0)
-        row = {"kernel": f"gta_gen_{kind}_kernel<{dhp}{', bias' if bias == '1' else ''}{', varlen' if varlen == '1' else ''}>", "vgpr": vgpr, "scratch": body.count("scratch_"),
+        gather = kind == "prep" and "JPKiEE" in name      # the VARLEN pre-pass with the trailing key_idx argument (gta_attn_fwd_staged_gather): + its 256-byte row of token numbers
+        lds = (2 * 64 * (dhp + 1) * 4 + 2 * 64 * dhp * 2 + (256 if gather else 0)) if kind == "prep" else 3 * 2 * 64 * dhp * 2 + (3 * 4 * 256 if bias == "1" else 0)
+        row = {"kernel": f"gta_gen_{kind}_kernel<{dhp}{', bias' if bias == '1' else ''}{', varlen' if varlen == '1' else ''}{', gather' if gather else ''}>", "vgpr": vgpr, "scratch": body.count("scratch_"),
                "lds_bytes": lds, "sgpr_spill_writes": body.count("v_writelane")}
         report.append(row)
         if row["scratch"]:                                # (a hard failure, not a "perf:" warning: these kernels have no spill to tolerate)

@@ -6,7 +6,7 @@ Compiles every kernel source of gta_amd/csrc in both trees to gfx950 assembly wi
 the instruction streams (comments, directives and the numbering of local labels dropped; other symbols replaced by a placeholder).  A
 function is matched by its demangled name; against an OLD_TREE from before the templates gained their defaulted VARLEN argument, a trailing
 `false` of those is ignored and their `true` instances are counted as new (so are the instances with a trailing argument type: the GATHER
-instances of gta_kv_prep_kernel, the q_lens / dlse / (q_lens, q_live) instances of gta_bwd_prep_kernel, the QMASK instances
+instances of gta_kv_prep_kernel and of gta_gen_prep_kernel, the q_lens / dlse / (q_lens, q_live) instances of gta_bwd_prep_kernel, the QMASK instances
 `gta_fwd2_kernel<..., true, unsigned char const*>`; a kernel with a name of its own, as gta_bwd_dkv_gather_kernel or gta_bwd_dq_qmask_kernel, is new anyway).  Exit status 1 when a function of OLD_TREE is missing from NEW_TREE or differs.  Needs hipcc and c++filt."""
 import os
 import re
